@@ -18,6 +18,12 @@ initialised the GPU is ever replaced — and leaves with their exit code; starte
 A step = one frame through Integrator::render (scene + BVH resident in HBM, film left on the device). One ray = one
 Scene::intersect / intersect_p call. Prints ONE JSON line on rank 0. A rank that fails or hangs ends the job with a non-zero
 exit code (3 = watchdog, 4 = a stage failed on some rank; the line, when there is one, is printed first).
+
+A plain run sets up, warms up, times the --steps frames and prints the line (value, ms_per_step, configuration, the ranks'
+reports). --full adds everything that is not the headline figure, untimed, after the steps: the film check, the roofline
+block with its instrumented renders and gather probes, the config-5 and config-4 side blocks, the CPU oracle baseline, the
+one-GPU anchor of the N-GPU curve and (N > 1 over RCCL) the film merge through the C ABI's own communicator.
+--dump-outputs DIR writes what the last timed step computed (rank 0: the film, its ray counts) as .npy files into DIR.
 """
 import argparse
 import json
@@ -48,6 +54,8 @@ TRAFFIC_FILE = os.path.join(ROOT, "profiles", "r05_traffic.json")
 ANCHOR_FILES = [os.path.join(ROOT, "profiles", f) for f in ("r05_bench_line.json", "r04_bench_line.json")]
 # what a stamped counter profile was measured on: the kernels, and what decides the workload they were given
 KERNEL_SOURCES = ("pbrt-rs_amd/csrc", "pbrt-rs_amd/build.sh", "bench.py", "pbrt-rs_amd/pbrt_hip/scenes.py")
+# --dump-outputs: a film larger than this is written as a fixed, seeded sample of its pixels (4K x 4 channels is 133 MB)
+DUMP_LIMIT_BYTES = 48 << 20
 
 
 def parse(argv=None):
@@ -73,10 +81,10 @@ def parse(argv=None):
                          "weak: the frame has spp x N samples per pixel (per-GPU work fixed)")
     ap.add_argument("--tile-order", choices=("morton", "row-major"), default="morton",
                     help="order in which the 16x16 tiles are dealt to the ranks (PbrtRenderParams.tile_order; SURVEY 8(e): Morton)")
-    ap.add_argument("--abi-reduce-check", action="store_true", help="(default at N > 1 over RCCL; kept for old command lines)")
+    ap.add_argument("--abi-reduce-check", action="store_true", help="(default at N > 1 over RCCL under --full; kept for old command lines)")
     ap.add_argument("--no-abi-reduce-check", action="store_true",
                     help="skip the untimed repeat of the film merge through the C ABI's own RCCL communicator (pbrt_hip_comm_create / "
-                         "pbrt_hip_film_reduce), which otherwise runs after the measurement at N > 1 and is compared with torch.distributed's")
+                         "pbrt_hip_film_reduce), which otherwise runs after the measurement at N > 1 under --full and is compared with torch.distributed's")
     ap.add_argument("--abi-check-timeout-s", type=float, default=120.0,
                     help="the ABI reduce check may take this long; after that the measured line is printed with abi_film_reduce = TIMEOUT")
     ap.add_argument("--abi-check-strict", action="store_true",
@@ -94,7 +102,18 @@ def parse(argv=None):
                          "failure); torchrun = one child `python -m torch.distributed.run --nproc-per-node N` (its exit code is 1 for any failure)")
     ap.add_argument("--save-film", default="", help="rank 0 writes the reduced film of the last step here (.npy)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the untimed config-5 and config-4 blocks (N = 1, config 3 only)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the untimed checks and diagnostics: film check, roofline, config-5 / config-4 "
+                         "blocks, CPU baseline, N-GPU anchor, ABI reduce check at N > 1 (off: only what the headline figure needs)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the last timed step computed into DIR: film.npy (float32, H x W x 4; a fixed seeded "
+                         "pixel sample when the film exceeds %d MB) and rays.npy (float64: rank 0's closest and shadow rays)" % (DUMP_LIMIT_BYTES >> 20))
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 def resolve_workload(args, world):
@@ -372,6 +391,27 @@ def check_film_weights(weights, spp):
     return {"pixels": int(w * h), "spp": int(spp), "weight_sum": total, "expected": expected, "excess": total - expected,
             "pixels_off": off, "min": float(weights.min()), "max": float(weights.max()),
             "ok": bool(off == 0 and 0.0 <= total - expected <= 1e-3 * expected)}
+
+
+def dump_outputs(out_dir, film, step_stats, limit_bytes=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the timed path returned in its last step. film.npy = the film (H x W x 4 float32: RGB sums and the
+    filter-weight sum; at N > 1 the film reduced on rank 0) and rays.npy = [rays_closest, rays_shadow] of rank 0's render call
+    (float64). A film larger than limit_bytes is written as a sample instead: the same pixels every run (seed 0, sorted), as
+    film.npy (n x 4) and pixel_index.npy (float64 y * W + x). Returns the names written."""
+    os.makedirs(out_dir, exist_ok=True)
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    h, w, c = film.shape
+    arrays = {"rays": np.array([step_stats["rays_closest"], step_stats["rays_shadow"]], dtype=np.float64)}
+    if film.nbytes <= limit_bytes:
+        arrays["film"] = film
+    else:
+        n = limit_bytes // (c * 4 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(h * w, size=n, replace=False))
+        arrays["film"] = film.reshape(h * w, c)[idx]
+        arrays["pixel_index"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def scaling_anchor(config_name):
@@ -719,7 +759,9 @@ def run_rank(args):
                                              reduce_staged if (staged and use_dist) else None)
             if args.save_film and rank == 0:
                 np.save(args.save_film, last.cpu().numpy())
-            if rank == 0:   # untimed: the merged film of the last step holds every sample of the frame exactly once
+            if args.dump_outputs and rank == 0:
+                dump_outputs(args.dump_outputs, last.cpu().numpy(), stats[-1])
+            if rank == 0 and args.full:   # untimed: the merged film of the last step holds every sample of the frame exactly once
                 film_check[0] = check_film_weights(last[..., 3].double().cpu().numpy(), spp_total)
             return (seconds, sum(st["rays_closest"] + st["rays_shadow"] for st in stats), sum(st["trace_ms"] for st in stats),
                     sum(st["trace_launches"] for st in stats), stats)
@@ -775,7 +817,7 @@ def run_rank(args):
             out["config"]["film_check"] = film_check[0]
             if film_check[0] and not film_check[0]["ok"]:
                 out.setdefault("warnings", []).append("film_check failed: the merged film does not hold every sample once")
-            anchor = scaling_anchor(config_name) if world > 1 else None
+            anchor = scaling_anchor(config_name) if (world > 1 and args.full) else None
             if anchor:
                 out["scaling_vs_config4_n1"] = dict(anchor, ratio=round(value / anchor["value"], 3),
                                                     note="this job's rate over the one-GPU rate of the same frame from ANOTHER run (see source): a reading aid; "
@@ -886,7 +928,8 @@ def run_rank(args):
                 return roofline, cpu_baseline, secondary, config4_n1
 
             try:
-                out["roofline"], out["cpu_baseline"], out["secondary"], out["config4_n1"] = diagnostics()
+                if args.full:   # a plain run stops at the measured line: these blocks stay None
+                    out["roofline"], out["cpu_baseline"], out["secondary"], out["config4_n1"] = diagnostics()
             except Exception as e:  # noqa: BLE001 - the measurement stands
                 try:
                     ctx.set_counting(0)
@@ -897,7 +940,7 @@ def run_rank(args):
                 out.setdefault("warnings", []).append(f"untimed diagnostics failed ({type(e).__name__}: {e}); value and timing are unaffected")
                 print(f"[bench rank {rank}] untimed diagnostics failed: {type(e).__name__}: {e}", file=sys.stderr, flush=True)
 
-        want_abi_check = args.abi_reduce_check or (world > 1 and not args.no_abi_reduce_check)
+        want_abi_check = args.abi_reduce_check or (world > 1 and args.full and not args.no_abi_reduce_check)
         if want_abi_check and use_dist and not staged:
             # Untimed, after the measured line is assembled: the same film merge through the C ABI's own RCCL communicator
             # (pbrt_hip_comm_create / pbrt_hip_film_reduce), checked against torch.distributed's reduce. The measurement does

@@ -337,3 +337,36 @@ def test_ranks_do_not_outlive_the_parent(tmp_path):
         while time.time() < deadline and any(alive(p) for p in pids):
             time.sleep(0.1)
         assert not any(alive(p) for p in pids), (sig, pids)
+
+
+def test_plain_run_options():
+    """A plain command line runs only what the headline figure needs (--full off, no dump); --steps is the number of timed
+    steps and must be at least one."""
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, "")
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse(bad)
+
+
+def test_dump_outputs_writes_the_film_and_a_fixed_sample_of_a_large_one(tmp_path):
+    """--dump-outputs: the film of the last step as float32 and the ray counts as float64; above the size limit a sample of
+    pixels that is the same from run to run, with the pixels it took."""
+    import numpy as np
+    film = np.random.default_rng(5).random((36, 64, 4)).astype(np.float32)
+    stats = {"rays_closest": 1234, "rays_shadow": 567}
+    assert bench.dump_outputs(str(tmp_path / "a"), film, stats) == ["film", "rays"]
+    got = np.load(tmp_path / "a" / "film.npy")
+    assert got.dtype == np.float32 and got.tobytes() == film.tobytes()
+    rays = np.load(tmp_path / "a" / "rays.npy")
+    assert rays.dtype == np.float64 and rays.tolist() == [1234.0, 567.0]
+    limit = 24 * 100   # 100 pixels of 4 float32 channels + a float64 index each
+    for d in ("b", "c"):
+        assert bench.dump_outputs(str(tmp_path / d), film, stats, limit_bytes=limit) == ["film", "pixel_index", "rays"]
+    sample, idx = np.load(tmp_path / "b" / "film.npy"), np.load(tmp_path / "b" / "pixel_index.npy")
+    assert sample.dtype == np.float32 and sample.shape == (100, 4) and idx.dtype == np.float64
+    assert np.all(np.diff(idx) > 0) and sample.tobytes() == film.reshape(-1, 4)[idx.astype(np.int64)].tobytes()
+    assert sample.nbytes + idx.nbytes <= limit
+    assert np.load(tmp_path / "c" / "pixel_index.npy").tobytes() == idx.tobytes()

@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 W, H, SPP, TRIS, DEPTH = 256, 144, 8, 20000, 5
 ARGS = ["--gpus", "2", "--steps", "1", "--warmup", "1", "--dist-backend", "gloo", "--one-gpu", "--width", str(W), "--height", str(H),
         "--spp", str(SPP), "--tris", str(TRIS), "--max-depth", str(DEPTH), "--spp-per-pass", str(SPP), "--no-cpu-baseline",
-        "--watchdog-s", "240"]
+        "--watchdog-s", "240", "--full"]
 
 
 def _free_port():
@@ -140,7 +140,7 @@ def test_config5_job_on_two_ranks_equals_the_one_process_frame(hip_ctx, tmp_path
     film_path = str(tmp_path / "film5.npy")
     args = ["--config", "5", "--gpus", "2", "--steps", "1", "--warmup", "1", "--dist-backend", "gloo", "--one-gpu", "--width", str(w),
             "--height", str(h), "--spp", str(spp), "--spp-per-pass", "2", "--tris", str(tris), "--instances", str(inst), "--no-cpu-baseline",
-            "--watchdog-s", "240", "--save-film", film_path]
+            "--watchdog-s", "240", "--save-film", film_path, "--full"]
     env = _env()
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -203,7 +203,7 @@ def test_a_failure_in_the_untimed_diagnostics_does_not_take_the_line():
         env.pop(k, None)
     env["PBRT_BENCH_FAIL"] = "diagnostics@0"
     args = ["--steps", "1", "--warmup", "1", "--width", str(W), "--height", str(H), "--spp", str(SPP), "--tris", str(TRIS), "--max-depth", str(DEPTH),
-            "--no-cpu-baseline", "--no-secondary", "--watchdog-s", "240"]
+            "--no-cpu-baseline", "--no-secondary", "--watchdog-s", "240", "--full"]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, cwd=ROOT, env=env, capture_output=True, text=True, timeout=540)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

@@ -8,7 +8,7 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
 OUT=gpurun_out/traffic
 rm -rf $OUT; mkdir -p $OUT profiles
-CMD="python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary"
+CMD="python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary"
 timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o stats -- $CMD > $OUT/stats.log 2>&1 || { tail -5 $OUT/stats.log; exit 1; }
 grep '^{' $OUT/stats.log | tail -1 > $OUT/bench_line_under_rocprof.json
 for C in FETCH_SIZE WRITE_SIZE; do
@@ -91,7 +91,7 @@ rec = {
     "commit": os.environ.get("PB_COMMIT", commit), "source_hash": bench.kernel_source_hash(),
     "profile": "profiles/r05_bench_kernel_stats.csv + rocprofv3 --kernel-trace --pmc passes (FETCH_SIZE; WRITE_SIZE; SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU "
                "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_INSTS_SALU GRBM_GUI_ACTIVE; TA_TA_BUSY_sum GRBM_GUI_ACTIVE — one run each) on "
-               "`python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-secondary`; FETCH_SIZE = TCC_EA0_RDREQ x 64 B (Infinity-Cache hits "
+               "`python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-secondary`; FETCH_SIZE = TCC_EA0_RDREQ x 64 B (Infinity-Cache hits "
                "included), used without the x2 of wide coalesced streams: calibrated on this gather pattern in "
                "profiles/r01_fetch_size_calibration.txt (0.986)",
 }

@@ -285,6 +285,18 @@ int pbrt_hip_scene_create(PbrtHipContext* ctx, const float* positions, int32_t n
  * the scene was created from. Call once, after scene creation; any of the three pointers may be NULL. */
 int pbrt_hip_scene_set_shading_data(PbrtHipScene* scene, const float* positions, int32_t n_verts, const int32_t* indices,
                                     int32_t n_tris, const float* normals, const float* tangents, const float* uvs);
+/* InfiniteAreaLight::new(light_to_world, L, n_samples, texmap) (src/lights/infinite.rs:36-82) with the texels in memory:
+ * attaches an image environment map to light `light` (a PBRT_LIGHT_INFINITE light of this scene; without a map it keeps the
+ * constant map L). rgb: width x height RGB float32 texels, row-major, row 0 = theta 0 = light-space +z, column 0 = phi 0;
+ * they are multiplied by the light's L, resampled to powers of two and sampled by their sin-weighted luminance
+ * (pbrt_hip_envmap_tables). light_to_world: row-major 4x4, last row (0,0,0,1), not singular; le() looks the map up along
+ * normalize(world_to_light d) and sample_li() returns light_to_world v unnormalised, as the reference does, so only rigid
+ * transforms give an unbiased estimate. The light's power and the power light distribution are recomputed and a spatial
+ * light distribution already built is rebuilt by the next render that uses it. Calling it again replaces the map.
+ * PBRT_HIP_ERR_INVALID (pbrt_hip_last_error says why, the scene unchanged) for a bad light index or type, a non-finite,
+ * singular or non-affine transform, or texels pbrt_hip_envmap_tables refuses. */
+int pbrt_hip_scene_set_environment_map(PbrtHipScene* scene, int32_t light, const float* rgb, int32_t width, int32_t height,
+                                       const float light_to_world[16]);
 /* Scene with spheres next to the triangles (src/shapes/sphere.rs:38-92, 228-284 with src/core/efloat.rs; BASELINE
  * config 1): n_spheres full spheres {centre.xyz, radius}, i.e. Sphere::new with object_to_world = translate(centre).
  * Sphere i is primitive n_tris + i in prim_order; nodes come from pbrt_hip_bvh_build_boxes over the primitives' world
@@ -503,6 +515,17 @@ enum PbrtFilterType { PBRT_FILTER_BOX = 0, PBRT_FILTER_GAUSSIAN = 1, PBRT_FILTER
 int pbrt_hip_filter_table(int32_t type, float radius_x, float radius_y, float a, float b, float table256[256]);
 /* Film::get_sample_bounds (src/core/film.rs:76-81) of the whole film: {x0, y0, x1, y1}. Host only. */
 int pbrt_hip_sample_bounds(int32_t width, int32_t height, float radius_x, float radius_y, int32_t bounds[4]);
+/* InfiniteAreaLight::new's tables for an image map (src/lights/infinite.rs:36-82 over src/core/mipmap.rs:76-296 and
+ * src/core/sampling.rs:62-215), what pbrt_hip_scene_set_environment_map uploads. Host only.
+ * rgb: width x height RGB texels (see there), L: the light's radiance scale. Two calls: with level0_rgb, dist_func and
+ * power_rgb all NULL only *res_w, *res_h (the power-of-two size of level 0) are written; then level0_rgb
+ * (res_w * res_h * 3: the texels x L, Lanczos-resampled where a side is not a power of two), dist_func
+ * ((2 res_w) x (2 res_h), row-major: lookup((u+.5)/2W, (v+.5)/2H), 0.5/min(2W, 2H)).y * sin(pi (v+.5)/2H)) and power_rgb
+ * (lookup((.5, .5), .5), before InfiniteAreaLight::power's pi r^2); any of the three may be NULL. PBRT_HIP_ERR_INVALID for a
+ * null pointer, width or height < 1, a table past 2^28 texels, or a non-finite or negative texel or L; *reason (may be NULL)
+ * then says which. */
+int pbrt_hip_envmap_tables(const float* rgb, int32_t width, int32_t height, const float L[3], int32_t* res_w, int32_t* res_h,
+                           float* level0_rgb, float* dist_func, float power_rgb[3], const char** reason);
 /* Image output: Film::write_image ends in a file writer that is todo!() in the reference
  * (src/core/imageio.rs:3-5); this writes the RGB image as a little-endian PFM (top row first in memory). */
 int pbrt_hip_write_pfm(const char* path, const float* rgb, int32_t width, int32_t height);

@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "host_envmap.h"
 #include "host_wide.h"
 #include "scene.h"
 #include "trace.h"
@@ -1129,9 +1130,137 @@ extern "C" void pbrt_hip_scene_destroy(PbrtHipScene* s) {
     if (!s->ctx->lost) {  // a lost context: an abandoned kernel may still read the scene, and waiting for it may never end
         (void)hipStreamSynchronize(s->ctx->stream);
         for (void* p : s->allocs) (void)hipFree(p);
+        for (auto& a : s->env_allocs)
+            for (void* p : a) (void)hipFree(p);
     }
     delete s;
 }
+
+// InfiniteAreaLight::new(light_to_world, L, n_samples, texmap) (lights/infinite.rs:36-82) with the texels in memory: the map's
+// tables (host_envmap.cpp) go to the device for light `light`, its power and the power distribution are recomputed, and a
+// spatial light table already built is dropped (the next render with that strategy builds it again).
+extern "C" int pbrt_hip_scene_set_environment_map(PbrtHipScene* s, int32_t light, const float* rgb, int32_t width, int32_t height,
+                                                  const float light_to_world[16]) try {
+    if (!s) return PBRT_HIP_ERR_INVALID;
+    PbrtHipContext* ctx = s->ctx;
+    PB_ENTER(ctx);
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = "pbrt_hip_scene_set_environment_map: " + why;
+        return PBRT_HIP_ERR_INVALID;
+    };
+    if (light < 0 || light >= s->d.n_lights) return invalid("light index out of range");
+    if (s->h_lights[light].type != PBRT_LIGHT_INFINITE) return invalid("light is not PBRT_LIGHT_INFINITE");
+    if (!light_to_world) return invalid("null light_to_world");
+    const float* m = light_to_world;
+    for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(m[k])) return invalid("light_to_world is not finite");
+    if (m[12] != 0.0f || m[13] != 0.0f || m[14] != 0.0f || m[15] != 1.0f) return invalid("light_to_world's last row is not (0, 0, 0, 1)");
+    // world_to_light's directions: the inverse of the upper 3x3, in double
+    double a[9];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) a[3 * r + c] = m[4 * r + c];
+    double inv[9] = {a[4] * a[8] - a[5] * a[7], a[2] * a[7] - a[1] * a[8], a[1] * a[5] - a[2] * a[4],
+                     a[5] * a[6] - a[3] * a[8], a[0] * a[8] - a[2] * a[6], a[2] * a[3] - a[0] * a[5],
+                     a[3] * a[7] - a[4] * a[6], a[1] * a[6] - a[0] * a[7], a[0] * a[4] - a[1] * a[3]};
+    double det = a[0] * inv[0] + a[1] * inv[3] + a[2] * inv[6];
+    DevEnvMap e{};
+    for (int k = 0; k < 9; ++k) {
+        e.l2w[k] = (float)a[k];
+        e.w2l[k] = det != 0.0 ? (float)(inv[k] / det) : 0.0f;
+        if (det == 0.0 || !std::isfinite(e.w2l[k])) return invalid("light_to_world is singular");
+    }
+    EnvTables t;
+    if (const char* why = envmap_build(rgb, width, height, s->h_lights[light].L, &t)) return invalid(why);
+
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<void*> fresh;
+    auto release = [&]() {
+        for (void* p : fresh) (void)hipFree(p);
+    };
+    auto upload = [&](const void* src, size_t bytes) -> void* {
+        void* p = nullptr;
+        if (!hip_ok(ctx, hipMalloc(&p, bytes), "hipMalloc environment map")) return nullptr;
+        fresh.push_back(p);
+        if (!hip_ok(ctx, hipMemcpy(p, src, bytes, hipMemcpyHostToDevice), "hipMemcpy environment map")) return nullptr;
+        return p;
+    };
+    std::vector<float4> texels((size_t)t.w * t.h);
+    for (size_t i = 0; i < texels.size(); ++i) texels[i] = make_float4(t.level0[3 * i], t.level0[3 * i + 1], t.level0[3 * i + 2], 0.0f);
+    e.texels = (const float4*)upload(texels.data(), texels.size() * sizeof(float4));
+    e.func = e.texels ? (const float*)upload(t.func.data(), t.func.size() * sizeof(float)) : nullptr;
+    e.cdf = e.func ? (const float*)upload(t.cdf.data(), t.cdf.size() * sizeof(float)) : nullptr;
+    e.row_int = e.cdf ? (const float*)upload(t.row_int.data(), t.row_int.size() * sizeof(float)) : nullptr;
+    e.marg_cdf = e.row_int ? (const float*)upload(t.marg_cdf.data(), t.marg_cdf.size() * sizeof(float)) : nullptr;
+    if (!e.marg_cdf) {
+        release();
+        return PBRT_HIP_ERR_DEVICE;
+    }
+    e.marg_int = t.marg_int;
+    e.w = t.w;
+    e.h = t.h;
+    e.nu = t.nu;
+    e.nv = t.nv;
+    const int n = s->d.n_lights;
+    if (!s->d.env_maps) {
+        void* p = nullptr;
+        if (!hip_ok(ctx, hipMalloc(&p, (size_t)n * sizeof(DevEnvMap)), "hipMalloc environment maps")) {
+            release();
+            return PBRT_HIP_ERR_DEVICE;
+        }
+        s->allocs.push_back(p);
+        s->d.env_maps = (const DevEnvMap*)p;
+        s->h_env.assign(n, DevEnvMap{});
+        s->env_allocs.assign(n, {});
+    }
+    // the light itself: its map, and InfiniteAreaLight::power (infinite.rs:131-133) for the power distribution
+    DevLight lt = s->h_lights[light];
+    lt.slot = light;
+    const float scale = kPi * s->d.world_radius * s->d.world_radius;
+    float p[3] = {t.power_rgb[0] * scale, t.power_rgb[1] * scale, t.power_rgb[2] * scale};
+    lt.power_y = 0.212671f * p[0] + 0.715160f * p[1] + 0.072169f * p[2];
+    std::vector<float> power_y(n), cdf;
+    for (int i = 0; i < n; ++i) power_y[i] = i == light ? lt.power_y : s->h_lights[i].power_y;
+    float fi;
+    make_distribution(power_y, &cdf, &fi);
+    std::vector<DevEnvMap> h_env = s->h_env;
+    h_env[light] = e;
+    std::vector<float> old_power_y(n), old_cdf;
+    for (int i = 0; i < n; ++i) old_power_y[i] = s->h_lights[i].power_y;
+    float old_fi;
+    make_distribution(old_power_y, &old_cdf, &old_fi);
+    // the device copies of the descriptors, the light and the power distribution, from one consistent host state
+    auto write_state = [&](const std::vector<DevEnvMap>& env, const DevLight& l, const std::vector<float>& py, const std::vector<float>& pc) {
+        return hip_ok(ctx, hipMemcpy((void*)s->d.env_maps, env.data(), (size_t)n * sizeof(DevEnvMap), hipMemcpyHostToDevice), "hipMemcpy") &&
+               hip_ok(ctx, hipMemcpy((void*)(s->d.lights + light), &l, sizeof(DevLight), hipMemcpyHostToDevice), "hipMemcpy") &&
+               hip_ok(ctx, hipMemcpy((void*)s->d.light_distrib_power.func, py.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy") &&
+               hip_ok(ctx, hipMemcpy((void*)s->d.light_distrib_power.cdf, pc.data(), (size_t)(n + 1) * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy");
+    };
+    if (!write_state(h_env, lt, power_y, cdf)) {
+        // put the previous state back; if that fails as well the device may still point at the new arrays: they then stay
+        // allocated until the scene is destroyed instead of being freed under a descriptor that names them
+        std::string why = ctx->last_error;
+        if (write_state(s->h_env, s->h_lights[light], old_power_y, old_cdf)) {
+            release();
+        } else {
+            s->allocs.insert(s->allocs.end(), fresh.begin(), fresh.end());
+        }
+        ctx->last_error = why;
+        return PBRT_HIP_ERR_DEVICE;
+    }
+    s->d.light_distrib_power.func_int = fi;
+    for (void* q : s->env_allocs[light]) (void)hipFree(q);  // a map set before on this light
+    s->env_allocs[light].swap(fresh);
+    s->h_env.swap(h_env);
+    s->h_lights[light] = lt;
+    if (s->d_spatial) {
+        (void)hipFree(s->d_spatial);
+        s->allocs.erase(std::remove(s->allocs.begin(), s->allocs.end(), (void*)s->d_spatial), s->allocs.end());
+        s->d_spatial = nullptr;
+    }
+    return PBRT_HIP_OK;
+}
+PB_ABI_CATCH
 
 // ------------------------------------------------------------------------------------
 // batch intersect

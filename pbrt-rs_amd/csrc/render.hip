@@ -773,6 +773,7 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
     sc.n_lights = s->d.n_lights;
     sc.n_infinite = s->d.n_infinite;
     sc.infinite_ids = s->d.infinite_ids;
+    sc.env_maps = s->d.env_maps;
     // create_light_sample_distribution (lightdistrib.rs:222-232): "uniform", or one light -> uniform
     sc.distrib = (rp.light_strategy == 0 || s->d.n_lights == 1) ? s->d.light_distrib_uniform : s->d.light_distrib_power;
     if (rp.integrator == PBRT_INTEGRATOR_PATH && (rp.light_strategy < 0 || rp.light_strategy > 2))

@@ -85,7 +85,7 @@ constexpr int kWorkCounters = 16, kFollowUpCounter = 8, kSpecialCount = 12;
 struct DevLight {
     int type;       // PbrtLightType
     float L[3];
-    int slot;       // area light: leaf slot of its triangle
+    int slot;       // area light: leaf slot of its triangle; infinite light: its DevEnvMap (= its own index) or -1 (constant map)
     int two_sided;
     float area;     // Triangle::area (triangle.rs:323-328)
     float power_y;  // Light::power().y_value() for the power distribution
@@ -109,6 +109,19 @@ struct DevDistribution1D {
     int n;
 };
 
+// InfiniteAreaLight with an image map (pbrt_hip_scene_set_environment_map; lights/infinite.rs:36-82): level 0 of the
+// MIPMap (the lookups are bilinear there) and the 2w x 2h sin-weighted Distribution2D (host_envmap.cpp). One per light.
+struct DevEnvMap {
+    const float4* texels;   // w * h, row t = 0 is theta = 0 (light-space +z)
+    const float* func;      // nv * nu: the conditional rows (nu = 2w, nv = 2h)
+    const float* cdf;       // nv * (nu + 1)
+    const float* row_int;   // nv: the rows' integrals = the marginal's function
+    const float* marg_cdf;  // nv + 1
+    float marg_int;
+    int w, h, nu, nv;
+    float w2l[9], l2w[9];  // upper 3x3 of world_to_light / light_to_world, row-major
+};
+
 struct DevSceneData {
     DevBVH bvh;
     const int* slot_prim;       // leaf slot -> caller's triangle index
@@ -124,6 +137,7 @@ struct DevSceneData {
     float env_marg_func[2], env_marg_cdf[3], env_marg_int;
     float world_center[3], world_radius;  // lights/infinite.rs:135-139
     DevDistribution1D light_distrib_uniform, light_distrib_power;
+    const DevEnvMap* env_maps;  // [n_lights] once a map was set (DevLight::slot names the entry), else null
 };
 
 }  // namespace pb
@@ -136,6 +150,9 @@ struct PbrtHipScene {
     int spill_lanes = 0;
     std::vector<pb::DevLight> h_lights;
     std::vector<int> light_samples;  // max(1, n_samples) per light (light.rs:76)
+    // image maps of infinite lights (pbrt_hip_scene_set_environment_map): per light its descriptor and its device arrays
+    std::vector<pb::DevEnvMap> h_env;
+    std::vector<std::vector<void*>> env_allocs;
     // SpatialLightDistribution tables (lightdistrib.rs:76-220), built on first use by a render with that strategy
     float* d_spatial = nullptr;
     int spatial_voxels[3] = {0, 0, 0};

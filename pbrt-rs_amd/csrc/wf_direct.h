@@ -126,7 +126,12 @@ __global__ void __launch_bounds__(256, PB_DIRECT_WAVES) k_shade_direct(ShadeCons
                     // Σ light.le(ray): only infinite lights emit on a miss (AO: nothing, ao.rs:66)
                     for (int k = 0; k < sc.n_infinite && mode != PBRT_INTEGRATOR_AO; ++k) {
                         DevLight lt = sc.lights[sc.infinite_ids[k]];
-                        L = L + mulv(T, V3{lt.L[0], lt.L[1], lt.L[2]});
+                        V3 le = V3{lt.L[0], lt.L[1], lt.L[2]};
+                        if (lt.slot >= 0) {
+                            float4 r1 = ps.ray[rbase + 1];
+                            le = env_le(sc.env_maps[lt.slot], V3{r0.w, r1.x, r1.y});
+                        }
+                        L = L + mulv(T, le);
                     }
                     stage = 0xfffe;  // nothing more at this vertex: unwind
                 } else {

@@ -168,6 +168,23 @@ PB_DEV void light_sample_li(const ShadeConsts& sc, const Surf& sf, const DevLigh
         light_pdf = 1.0f;
         p1 = sf.p + wi * (2.0f * sc.world_radius);
         li = Lc;
+    } else if (lt.slot >= 0) {
+        // InfiniteAreaLight::sample_li (infinite.rs:96-129) with an image map: light_to_world on the direction, not
+        // renormalised (rigid transforms only give an unbiased estimate, as in the reference)
+        const DevEnvMap& e = sc.env_maps[lt.slot];
+        float d0, d1, map_pdf;
+        env_sample(e, ul0, ul1, &d0, &d1, &map_pdf);
+        if (map_pdf != 0.0f) {
+            float theta = d1 * kPi, phi = d0 * 2.0f * kPi;
+            float st, ct, sp, cp;
+            det_sincos(theta, &st, &ct);
+            det_sincos(phi, &sp, &cp);
+            wi = mat3_mul(e.l2w, V3{st * cp, st * sp, ct});
+            light_pdf = map_pdf / (2.0f * kPi * kPi * st);
+            if (st == 0.0f) light_pdf = 0.0f;
+            p1 = sf.p + wi * (2.0f * sc.world_radius);
+            li = env_lookup(e, d0, d1);
+        }
     } else {
         // InfiniteAreaLight::sample_li (infinite.rs:96-129)
         float pdf1, pdf0;
@@ -338,6 +355,8 @@ PB_DEV int estimate_direct_emit(const ShadeConsts& sc, const PathState& ps, uint
                 lpdf = len2(sf.p - ph) / (absdot(nh, -wi2) * lt.area);
                 if (__builtin_isinf(lpdf)) lpdf = 0.0f;
             }
+        } else if (lt.slot >= 0) {
+            lpdf = env_pdf(sc.env_maps[lt.slot], wi2);  // InfiniteAreaLight::pdf_li with an image map
         } else {
             // InfiniteAreaLight::pdf_li (infinite.rs:140-151)
             float theta = det_acos(clampf(wi2.z, -1.0f, 1.0f));
@@ -400,7 +419,12 @@ PB_DEV V3 estimate_direct_resolve(const ShadeConsts& sc, const PathState& ps, ui
                 if (lt.two_sided || dot(n, -wi) > 0.0f) li = V3{lt.L[0], lt.L[1], lt.L[2]};
             }
         } else if (lt.type == PBRT_LIGHT_INFINITE) {
-            li = V3{lt.L[0], lt.L[1], lt.L[2]};
+            if (lt.slot >= 0) {  // the MIS ray escaped: the map's le along it
+                float4 r0 = ps.ray[ray_index(ps, p, RS_MIS)], r1 = ps.ray[ray_index(ps, p, RS_MIS) + 1];
+                li = env_le(sc.env_maps[lt.slot], V3{r0.w, r1.x, r1.y});
+            } else {
+                li = V3{lt.L[0], lt.L[1], lt.L[2]};
+            }
         }
         if (!is_black(li)) {
             V3 f = V3{nf.x, nf.y, nf.z};

@@ -120,7 +120,8 @@ __global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, P
                 } else {
                     for (int k = 0; k < sc.n_infinite; ++k) {
                         DevLight lt = sc.lights[sc.infinite_ids[k]];
-                        L = L + mulv(beta, V3{lt.L[0], lt.L[1], lt.L[2]});
+                        V3 le = lt.slot >= 0 ? env_le(sc.env_maps[lt.slot], rd) : V3{lt.L[0], lt.L[1], lt.L[2]};
+                        L = L + mulv(beta, le);
                     }
                 }
             }

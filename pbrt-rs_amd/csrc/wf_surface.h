@@ -313,6 +313,7 @@ struct ShadeConsts {
     const DevLight* lights;
     int n_lights, n_infinite;
     const int* infinite_ids;
+    const DevEnvMap* env_maps;  // image maps of infinite lights (DevLight::slot >= 0), null when there are none
     DevDistribution1D distrib;  // light_distribution.lookup (lightdistrib.rs:43/66)
     float env_cond_func[2][2], env_cond_cdf[2][3], env_cond_int[2];
     float env_marg_func[2], env_marg_cdf[3], env_marg_int;
@@ -328,6 +329,73 @@ struct ShadeConsts {
     // loops are being counted (pbrt_hip_set_counting(1): the reference walks those rays to their closest hit)
     int mis_bool;
 };
+
+// ---- InfiniteAreaLight with an image map (DevEnvMap): one lookup and one Distribution2D for le, sample_li and pdf_li ----
+// MIPMap::lookup at width 0 (mipmap.rs:211-215): MIPMap::triangle on level 0, ImageWrap::Repeat, signed floor (D60)
+PB_DEV V3 env_lookup(const DevEnvMap& e, float st_s, float st_t) {
+    float s = st_s * (float)e.w - 0.5f, t = st_t * (float)e.h - 0.5f;
+    if (!(s >= -1.0f && s <= (float)e.w)) s = -0.5f;  // a NaN direction: keep the fetches inside the level
+    if (!(t >= -1.0f && t <= (float)e.h)) t = -0.5f;
+    float fs = __builtin_floorf(s), ft = __builtin_floorf(t);
+    float ds = s - fs, dt = t - ft;
+    int s0 = (int)fs, t0 = (int)ft;
+    s0 = s0 < 0 ? s0 + e.w : (s0 >= e.w ? s0 - e.w : s0);  // -1 <= s0 <= w, -1 <= t0 <= h
+    t0 = t0 < 0 ? t0 + e.h : (t0 >= e.h ? t0 - e.h : t0);
+    int s1 = s0 + 1 >= e.w ? s0 + 1 - e.w : s0 + 1;
+    int t1 = t0 + 1 >= e.h ? t0 + 1 - e.h : t0 + 1;
+    float4 a = e.texels[(size_t)t0 * e.w + s0], b = e.texels[(size_t)t1 * e.w + s0];
+    float4 c = e.texels[(size_t)t0 * e.w + s1], d = e.texels[(size_t)t1 * e.w + s1];
+    float wa = (1.0f - ds) * (1.0f - dt), wb = (1.0f - ds) * dt, wc = ds * (1.0f - dt), wd = ds * dt;
+    return V3{a.x * wa + b.x * wb + c.x * wc + d.x * wd, a.y * wa + b.y * wb + c.y * wc + d.y * wd,
+              a.z * wa + b.z * wb + c.z * wc + d.z * wd};
+}
+PB_DEV V3 mat3_mul(const float* m, V3 v) {  // Transform * Vector3 (transform.rs), upper 3x3 row-major
+    return V3{m[0] * v.x + m[1] * v.y + m[2] * v.z, m[3] * v.x + m[4] * v.y + m[5] * v.z, m[6] * v.x + m[7] * v.y + m[8] * v.z};
+}
+// spherical (phi / 2pi, theta / pi) of a light-space direction (geometry.rs spherical_phi / spherical_theta); sin(theta)
+PB_DEV void env_uv(V3 wl, float* u, float* v, float* sin_theta) {
+    float theta = det_acos(clampf(wl.z, -1.0f, 1.0f));
+    float phi = det_atan2(wl.y, wl.x);
+    if (phi < 0.0f) phi = phi + 2.0f * kPi;
+    *u = phi * kInv2Pi;
+    *v = theta * kInvPi;
+    if (sin_theta) *sin_theta = det_sin(theta);
+}
+// InfiniteAreaLight::le (infinite.rs:84-88; D33 intended: the light's le) for a world direction
+PB_DEV V3 env_le(const DevEnvMap& e, V3 d) {
+    float u, v;
+    env_uv(normalize(mat3_mul(e.w2l, d)), &u, &v, nullptr);
+    return env_lookup(e, u, v);
+}
+// Distribution1D::sample_continuous (sampling.rs:99-123) over an n-entry table
+PB_DEV float sample_continuous_n(const float* func, const float* cdf, float func_int, int n, float u, float* pdf, int* off) {
+    int offset = find_interval_cdf(cdf, n + 1, u);
+    *off = offset;
+    float c0 = cdf[offset], c1 = cdf[offset + 1];
+    float du = u - c0;
+    if (c1 - c0 > 0.0f) du /= c1 - c0;
+    *pdf = func_int > 0.0f ? func[offset] / func_int : 0.0f;
+    return ((float)offset + du) / (float)n;
+}
+// Distribution2D::sample_continuous (sampling.rs:186-197): (u, v) and the map pdf
+PB_DEV void env_sample(const DevEnvMap& e, float u0, float u1, float* d0, float* d1, float* map_pdf) {
+    float pdf0, pdf1;
+    int v, dummy;
+    *d1 = sample_continuous_n(e.row_int, e.marg_cdf, e.marg_int, e.nv, u1, &pdf1, &v);
+    *d0 = sample_continuous_n(e.func + (size_t)v * e.nu, e.cdf + (size_t)v * (e.nu + 1), e.row_int[v], e.nu, u0, &pdf0, &dummy);
+    *map_pdf = pdf0 * pdf1;
+}
+// InfiniteAreaLight::pdf_li (infinite.rs:140-151; Distribution2D::pdf, sampling.rs:199-212, D48 intended) for a world direction
+PB_DEV float env_pdf(const DevEnvMap& e, V3 wi) {
+    float u, v, st;
+    env_uv(mat3_mul(e.w2l, wi), &u, &v, &st);
+    if (st == 0.0f || e.marg_int == 0.0f) return 0.0f;  // (a black map: no light sample either, D61)
+    int iu = (int)(u * (float)e.nu);
+    iu = iu < 0 ? 0 : (iu > e.nu - 1 ? e.nu - 1 : iu);
+    int iv = (int)(v * (float)e.nv);
+    iv = iv < 0 ? 0 : (iv > e.nv - 1 ? e.nv - 1 : iv);
+    return e.func[(size_t)iv * e.nu + iu] / e.marg_int / (2.0f * kPi * kPi * st);
+}
 
 // SpatialLightDistribution::lookup (lightdistrib.rs:171-182): the voxel of p, then its distribution
 PB_DEV DevDistribution1D light_distribution_lookup(const ShadeConsts& sc, V3 p) {

@@ -39,6 +39,7 @@ EXPORTS = [
     "pbrt_hip_film_create", "pbrt_hip_film_download", "pbrt_hip_film_destroy",
     "pbrt_hip_comm_last_error", "pbrt_hip_scene_wide_records", "pbrt_hip_get_wide_counters", "pbrt_hip_probe_gather", "pbrt_hip_probe_state_stream",
     "pbrt_hip_li", "pbrt_hip_li_device", "pbrt_hip_camera_rays", "pbrt_hip_scene_create_two_level", "pbrt_hip_debug_wide_export",
+    "pbrt_hip_scene_set_environment_map", "pbrt_hip_envmap_tables",
 ]
 
 
@@ -156,6 +157,9 @@ def lib():
         L.pbrt_hip_write_png.argtypes = [ctypes.c_char_p, vp, i32, i32]
         L.pbrt_hip_write_exr.argtypes = [ctypes.c_char_p, vp, i32, i32]
         L.pbrt_hip_film_to_rgb.argtypes = [vp, i64, vp]
+        L.pbrt_hip_scene_set_environment_map.argtypes = [vp, i32, vp, i32, i32, vp]
+        L.pbrt_hip_envmap_tables.argtypes = [vp, i32, i32, vp, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp, vp,
+                                             ctypes.POINTER(ctypes.c_char_p)]
         L.pbrt_hip_film_to_rgb.restype = None
         _lib = L
     return _lib
@@ -621,6 +625,16 @@ class Scene:
         self.ctx.check(lib().pbrt_hip_li(self.h, ctypes.byref(lp), _p(rays), _p(keys), len(rays), _p(rgb), ctypes.byref(st)), "pbrt_hip_li")
         return rgb, {name: getattr(st, name) for name, _ in RenderStats._fields_}
 
+    def set_environment_map(self, light, rgb, light_to_world=None):
+        """InfiniteAreaLight::new(light_to_world, L, .., texmap) for light `light` (PBRT_LIGHT_INFINITE): rgb (h, w, 3) float32,
+        row 0 = theta 0 (light-space +z); light_to_world a 4x4 (row-major, last row 0 0 0 1), None = identity."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("rgb must be (h, w, 3)")
+        m = np.eye(4, dtype=np.float32) if light_to_world is None else np.ascontiguousarray(light_to_world, dtype=np.float32).reshape(4, 4)
+        self.ctx.check(lib().pbrt_hip_scene_set_environment_map(self.h, int(light), _p(rgb), rgb.shape[1], rgb.shape[0], _p(m)),
+                       "pbrt_hip_scene_set_environment_map")
+
     def camera_rays(self, camera, width, height, spp, seed=0, bounds=None, tile_rank=0, tile_world=1, tile_order=0, sampler=None, filter=None):
         """The camera-ray stage of render(): (rays[RAY_DTYPE], stream_keys[uint64], p_film[n, 2], pixel_sample[n, 3]).
         sampler as in render(): the camera sample is the sampler's first 2D, first 1D (ray.time) and second 2D draw (sampler.rs:66-73)."""
@@ -762,6 +776,56 @@ def write_pfm(path, rgb):
     rc = lib().pbrt_hip_write_pfm(str(path).encode(), _p(rgb), rgb.shape[1], rgb.shape[0])
     if rc != 0:
         raise PbrtHipError(f"pbrt_hip_write_pfm failed ({rc})")
+
+
+def read_pfm(path):
+    """An RGB (or grey) PFM file as a float32 (h, w, 3) array, top row first (write_pfm's layout); both byte orders."""
+    raw = open(path, "rb").read()
+    n, fields, pos = len(raw), [], 0
+    while len(fields) < 4:  # "PF" / "Pf", width, height, scale: whitespace-separated, one whitespace byte before the data
+        while pos < n and raw[pos:pos + 1].isspace():
+            pos += 1
+        end = pos
+        while end < n and not raw[end:end + 1].isspace():
+            end += 1
+        if end == pos or end == n:  # a field missing, or no whitespace byte after the scale
+            raise ValueError(f"{path}: truncated PFM header")
+        fields.append(raw[pos:end].decode("latin-1"))
+        pos = end
+    pos += 1
+    kind = fields[0]
+    if kind not in ("PF", "Pf"):
+        raise ValueError(f"{path}: not a PFM file")
+    try:
+        w, h, scale = int(fields[1]), int(fields[2]), float(fields[3])
+    except ValueError:
+        raise ValueError(f"{path}: bad PFM header {fields[1:]}") from None
+    c = 3 if kind == "PF" else 1
+    if w < 1 or h < 1 or scale == 0.0 or n - pos < 4 * w * h * c:
+        raise ValueError(f"{path}: bad PFM size or truncated data ({w} x {h} x {c}, {n - pos} bytes)")
+    img = np.frombuffer(raw, dtype="<f4" if scale < 0 else ">f4", count=w * h * c, offset=pos).reshape(h, w, c)[::-1]
+    img = img.astype(np.float32)
+    return np.repeat(img, 3, axis=2) if c == 1 else np.ascontiguousarray(img)
+
+
+def envmap_tables(rgb, L=(1.0, 1.0, 1.0)):
+    """pbrt_hip_envmap_tables: InfiniteAreaLight::new's tables for an (h, w, 3) map scaled by L.
+    Returns (level0[H, W, 3], dist_func[2H, 2W], power_rgb[3]) with W x H the power-of-two size of level 0."""
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    Lv = np.ascontiguousarray(L, dtype=np.float32).reshape(3)
+    rw, rh, why = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_char_p()
+    h, w = rgb.shape[:2]
+    rc = lib().pbrt_hip_envmap_tables(_p(rgb), w, h, _p(Lv), ctypes.byref(rw), ctypes.byref(rh), None, None, None, ctypes.byref(why))
+    if rc != 0:
+        raise PbrtHipError(f"pbrt_hip_envmap_tables failed ({rc}): {(why.value or b'').decode()}")
+    level0 = np.zeros((rh.value, rw.value, 3), dtype=np.float32)
+    func = np.zeros((2 * rh.value, 2 * rw.value), dtype=np.float32)
+    power = np.zeros(3, dtype=np.float32)
+    rc = lib().pbrt_hip_envmap_tables(_p(rgb), w, h, _p(Lv), ctypes.byref(rw), ctypes.byref(rh), _p(level0), _p(func), _p(power),
+                                      ctypes.byref(why))
+    if rc != 0:
+        raise PbrtHipError(f"pbrt_hip_envmap_tables failed ({rc}): {(why.value or b'').decode()}")
+    return level0, func, power
 
 
 def write_exr(path, rgb):

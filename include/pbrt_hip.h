@@ -70,14 +70,24 @@ typedef struct PbrtHit {
     int32_t pad[2];
 } PbrtHit;
 
-/* The material files under src/materials/ are empty stubs; the three materials are pbrt-v3's on the reference's
- * BxDFs (src/core/reflection.rs:821-855, 614-659, 733-819). */
-enum PbrtMaterialType { PBRT_MAT_NONE = 0, PBRT_MAT_MATTE = 1, PBRT_MAT_MIRROR = 2, PBRT_MAT_GLASS = 3 };
+/* The material files under src/materials/ are empty stubs; the materials are pbrt-v3's on the reference's BxDFs
+ * (src/core/reflection.rs:821-855, 614-659, 733-819; plastic and metal: MicrofacetReflection :977-1056 over the
+ * Trowbridge-Reitz distribution src/core/microfacet.rs:145-232 with visible-area sampling, FresnelDielectric(1.5, 1) /
+ * FresnelConductor(1, eta, k) :42-67, 571-612).
+ *   PBRT_MAT_PLASTIC  LambertianReflection(Kd) if Kd is not black, then MicrofacetReflection(Ks, TR(a, a),
+ *                     FresnelDielectric(1.5, 1)) if Ks is not black (pbrt-v3's PlasticMaterial);
+ *   PBRT_MAT_METAL    MicrofacetReflection(1, TR(a_u, a_v), FresnelConductor(1, eta, k)), eta and k per RGB channel
+ *                     (pbrt-v3's MetalMaterial).
+ * Roughness is remapped by TrowbridgeReitzDistribution::roughness_to_alpha (microfacet.rs:160-169) unless
+ * pbrt_hip_scene_set_material_roughness says otherwise. */
+enum PbrtMaterialType { PBRT_MAT_NONE = 0, PBRT_MAT_MATTE = 1, PBRT_MAT_MIRROR = 2, PBRT_MAT_GLASS = 3, PBRT_MAT_PLASTIC = 4,
+                        PBRT_MAT_METAL = 5 };
 typedef struct PbrtMaterial {
     int32_t type;
-    float kd[3]; /* matte Kd; mirror / glass Kr */
-    float kt[3]; /* glass Kt */
-    float eta;   /* glass index of refraction */
+    float kd[3]; /* matte Kd; mirror / glass Kr; plastic Kd; metal eta (> 0) */
+    float kt[3]; /* glass Kt; plastic Ks; metal k (>= 0) */
+    float eta;   /* glass index of refraction; plastic / metal roughness (>= 0, isotropic, remapped; pbrt-v3's defaults
+                  * are 0.1 for plastic and 0.01 for metal) */
 } PbrtMaterial;
 
 /* src/lights/diffuse.rs:19-27 DiffuseAreaLight on one triangle; src/lights/infinite.rs:23-31
@@ -297,6 +307,20 @@ int pbrt_hip_scene_set_shading_data(PbrtHipScene* scene, const float* positions,
  * singular or non-affine transform, or texels pbrt_hip_envmap_tables refuses. */
 int pbrt_hip_scene_set_environment_map(PbrtHipScene* scene, int32_t light, const float* rgb, int32_t width, int32_t height,
                                        const float light_to_world[16]);
+/* Roughness of a plastic or metal material after creation: TrowbridgeReitzDistribution(a_u, a_v) with a = roughness_to_alpha(r)
+ * (microfacet.rs:160-169, r clamped at 1e-3) when remap != 0, else a = r (pbrt-v3's remaproughness = false). Metal may be
+ * anisotropic (u along the shading frame's dpdu); plastic is isotropic (u == v). PBRT_HIP_ERR_INVALID (pbrt_hip_last_error says
+ * why, the scene unchanged) for a material index out of range or of another type, a non-finite or negative roughness, a
+ * roughness of 0 with remap == 0, or u != v on plastic. */
+int pbrt_hip_scene_set_material_roughness(PbrtHipScene* scene, int32_t material, float u_roughness, float v_roughness, int32_t remap);
+/* BSDF::f, BSDF::pdf and BSDF::sample_f (reflection.rs:264-446) of material `material` of the scene, in batch form, evaluated
+ * on the device by the functions the shading kernels inline (any material type). Directions are in the shading frame
+ * (ns = ng = +z, dpdu = +x): wo[3 i ..], wi[3 i ..], u[2 i ..] the sample_f sample. Outputs: f[3 i ..] = f(wo, wi),
+ * pdf[i] = pdf(wo, wi) (non-specular lobes: specular ones have neither), and of sample_f(wo, u): wi_s[3 i ..], f_s[3 i ..],
+ * pdf_s[i] and sampled_flags[i] = the sampled lobe's BxDFType (1 reflection, 2 transmission, 4 diffuse, 8 glossy,
+ * 16 specular); all 0 when nothing was sampled. Host buffers; any output may be NULL. n = 0 is a no-op. */
+int pbrt_hip_bsdf_query(PbrtHipScene* scene, int32_t material, int64_t n, const float* wo, const float* wi, const float* u, float* f,
+                        float* pdf, float* wi_s, float* f_s, float* pdf_s, int32_t* sampled_flags);
 /* Scene with spheres next to the triangles (src/shapes/sphere.rs:38-92, 228-284 with src/core/efloat.rs; BASELINE
  * config 1): n_spheres full spheres {centre.xyz, radius}, i.e. Sphere::new with object_to_world = translate(centre).
  * Sphere i is primitive n_tris + i in prim_order; nodes come from pbrt_hip_bvh_build_boxes over the primitives' world

@@ -568,6 +568,31 @@ extern "C" int pbrt_hip_scene_create_instanced(PbrtHipContext* ctx, const float*
 }
 PB_ABI_CATCH
 
+// TrowbridgeReitzDistribution::roughness_to_alpha (microfacet.rs:160-169), in double, rounded once
+static float roughness_to_alpha(float roughness) {
+    double x = std::log(std::max((double)roughness, 1e-3));
+    return (float)(1.62142 + 0.819955 * x + 0.1734 * x * x + 0.0171201 * x * x * x + 0.000640711 * x * x * x * x);
+}
+// Roughness of a plastic / metal material: finite, >= 0, and > 0 when it is taken as alpha unchanged (remap off)
+static const char* roughness_invalid(float u, float v, bool remap) {
+    if (!std::isfinite(u) || !std::isfinite(v) || u < 0.0f || v < 0.0f) return "roughness must be finite and >= 0";
+    if (!remap && (u == 0.0f || v == 0.0f)) return "roughness 0 without remapping (alpha 0)";
+    return nullptr;
+}
+// The one place materials are checked (scene creation); nullptr when the material is usable
+static const char* material_invalid(const PbrtMaterial& m) {
+    if (m.type < PBRT_MAT_NONE || m.type > PBRT_MAT_METAL) return "unknown material type";
+    if (m.type == PBRT_MAT_GLASS && !(m.eta > 0.0f)) return "glass needs eta > 0";
+    if (m.type == PBRT_MAT_PLASTIC || m.type == PBRT_MAT_METAL)
+        if (const char* why = roughness_invalid(m.eta, m.eta, true)) return why;
+    if (m.type == PBRT_MAT_METAL)
+        for (int c = 0; c < 3; ++c) {
+            if (!(std::isfinite(m.kd[c]) && m.kd[c] > 0.0f)) return "metal eta must be finite and > 0";
+            if (!(std::isfinite(m.kt[c]) && m.kt[c] >= 0.0f)) return "metal k must be finite and >= 0";
+        }
+    return nullptr;
+}
+
 static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_t n_verts, const int32_t* indices,
                              int32_t n_tris, const int32_t* tri_material, const PbrtMaterial* materials,
                              int32_t n_materials, const int32_t* tri_light, const PbrtLight* lights, int32_t n_lights,
@@ -603,8 +628,7 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
         if (tri_light && (tri_light[i] < -1 || tri_light[i] >= n_lights)) return fail("tri_light out of range");
     }
     for (int32_t i = 0; i < n_materials; ++i) {
-        if (materials[i].type < PBRT_MAT_NONE || materials[i].type > PBRT_MAT_GLASS) return fail("unknown material type");
-        if (materials[i].type == PBRT_MAT_GLASS && !(materials[i].eta > 0.0f)) return fail("glass needs eta > 0");
+        if (const char* why = material_invalid(materials[i])) return fail(why);
     }
     for (int32_t i = 0; i < n_lights; ++i) {
         if (lights[i].type < PBRT_LIGHT_DIFFUSE_AREA || lights[i].type > PBRT_LIGHT_DISTANT) return fail("unknown light type");
@@ -772,7 +796,11 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
         std::memcpy(dm[i].kd, materials[i].kd, 12);
         std::memcpy(dm[i].kt, materials[i].kt, 12);
         dm[i].eta = materials[i].eta;
+        const bool glossy = materials[i].type == PBRT_MAT_PLASTIC || materials[i].type == PBRT_MAT_METAL;
+        dm[i].alpha_u = dm[i].alpha_v = glossy ? roughness_to_alpha(materials[i].eta) : 0.0f;
+        s->glossy = s->glossy || glossy;
     }
+    s->h_materials = dm;
 
     DevSceneData& d = s->d;
     std::memset(&d, 0, sizeof(d));
@@ -1135,6 +1163,32 @@ extern "C" void pbrt_hip_scene_destroy(PbrtHipScene* s) {
     }
     delete s;
 }
+
+// TrowbridgeReitzDistribution::new(alpha_u, alpha_v, true) of a plastic / metal material with pbrt-v3's remaproughness switch
+// (plastic.cpp / metal.cpp): the alphas of material `material` are replaced in the device table and its host copy.
+extern "C" int pbrt_hip_scene_set_material_roughness(PbrtHipScene* s, int32_t material, float u_roughness, float v_roughness,
+                                                     int32_t remap) try {
+    if (!s) return PBRT_HIP_ERR_INVALID;
+    PbrtHipContext* ctx = s->ctx;
+    PB_ENTER(ctx);
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = "pbrt_hip_scene_set_material_roughness: " + why;
+        return PBRT_HIP_ERR_INVALID;
+    };
+    if (material < 0 || material >= (int32_t)s->h_materials.size()) return invalid("material index out of range");
+    DevMaterial m = s->h_materials[material];
+    if (m.type != PBRT_MAT_PLASTIC && m.type != PBRT_MAT_METAL) return invalid("material is not PBRT_MAT_PLASTIC or PBRT_MAT_METAL");
+    if (const char* why = roughness_invalid(u_roughness, v_roughness, remap != 0)) return invalid(why);
+    if (m.type == PBRT_MAT_PLASTIC && u_roughness != v_roughness) return invalid("plastic is isotropic: u_roughness must equal v_roughness");
+    m.alpha_u = remap ? roughness_to_alpha(u_roughness) : u_roughness;
+    m.alpha_v = remap ? roughness_to_alpha(v_roughness) : v_roughness;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy((void*)(s->d.materials + material), &m, sizeof(DevMaterial), hipMemcpyHostToDevice));
+    s->h_materials[material] = m;
+    return PBRT_HIP_OK;
+}
+PB_ABI_CATCH
 
 // InfiniteAreaLight::new(light_to_world, L, n_samples, texmap) (lights/infinite.rs:36-82) with the texels in memory: the map's
 // tables (host_envmap.cpp) go to the device for light `light`, its power and the power distribution are recomputed, and a

@@ -164,6 +164,122 @@ extern "C" int pbrt_hip_li(PbrtHipScene* s, const PbrtLiParams* lp, const PbrtRa
 }
 PB_ABI_CATCH
 
+// BSDF::f / pdf / sample_f of one material in the shading frame (ns = ng = +z, dpdu = +x), evaluated by the functions k_shade
+// and k_shade_direct inline (wf_microfacet.h; mirror / glass: the specular sampler of k_shade). out: 12 floats per query,
+// {f.xyz, pdf, wi_s.xyz, f_s.xyz, pdf_s, sampled BxDFType bits}.
+__global__ void k_bsdf_query(const DevMaterial* __restrict__ materials, int material, int64_t n, const float* __restrict__ wo_in,
+                             const float* __restrict__ wi_in, const float* __restrict__ u_in, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const DevMaterial mat = materials[material];
+    Frame fr;
+    fr.ss = V3{1.0f, 0.0f, 0.0f};
+    fr.ts = V3{0.0f, 1.0f, 0.0f};
+    fr.ns = V3{0.0f, 0.0f, 1.0f};
+    fr.ng = fr.ns;
+    const V3 wo = V3{wo_in[3 * i], wo_in[3 * i + 1], wo_in[3 * i + 2]};
+    const V3 wi = V3{wi_in[3 * i], wi_in[3 * i + 1], wi_in[3 * i + 2]};
+    const float u0 = u_in[2 * i], u1 = u_in[2 * i + 1];
+    V3 f = V3{0.0f, 0.0f, 0.0f}, wi_s = f, f_s = f;
+    float pdf = 0.0f, pdf_s = 0.0f;
+    int sampled = 0;
+    const NsBsdf nsb = ns_bsdf(mat);
+    if (nsb.n > 0) {
+        ns_f_pdf(nsb, fr, wo, wi, &f, &pdf);
+        bool ok;
+        float ps = 0.0f;
+        V3 w;
+        V3 fs = ns_sample_f(nsb, fr, wo, u0, u1, &w, &ps, &ok, &sampled);
+        if (ok) {
+            wi_s = w;
+            f_s = fs;
+            pdf_s = ps;
+        } else {
+            sampled = 0;
+        }
+    } else if (mat.type == PBRT_MAT_MIRROR || mat.type == PBRT_MAT_GLASS) {
+        const V3 kd = V3{mat.kd[0], mat.kd[1], mat.kd[2]}, kt = V3{mat.kt[0], mat.kt[1], mat.kt[2]};
+        const bool has_lobe = mat.type == PBRT_MAT_GLASS ? !(is_black(kd) && is_black(kt)) : !is_black(kd);
+        const float ur = fminr(u0 * 1.0f - 0.0f, kOneMinusEpsilon);
+        if (has_lobe && wo.z != 0.0f) {
+            V3 wil = V3{0.0f, 0.0f, 0.0f};
+            float ps = 0.0f;
+            bool tr = false;
+            V3 fs = sample_specular_local(mat, kd, kt, wo, ur, 0, &wil, &ps, &tr);
+            if (ps != 0.0f) {
+                wi_s = to_world(fr, wil);
+                f_s = fs;
+                pdf_s = ps;
+                sampled = kBxdfSpecular | (tr ? kBxdfTransmission : kBxdfReflection);
+            }
+        }
+    }
+    float* o = out + 12 * i;
+    o[0] = f.x;
+    o[1] = f.y;
+    o[2] = f.z;
+    o[3] = pdf;
+    o[4] = wi_s.x;
+    o[5] = wi_s.y;
+    o[6] = wi_s.z;
+    o[7] = f_s.x;
+    o[8] = f_s.y;
+    o[9] = f_s.z;
+    o[10] = pdf_s;
+    o[11] = __int_as_float(sampled);
+}
+
+extern "C" int pbrt_hip_bsdf_query(PbrtHipScene* s, int32_t material, int64_t n, const float* wo, const float* wi, const float* u, float* f,
+                                   float* pdf, float* wi_s, float* f_s, float* pdf_s, int32_t* sampled_flags) try {
+    if (!s) return PBRT_HIP_ERR_INVALID;
+    PbrtHipContext* ctx = s->ctx;
+    PB_ENTER(ctx);
+    auto invalid = [&](const char* why) {
+        ctx->last_error = std::string("pbrt_hip_bsdf_query: ") + why;
+        return PBRT_HIP_ERR_INVALID;
+    };
+    if (material < 0 || material >= s->d.n_materials) return invalid("material index out of range");
+    if (n < 0 || n > ((int64_t)1 << 31)) return invalid("n must be in [0, 2^31]");
+    if (n == 0) return PBRT_HIP_OK;
+    if (!wo || !wi || !u) return invalid("null wo / wi / u");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t un = (size_t)n;
+    float *d_in = nullptr, *d_out = nullptr;
+    int rc = PBRT_HIP_OK;
+    if (!hip_ok(ctx, hipMalloc((void**)&d_in, un * 8 * sizeof(float)), "hipMalloc") ||
+        !hip_ok(ctx, hipMalloc((void**)&d_out, un * 12 * sizeof(float)), "hipMalloc"))
+        rc = PBRT_HIP_ERR_OOM;
+    if (rc == PBRT_HIP_OK && (!hip_ok(ctx, hipMemcpy(d_in, wo, un * 3 * sizeof(float), hipMemcpyHostToDevice), "H2D") ||
+                              !hip_ok(ctx, hipMemcpy(d_in + 3 * un, wi, un * 3 * sizeof(float), hipMemcpyHostToDevice), "H2D") ||
+                              !hip_ok(ctx, hipMemcpy(d_in + 6 * un, u, un * 2 * sizeof(float), hipMemcpyHostToDevice), "H2D")))
+        rc = PBRT_HIP_ERR_DEVICE;
+    std::vector<float> h;
+    if (rc == PBRT_HIP_OK) {
+        hipLaunchKernelGGL(k_bsdf_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, s->d.materials, material, n, d_in,
+                           d_in + 3 * un, d_in + 6 * un, d_out);
+        h.resize(un * 12);
+        if (!hip_ok(ctx, hipGetLastError(), "k_bsdf_query") || !hip_ok(ctx, hipStreamSynchronize(ctx->stream), "k_bsdf_query") ||
+            !hip_ok(ctx, hipMemcpy(h.data(), d_out, un * 12 * sizeof(float), hipMemcpyDeviceToHost), "D2H"))
+            rc = PBRT_HIP_ERR_DEVICE;
+    }
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    if (rc != PBRT_HIP_OK) return rc;
+    for (size_t i = 0; i < un; ++i) {
+        const float* o = &h[12 * i];
+        for (int k = 0; k < 3; ++k) {
+            if (f) f[3 * i + k] = o[k];
+            if (wi_s) wi_s[3 * i + k] = o[4 + k];
+            if (f_s) f_s[3 * i + k] = o[7 + k];
+        }
+        if (pdf) pdf[i] = o[3];
+        if (pdf_s) pdf_s[i] = o[10];
+        if (sampled_flags) std::memcpy(&sampled_flags[i], &o[11], 4);
+    }
+    return PBRT_HIP_OK;
+}
+PB_ABI_CATCH
+
 static int round_up_pow2(int v);
 extern "C" int pbrt_hip_camera_rays(PbrtHipScene* s, const PbrtCamera* camera, const PbrtRenderParams* params, int64_t capacity,
                                     PbrtRay* rays, uint64_t* stream_keys, float* p_film, int32_t* pixel_sample, int64_t* n_out) try {
@@ -967,12 +1083,17 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
             if (direct)
 {
                 dim3 sg((n_shade + 255) / 256), sb(256);
-                if (rp.integrator == PBRT_INTEGRATOR_DIRECT)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                // a plastic or metal material in the scene's table selects the glossy instantiations (AO reads no BSDF)
+                if (rp.integrator == PBRT_INTEGRATOR_DIRECT && s->glossy)
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, true>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                else if (rp.integrator == PBRT_INTEGRATOR_DIRECT)
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, false>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                else if (rp.integrator == PBRT_INTEGRATOR_WHITTED && s->glossy)
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, true>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
                 else if (rp.integrator == PBRT_INTEGRATOR_WHITTED)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, false>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
                 else
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_AO>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_AO, false>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
             }
             else {
                 Queues qin = q[cur];
@@ -987,10 +1108,15 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
                     }
                     qin.shade = shade_sorted;
                 }
-                if (bin_shade && wavefront >= 1)
-                    hipLaunchKernelGGL(k_shade<true>, dim3((n_shade + 255) / 256), dim3(256), 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade);
+                const dim3 sg((n_shade + 255) / 256), sb(256);
+                if (bin_shade && wavefront >= 1 && s->glossy)
+                    hipLaunchKernelGGL((k_shade<true, true>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade);
+                else if (bin_shade && wavefront >= 1)
+                    hipLaunchKernelGGL((k_shade<true, false>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade);
+                else if (s->glossy)
+                    hipLaunchKernelGGL((k_shade<false, true>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade);
                 else
-                    hipLaunchKernelGGL(k_shade<false>, dim3((n_shade + 255) / 256), dim3(256), 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade);
+                    hipLaunchKernelGGL((k_shade<false, false>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade);
             }
             RENDER_TRY(hipGetLastError());
             RENDER_TRY(hipMemcpyAsync(ctx->h_counts, q[nxt].counts64, sizeof(counts), hipMemcpyDeviceToHost, st));

@@ -99,6 +99,7 @@ struct DevMaterial {
     int type;
     float kd[3], kt[3];
     float eta;
+    float alpha_u, alpha_v;  // plastic / metal: TrowbridgeReitzDistribution's alphas, computed on the host
 };
 
 // Distribution1D (src/core/sampling.rs:62-154) flattened: func[n], cdf[n+1]
@@ -149,6 +150,8 @@ struct PbrtHipScene {
     int n_tris = 0, n_nodes = 0, n_interior = 0, n_instances = 0;
     int spill_lanes = 0;
     std::vector<pb::DevLight> h_lights;
+    std::vector<pb::DevMaterial> h_materials;  // the device table's host copy (pbrt_hip_scene_set_material_roughness)
+    bool glossy = false;  // a plastic or metal material in the table: the shading kernels' glossy instantiations run
     std::vector<int> light_samples;  // max(1, n_samples) per light (light.rs:76)
     // image maps of infinite lights (pbrt_hip_scene_set_environment_map): per light its descriptor and its device arrays
     std::vector<pb::DevEnvMap> h_env;

@@ -25,8 +25,11 @@ struct DirectState {
 #ifndef PB_DIRECT_WAVES
 #define PB_DIRECT_WAVES 2  // 128 VGPRs: +5..9 % on direct lighting / Whitted / AO over the unconstrained 256-VGPR build
 #endif
-template <int MODE>  // PBRT_INTEGRATOR_DIRECT / _WHITTED / _AO: one instantiation each, the other integrators' stages compile away
-__global__ void __launch_bounds__(256, PB_DIRECT_WAVES) k_shade_direct(ShadeConsts sc, PathState ps, DirectState ds, Queues qin,
+// MODE: PBRT_INTEGRATOR_DIRECT / _WHITTED / _AO: one instantiation each, the other integrators' stages compile away.
+// GLOSSY: the scene holds plastic or metal: the non-specular BSDF is the general one of wf_microfacet.h (matte included).
+// The glossy direct-lighting instantiation runs one wave per SIMD: at two it spills 19 registers.
+template <int MODE, bool GLOSSY>
+__global__ void __launch_bounds__(256, (GLOSSY && MODE == PBRT_INTEGRATOR_DIRECT) ? 1 : PB_DIRECT_WAVES) k_shade_direct(ShadeConsts sc, PathState ps, DirectState ds, Queues qin,
                                                         Queues qout, PassParams pp, TileList tiles, uint32_t n_in) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool active = i < n_in;
@@ -203,7 +206,12 @@ __global__ void __launch_bounds__(256, PB_DIRECT_WAVES) k_shade_direct(ShadeCons
                 if (is_black(li) || pdf == 0.0f) continue;
                 V3 f = V3{0.0f, 0.0f, 0.0f};
                 float spdf;
-                if (mat.type == PBRT_MAT_MATTE && !is_black(kd)) matte_f_pdf(fr, kd, sf.wo, wi, &f, &spdf);  // BSDF::f, all lobes
+                if (GLOSSY) {
+                    NsBsdf nsb = ns_bsdf(sc.materials[sf.material]);  // read again here: keeps the alphas out of the loop's registers
+                    if (nsb.n > 0) ns_f_pdf(nsb, fr, sf.wo, wi, &f, &spdf);  // BSDF::f, all lobes
+                } else if (mat.type == PBRT_MAT_MATTE && !is_black(kd)) {
+                    matte_f_pdf(fr, kd, sf.wo, wi, &f, &spdf);  // BSDF::f, all lobes
+                }
                 if (is_black(f)) continue;
                 V3 origin = offset_ray_origin(sf.p, sf.p_error, sf.n, p1 - sf.p);
                 V3 target = offset_ray_origin(p1, p1_err, p1_n, origin - p1);
@@ -217,7 +225,6 @@ __global__ void __launch_bounds__(256, PB_DIRECT_WAVES) k_shade_direct(ShadeCons
             if (stage < total) {
                 // ---- one estimate_direct ----
                 if (!surface_ready) load_surface();
-                bool matte = (mat.type == PBRT_MAT_MATTE) && !is_black(kd);
                 int light_num;
                 float pick_pdf = 1.0f;
                 if (sample_all && fallback) {
@@ -241,7 +248,14 @@ __global__ void __launch_bounds__(256, PB_DIRECT_WAVES) k_shade_direct(ShadeCons
                     samp_2d(pp, sm, &ul0, &ul1);
                     samp_2d(pp, sm, &us0, &us1);
                 }
-                int nee_flags = estimate_direct_emit(sc, ps, p, sf, fr, matte, kd, light_num, ul0, ul1, us0, us1, pick_pdf, T);
+                int nee_flags;
+                if (GLOSSY) {
+                    NsBsdf nsb = ns_bsdf(sc.materials[sf.material]);
+                    nee_flags = estimate_direct_emit(sc, ps, p, sf, fr, nsb.n > 0, nsb, light_num, ul0, ul1, us0, us1, pick_pdf, T);
+                } else {
+                    bool matte = (mat.type == PBRT_MAT_MATTE) && !is_black(kd);
+                    nee_flags = estimate_direct_emit(sc, ps, p, sf, fr, matte, MatteBsdf{kd}, light_num, ul0, ul1, us0, us1, pick_pdf, T);
+                }
                 stage += 1;
                 if (nee_flags) {
                     flags |= nee_flags & 0xff;

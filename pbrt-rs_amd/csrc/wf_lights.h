@@ -1,6 +1,6 @@
 // wf_lights.h — Light::sample_li for every light type, spatial light tables, estimate_direct (emit / resolve), specular lobes (part of wavefront.h)
 #pragma once
-#include "wf_surface.h"
+#include "wf_microfacet.h"
 
 namespace pb {
 
@@ -276,12 +276,14 @@ __global__ void k_spatial_light_tables(ShadeConsts sc, float* __restrict__ table
 
 // estimate_direct (integrator.rs:136-266), first part: sample the light, evaluate the BSDF, sample the
 // BSDF, evaluate the light pdf. Writes the shadow ray (slot 2), the MIS ray (slot 1) and the pending
-// terms into the path state; returns PF_NEE_* flags for the rays that must be traced. `matte` = the
-// BSDF has a non-specular (Lambertian) lobe with reflectance kd; otherwise f == 0 and nothing is emitted.
+// terms into the path state; returns PF_NEE_* flags for the rays that must be traced. `nonspecular` = the
+// BSDF has a non-specular lobe, `bsdf` its lobes (MatteBsdf: matte only; NsBsdf: matte, plastic or metal); otherwise f == 0
+// and nothing is emitted.
+template <class Bsdf>
 PB_DEV int estimate_direct_emit(const ShadeConsts& sc, const PathState& ps, uint32_t p, const Surf& sf, const Frame& fr,
-                                bool matte, V3 kd, int light_num, float ul0, float ul1, float us0, float us1,
+                                bool nonspecular, const Bsdf& bsdf, int light_num, float ul0, float ul1, float us0, float us1,
                                 float pick_pdf, V3 beta) {
-    if (!matte) return 0;
+    if (!nonspecular) return 0;
     V3 wo = sf.wo;
     DevLight lt = sc.lights[light_num];
     V3 wi, li, p1, p1_err, p1_n;
@@ -292,7 +294,7 @@ PB_DEV int estimate_direct_emit(const ShadeConsts& sc, const PathState& ps, uint
     if (light_pdf > 0.0f && !is_black(li)) {
         V3 f;
         float scattering_pdf;
-        matte_f_pdf(fr, kd, wo, wi, &f, &scattering_pdf);
+        bsdf_f_pdf(bsdf, fr, wo, wi, &f, &scattering_pdf);
         f = f * absdot(wi, fr.ns);
         if (!is_black(f)) {
             // VisibilityTester::un_occluded -> spawn_ray_to (interaction.rs:147-153)
@@ -315,7 +317,7 @@ PB_DEV int estimate_direct_emit(const ShadeConsts& sc, const PathState& ps, uint
     bool ok = false;
     V3 f2 = V3{0.0f, 0.0f, 0.0f};
     // scattering_pdf keeps the light-half value if wo.z == 0 (then it is 0 as well)
-    if (!lt.delta) f2 = matte_sample_f(fr, kd, wo, us0, us1, &wi2, &spdf, &ok);
+    if (!lt.delta) f2 = bsdf_sample_f(bsdf, fr, wo, us0, us1, &wi2, &spdf, &ok);
     if (ok) f2 = f2 * absdot(wi2, fr.ns);
     if (ok && !is_black(f2) && spdf > 0.0f) {
         float lpdf;

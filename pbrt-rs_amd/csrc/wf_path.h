@@ -38,24 +38,30 @@ __global__ void k_shade_sort_keys(ShadeConsts sc, PathState ps, const uint32_t* 
     keys[i] = shade_key(sc, ps, shade_queue[i], max_depth);
 }
 
-constexpr int kShadeKeys = 6;  // 0 nothing to shade, 1 + PBRT_MAT_* (none, matte, mirror, glass), 5 = no queue entry (block tail)
+// keys: 0 nothing to shade, 1 + PBRT_MAT_* (none, matte, mirror, glass; the glossy instantiations: plastic, metal as well),
+// the last = no queue entry (block tail)
+constexpr int shade_keys(bool glossy) { return glossy ? 8 : 6; }
+template <int KEYS>
 struct ShadeBins {
-    uint32_t count[4][kShadeKeys];  // per wave of the block, per key
+    uint32_t count[4][KEYS];  // per wave of the block, per key
     uint32_t path[256];
 };
 
 #ifndef PB_SHADE_WAVES
 #define PB_SHADE_WAVES 3  // 162 VGPRs; 4 waves (128 VGPRs, spills) measured in profiles/r04_wide_kernel_ladder.txt
 #endif
-template <bool BIN>
+// GLOSSY: the scene's material table holds plastic or metal (MicrofacetReflection lobes, wf_microfacet.h); matte then goes
+// through the same general BSDF (bit for bit the Lambertian code), and the instantiations without it stay as they were.
+template <bool BIN, bool GLOSSY>
 __global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
                                                  TileList tiles, uint32_t n_in) {
+    constexpr int kShadeKeys = shade_keys(GLOSSY);
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool active = i < n_in;
     uint32_t p = active ? qin.shade[i] : 0u;
     if (BIN) {
         // counting sort of the block's 256 entries by key: rank inside the wave by ballot + mbcnt, waves and keys through LDS
-        __shared__ ShadeBins bins;
+        __shared__ ShadeBins<kShadeKeys> bins;
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
         const uint32_t key = active ? shade_key(sc, ps, p, pp.max_depth) : (uint32_t)(kShadeKeys - 1);
         uint32_t rank = 0;
@@ -139,10 +145,20 @@ __global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, P
                     V3 kd = V3{mat.kd[0], mat.kd[1], mat.kd[2]};
                     V3 kt = V3{mat.kt[0], mat.kt[1], mat.kt[2]};
                     V3 wo = -rd;  // path.rs:122 `let wo = -ray.d` (estimate_direct uses isect.wo = sf.wo)
-                    bool has_lobe;  // which BxDFs the material adds: pbrt-v3 rules (matte / mirror / glass)
-                    if (mat.type == PBRT_MAT_GLASS) has_lobe = !(is_black(kd) && is_black(kt));
-                    else has_lobe = !is_black(kd);
-                    bool nonspecular = (mat.type == PBRT_MAT_MATTE) && has_lobe;
+                    bool has_lobe;  // which BxDFs the material adds: pbrt-v3 rules (matte / mirror / glass / plastic / metal)
+                    bool nonspecular;
+                    NsBsdf nsb;
+                    if (GLOSSY) {
+                        nsb = ns_bsdf(mat);
+                        nonspecular = nsb.n > 0;
+                        if (mat.type == PBRT_MAT_GLASS) has_lobe = !(is_black(kd) && is_black(kt));
+                        else if (mat.type == PBRT_MAT_MIRROR) has_lobe = !is_black(kd);
+                        else has_lobe = nonspecular;
+                    } else {
+                        if (mat.type == PBRT_MAT_GLASS) has_lobe = !(is_black(kd) && is_black(kt));
+                        else has_lobe = !is_black(kd);
+                        nonspecular = (mat.type == PBRT_MAT_MATTE) && has_lobe;
+                    }
 
                     // ---- uniform_sample_one_light (integrator.rs:92-134) ----
                     if (nonspecular && sc.n_lights > 0) {
@@ -155,8 +171,10 @@ __global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, P
                             float ul0, ul1, us0, us1;
                             samp_2d(pp, sm, &ul0, &ul1);
                             samp_2d(pp, sm, &us0, &us1);
-                            int nee_flags = estimate_direct_emit(sc, ps, p, sf, fr, true, kd, light_num, ul0, ul1, us0, us1,
-                                                                 pick_pdf, beta);
+                            int nee_flags = GLOSSY ? estimate_direct_emit(sc, ps, p, sf, fr, true, nsb, light_num, ul0, ul1, us0,
+                                                                          us1, pick_pdf, beta)
+                                                   : estimate_direct_emit(sc, ps, p, sf, fr, true, MatteBsdf{kd}, light_num, ul0, ul1,
+                                                                          us0, us1, pick_pdf, beta);
                             flags |= nee_flags & 0xff;
                             emit_shadow = (nee_flags & PF_NEE_SHADOW) != 0;
                             emit_mis = (nee_flags & PF_NEE_MIS) != 0;
@@ -171,7 +189,11 @@ __global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, P
                     float pdf = 0.0f;
                     bool sampled_specular = false, sampled_transmission = false;
                     if (has_lobe) {
-                        if (mat.type == PBRT_MAT_MATTE) {
+                        if (GLOSSY && nonspecular) {  // glossy lobes: not specular, PF_SPECULAR_BOUNCE stays clear
+                            bool ok;
+                            f = bsdf_sample_f(nsb, fr, wo, u0, u1, &wi, &pdf, &ok);
+                            if (!ok) pdf = 0.0f;
+                        } else if (!GLOSSY && mat.type == PBRT_MAT_MATTE) {
                             bool ok;
                             f = matte_sample_f(fr, kd, wo, u0, u1, &wi, &pdf, &ok);
                             if (!ok) pdf = 0.0f;

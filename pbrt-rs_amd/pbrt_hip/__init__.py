@@ -39,8 +39,11 @@ EXPORTS = [
     "pbrt_hip_film_create", "pbrt_hip_film_download", "pbrt_hip_film_destroy",
     "pbrt_hip_comm_last_error", "pbrt_hip_scene_wide_records", "pbrt_hip_get_wide_counters", "pbrt_hip_probe_gather", "pbrt_hip_probe_state_stream",
     "pbrt_hip_li", "pbrt_hip_li_device", "pbrt_hip_camera_rays", "pbrt_hip_scene_create_two_level", "pbrt_hip_debug_wide_export",
-    "pbrt_hip_scene_set_environment_map", "pbrt_hip_envmap_tables",
+    "pbrt_hip_scene_set_environment_map", "pbrt_hip_envmap_tables", "pbrt_hip_scene_set_material_roughness", "pbrt_hip_bsdf_query",
 ]
+MAT_NONE, MAT_MATTE, MAT_MIRROR, MAT_GLASS, MAT_PLASTIC, MAT_METAL = (scenes.MAT_NONE, scenes.MAT_MATTE, scenes.MAT_MIRROR,
+                                                                      scenes.MAT_GLASS, scenes.MAT_PLASTIC, scenes.MAT_METAL)
+BSDF_REFLECTION, BSDF_TRANSMISSION, BSDF_DIFFUSE, BSDF_GLOSSY, BSDF_SPECULAR = 1, 2, 4, 8, 16  # BxDFType (bsdf_query's flags)
 
 
 class RenderParams(ctypes.Structure):
@@ -160,6 +163,8 @@ def lib():
         L.pbrt_hip_scene_set_environment_map.argtypes = [vp, i32, vp, i32, i32, vp]
         L.pbrt_hip_envmap_tables.argtypes = [vp, i32, i32, vp, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp, vp,
                                              ctypes.POINTER(ctypes.c_char_p)]
+        L.pbrt_hip_scene_set_material_roughness.argtypes = [vp, i32, ctypes.c_float, ctypes.c_float, i32]
+        L.pbrt_hip_bsdf_query.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.pbrt_hip_film_to_rgb.restype = None
         _lib = L
     return _lib
@@ -634,6 +639,28 @@ class Scene:
         m = np.eye(4, dtype=np.float32) if light_to_world is None else np.ascontiguousarray(light_to_world, dtype=np.float32).reshape(4, 4)
         self.ctx.check(lib().pbrt_hip_scene_set_environment_map(self.h, int(light), _p(rgb), rgb.shape[1], rgb.shape[0], _p(m)),
                        "pbrt_hip_scene_set_environment_map")
+
+    def set_material_roughness(self, m, u, v=None, remap=True):
+        """TrowbridgeReitzDistribution alphas of plastic / metal material m: roughness_to_alpha(u, v) with remap, else (u, v).
+        v = None: isotropic (plastic must be)."""
+        v = u if v is None else v
+        self.ctx.check(lib().pbrt_hip_scene_set_material_roughness(self.h, int(m), float(u), float(v), int(bool(remap))),
+                       "pbrt_hip_scene_set_material_roughness")
+
+    def bsdf_query(self, material, wo, wi, u):
+        """BSDF::f / pdf / sample_f of a material on the device, in the shading frame (n = +z): wo, wi (n, 3), u (n, 2).
+        Returns dict f (n, 3), pdf (n,), wi_s (n, 3), f_s (n, 3), pdf_s (n,), flags (n,) int32 BxDFType of the sampled lobe."""
+        wo = np.ascontiguousarray(wo, dtype=np.float32).reshape(-1, 3)
+        wi = np.ascontiguousarray(wi, dtype=np.float32).reshape(-1, 3)
+        u = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 2)
+        n = len(wo)
+        assert len(wi) == n and len(u) == n
+        out = dict(f=np.zeros((n, 3), np.float32), pdf=np.zeros(n, np.float32), wi_s=np.zeros((n, 3), np.float32),
+                   f_s=np.zeros((n, 3), np.float32), pdf_s=np.zeros(n, np.float32), flags=np.zeros(n, np.int32))
+        self.ctx.check(lib().pbrt_hip_bsdf_query(self.h, int(material), n, _p(wo), _p(wi), _p(u), _p(out["f"]), _p(out["pdf"]),
+                                                 _p(out["wi_s"]), _p(out["f_s"]), _p(out["pdf_s"]), _p(out["flags"])),
+                       "pbrt_hip_bsdf_query")
+        return out
 
     def camera_rays(self, camera, width, height, spp, seed=0, bounds=None, tile_rank=0, tile_world=1, tile_order=0, sampler=None, filter=None):
         """The camera-ray stage of render(): (rays[RAY_DTYPE], stream_keys[uint64], p_film[n, 2], pixel_sample[n, 3]).

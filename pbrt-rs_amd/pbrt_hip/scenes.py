@@ -26,7 +26,7 @@ NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("offset", "<i4")
 assert MATERIAL_DTYPE.itemsize == 32 and LIGHT_DTYPE.itemsize == 96
 assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 32 and NODE_DTYPE.itemsize == 32
 
-MAT_NONE, MAT_MATTE, MAT_MIRROR, MAT_GLASS = 0, 1, 2, 3
+MAT_NONE, MAT_MATTE, MAT_MIRROR, MAT_GLASS, MAT_PLASTIC, MAT_METAL = 0, 1, 2, 3, 4, 5
 LIGHT_DIFFUSE_AREA, LIGHT_INFINITE, LIGHT_POINT, LIGHT_SPOT, LIGHT_DISTANT = 0, 1, 2, 3, 4
 
 _PCG32_MULT = np.uint64(0x5851F42D4C957F2D)
@@ -68,6 +68,17 @@ def _materials(rows):
     for i, (t, kd, kt, eta) in enumerate(rows):
         m[i] = (t, kd, kt, eta)
     return m
+
+
+def plastic(kd, ks, roughness=0.1):
+    """_materials row of pbrt-v3's PlasticMaterial: Lambertian Kd + Trowbridge-Reitz Ks (FresnelDielectric(1.5, 1)),
+    roughness remapped (Scene.set_material_roughness changes that)."""
+    return (MAT_PLASTIC, kd, ks, roughness)
+
+
+def metal(eta, k, roughness=0.01):
+    """_materials row of pbrt-v3's MetalMaterial: Trowbridge-Reitz with FresnelConductor(1, eta, k), eta and k per RGB channel."""
+    return (MAT_METAL, eta, k, roughness)
 
 
 def _lights(rows):
@@ -510,6 +521,29 @@ def furnace_scene(rho=0.5, Le=1.0):
         tri_light=np.full(2, -1, dtype=np.int32),
         lights=_lights([(LIGHT_INFINITE, (Le, Le, Le), -1, 0, 1)]),
     )
+
+
+def _plane_z0(half):
+    """two triangles over [-half, half]^2 at z = 0, geometric normal +z, dpdu along +x on the first"""
+    h = float(half)
+    quad = np.array([[-h, -h, 0], [h, -h, 0], [h, h, 0], [-h, h, 0]], dtype=np.float32)
+    return quad, np.array([[0, 1, 2], [0, 2, 3]], dtype=np.int32)
+
+
+def glossy_plane_point_light_scene(material, p_light=(0.3, -0.2, 1.5), intensity=(2.0, 3.0, 4.0), half=10.0):
+    """One material row (plastic() / metal() / ...) on the plane z = 0 (normal +z) lit by one point light: what reaches
+    the eye from a hit p is f(wo, wi) I |cos theta_i| / r^2 (one bounce, no BSDF-sampling half for a delta light)."""
+    positions, indices = _plane_z0(half)
+    return dict(positions=positions, indices=indices, tri_material=np.zeros(2, dtype=np.int32), materials=_materials([material]),
+                tri_light=np.full(2, -1, dtype=np.int32), lights=_lights([point_light(p_light, intensity)]))
+
+
+def glossy_plane_env_scene(material, Le=(1.0, 1.0, 1.0), half=1e3):
+    """One material row on the plane z = 0 (normal +z) under a constant infinite light Le: one bounce leaves
+    Le * rho(wo), the directional albedo over the upper hemisphere."""
+    positions, indices = _plane_z0(half)
+    return dict(positions=positions, indices=indices, tri_material=np.zeros(2, dtype=np.int32), materials=_materials([material]),
+                tri_light=np.full(2, -1, dtype=np.int32), lights=_lights([(LIGHT_INFINITE, Le, -1, 0, 1)]))
 
 
 # ---------------------------------------------------------------------------------------

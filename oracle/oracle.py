@@ -90,6 +90,17 @@ def lib():
         L.orc_refract.argtypes = [vp, vp, ctypes.c_float, ctypes.c_uint32, vp]
         L.orc_refract.restype = ctypes.c_int
         L.orc_local_to_world.argtypes = [vp, vp, vp, vp, ctypes.c_uint32, vp]
+        L.orc_scene_set_material_roughness.argtypes = [vp, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int]
+        L.orc_scene_set_environment_map.argtypes = [vp, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp]
+        L.orc_envmap_probe.argtypes = [vp, ctypes.c_int, ctypes.c_int64, vp, vp, vp, vp, vp, vp, vp]
+        L.orc_bsdf_query.argtypes = [vp, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_int64] + [vp] * 9
+        L.orc_bsdf_query.restype = None
+        L.orc_fr_conductor.argtypes = [ctypes.c_float, vp, vp, vp]
+        L.orc_fr_conductor.restype = None
+        L.orc_trowbridge_reitz.argtypes = [ctypes.c_float, ctypes.c_float, vp, vp, vp, vp]
+        L.orc_trowbridge_reitz.restype = None
+        L.orc_roughness_to_alpha.argtypes = [ctypes.c_float]
+        L.orc_roughness_to_alpha.restype = ctypes.c_float
         _lib = L
     return _lib
 
@@ -314,6 +325,81 @@ def _li(self, rays, stream_keys, integrator=0, max_depth=5, rr_threshold=1.0, li
 
 
 OracleScene.li = _li
+
+
+def _set_material_roughness(self, m, u, v=None, remap=True):
+    """pbrt_hip.Scene.set_material_roughness on the oracle: TrowbridgeReitzDistribution(alpha_u, alpha_v) of plastic / metal
+    material m, roughness_to_alpha(u, v) with remap, else (u, v)."""
+    v = u if v is None else v
+    if lib().orc_scene_set_material_roughness(self.h, int(m), float(u), float(v), int(bool(remap))) != 0:
+        raise ValueError(f"material {m} is out of range or neither plastic nor metal")
+    if not hasattr(self, "_roughness"):
+        self._roughness = {}
+    self._roughness[int(m)] = (float(u), float(v), bool(remap))
+
+
+def bsdf_query(material_row, wo, wi, u, roughness=None):
+    """BSDF::f / pdf / sample_f of one material row {type, kd rgb, kt rgb, eta} in the shading frame (n = +z, dpdu = +x), with
+    pbrt_hip.Scene.bsdf_query's arguments and outputs. roughness = (u, v, remap) or None for the row's own (eta, eta, True)."""
+    row = _f32(material_row).reshape(8)
+    wo, wi, u = _f32(wo).reshape(-1, 3), _f32(wi).reshape(-1, 3), _f32(u).reshape(-1, 2)
+    n = len(wo)
+    assert len(wi) == n and len(u) == n
+    ru, rv, remap = (float(row[7]), float(row[7]), True) if roughness is None else roughness
+    out = dict(f=np.zeros((n, 3), np.float32), pdf=np.zeros(n, np.float32), wi_s=np.zeros((n, 3), np.float32),
+               f_s=np.zeros((n, 3), np.float32), pdf_s=np.zeros(n, np.float32), flags=np.zeros(n, np.int32))
+    lib().orc_bsdf_query(_p(row), ru, rv, int(bool(remap)), n, _p(wo), _p(wi), _p(u), _p(out["f"]), _p(out["pdf"]), _p(out["wi_s"]),
+                         _p(out["f_s"]), _p(out["pdf_s"]), _p(out["flags"]))
+    return out
+
+
+def _scene_bsdf_query(self, material, wo, wi, u):
+    """pbrt_hip.Scene.bsdf_query on the oracle, for material `material` of this scene's table."""
+    return bsdf_query(self._keep["materials"][int(material)], wo, wi, u, getattr(self, "_roughness", {}).get(int(material)))
+
+
+def _set_environment_map(self, light, rgb, light_to_world=None, tables=None):
+    """pbrt_hip.Scene.set_environment_map on the oracle. tables = (level0[H, W, 3], dist_func[2H, 2W], power_rgb[3]) of
+    InfiniteAreaLight::new for rgb x the light's L; None takes them from pbrt_hip.envmap_tables (host only, no context)."""
+    light = int(light)
+    if not 0 <= light < len(self._keep["lights"]):
+        raise ValueError(f"light {light} is out of range")
+    if tables is None:
+        import pbrt_hip
+        tables = pbrt_hip.envmap_tables(rgb, self._keep["lights"][light, 1:4])
+    level0, func, power = (_f32(t) for t in tables)
+    h, w = level0.shape[:2]
+    assert level0.shape == (h, w, 3) and func.shape == (2 * h, 2 * w) and power.shape == (3,)
+    m = np.eye(4, dtype=np.float32) if light_to_world is None else _f32(light_to_world).reshape(4, 4)
+    # the area lights of an instanced scene are not lights of the oracle's scene: its light list is the non-area ones
+    index = light
+    if hasattr(self, "n_instances") and not hasattr(self, "obj_tri_offset"):
+        index = int(np.count_nonzero(self._keep["lights"][:light, 0] != 0))
+    if lib().orc_scene_set_environment_map(self.h, index, _p(level0), w, h, _p(func), _p(power), _p(m)) != 0:
+        raise ValueError(f"light {light} is out of range or not an infinite light")
+    self._env_index = getattr(self, "_env_index", {})
+    self._env_index[light] = index
+
+
+def _envmap_probe(self, light, wi, u):
+    """InfiniteAreaLight::{le, pdf_li, sample_li} of light `light` outside any integrator: wi (n, 3) world directions, u (n, 2).
+    Returns dict le (n, 3), pdf (n,), wi_s (n, 3), li_s (n, 3), pdf_s (n,)."""
+    wi, u = _f32(wi).reshape(-1, 3), _f32(u).reshape(-1, 2)
+    n = len(wi)
+    assert len(u) == n
+    out = dict(le=np.zeros((n, 3), np.float32), pdf=np.zeros(n, np.float32), wi_s=np.zeros((n, 3), np.float32),
+               li_s=np.zeros((n, 3), np.float32), pdf_s=np.zeros(n, np.float32))
+    index = getattr(self, "_env_index", {}).get(int(light), int(light))
+    if lib().orc_envmap_probe(self.h, index, n, _p(wi), _p(u), _p(out["le"]), _p(out["pdf"]), _p(out["wi_s"]), _p(out["li_s"]),
+                              _p(out["pdf_s"])) != 0:
+        raise ValueError(f"light {light} is out of range or not an infinite light")
+    return out
+
+
+OracleScene.set_material_roughness = _set_material_roughness
+OracleScene.bsdf_query = _scene_bsdf_query
+OracleScene.set_environment_map = _set_environment_map
+OracleScene.envmap_probe = _envmap_probe
 
 
 def sampler_spec(sampler, max_sample_luminance=0.0):

@@ -1,6 +1,6 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY (see o_math.h header / oracle/README.md).
 //
-// o_reflection.h — BxDFs, BSDF, and the three materials the configs need.
+// o_reflection.h — BxDFs, BSDF, and the five materials the configs need.
 //
 // Follows:
 //   src/core/reflection.rs:19-40      fr_dielectric
@@ -12,6 +12,7 @@
 //   src/core/reflection.rs:661-731    SpecularTransmission
 //   src/core/reflection.rs:733-819    FresnelSpecular
 //   src/core/reflection.rs:821-855    LambertianReflection
+//   src/core/reflection.rs:977-1056   MicrofacetReflection (distribution and Fresnel objects: o_microfacet.h)
 //   src/core/material.rs:16-55        TransportMode, Material::compute_scattering_functions
 // src/materials/*.rs are empty stubs in the reference; matte / mirror / glass are restated from
 // pbrt-v3 on top of the reference's BxDFs:
@@ -22,6 +23,7 @@
 // Defect dispositions: D35 (matches_flags), D38 (sample_f unwraps None) — intended;
 // D36, D37 [Q] behind quirk bits; D46 (face_forward returns the wrong operand) — intended.
 #pragma once
+#include "o_microfacet.h"
 #include "o_shapes.h"
 
 namespace oracle {
@@ -174,6 +176,41 @@ struct FresnelSpecular : BxDF {
     Float pdf(const Vector3f&, const Vector3f&) const override { return 0.0f; }
 };
 
+// reflection.rs:977-1056 (D63: sample_f writes wi = reflect(wo, wh), pbrt-v3's reading)
+struct MicrofacetReflection : BxDF {
+    Spectrum r;
+    TrowbridgeReitzDistribution distribution;
+    std::shared_ptr<Fresnel> fresnel;
+    MicrofacetReflection(const Spectrum& r_, const TrowbridgeReitzDistribution& d, const std::shared_ptr<Fresnel>& fr)
+        : BxDF(BSDF_GLOSSY | BSDF_REFLECTION), r(r_), distribution(d), fresnel(fr) {}
+    // reflection.rs:1000-1018
+    Spectrum f(const Vector3f& wo, const Vector3f& wi) const override {
+        Float cos_theta_o = abs_cos_theta(wo), cos_theta_i = abs_cos_theta(wi);
+        Vector3f wh = wi + wo;
+        if (cos_theta_i == 0.0f || cos_theta_o == 0.0f) return Spectrum(0.0f);
+        if (wh.x == 0.0f && wh.y == 0.0f && wh.z == 0.0f) return Spectrum(0.0f);
+        wh = wh.normalize();
+        Spectrum fr = fresnel->evaluate(wi.dot(wh.face_forward(Vector3f(0.0f, 0.0f, 1.0f))));
+        return r * distribution.d(wh) * distribution.g(wo, wi) * fr / (4.0f * cos_theta_i * cos_theta_o);
+    }
+    // reflection.rs:1020-1043
+    Spectrum sample_f(const Vector3f& wo, Vector3f* wi, const Point2f& u, Float* pdf, uint8_t*) const override {
+        if (wo.z == 0.0f) return Spectrum(0.0f);
+        Vector3f wh = distribution.sample_wh(wo, u);
+        if (wo.dot(wh) < 0.0f) return Spectrum(0.0f);
+        *wi = reflect(wo, wh);
+        if (!same_hemisphere(wo, *wi)) return Spectrum(0.0f);
+        *pdf = distribution.pdf(wo, wh) / (4.0f * wo.dot(wh));
+        return f(wo, *wi);
+    }
+    // reflection.rs:1045-1051
+    Float pdf(const Vector3f& wo, const Vector3f& wi) const override {
+        if (!same_hemisphere(wo, wi)) return 0.0f;
+        Vector3f wh = (wo + wi).normalize();
+        return distribution.pdf(wo, wh) / (4.0f * wo.dot(wh));
+    }
+};
+
 // reflection.rs:207-449
 struct BSDF {
     Float eta;
@@ -278,12 +315,31 @@ struct BSDF {
 };
 
 // Material description shared with the C ABI (include/pbrt_hip.h PbrtMaterial).
-enum MaterialType { MAT_NONE = 0, MAT_MATTE = 1, MAT_MIRROR = 2, MAT_GLASS = 3 };
+enum MaterialType { MAT_NONE = 0, MAT_MATTE = 1, MAT_MIRROR = 2, MAT_GLASS = 3, MAT_PLASTIC = 4, MAT_METAL = 5 };
 struct MaterialDesc {
     int type;
-    Spectrum kd;  // matte Kd / mirror-glass Kr
-    Spectrum kt;  // glass Kt
-    Float eta;    // glass index
+    Spectrum kd;  // matte Kd / mirror-glass Kr / plastic Kd / metal eta
+    Spectrum kt;  // glass Kt / plastic Ks / metal k
+    Float eta;    // glass index; plastic / metal: the isotropic roughness, remapped
+    // plastic / metal: the roughness pair and pbrt-v3's remaproughness switch (orc_scene_set_material_roughness);
+    // set_roughness(eta, eta, true) is what a material row alone means
+    Float u_roughness = 0.0f, v_roughness = 0.0f;
+    bool remap_roughness = true;
+    Float alpha_u = 0.0f, alpha_v = 0.0f;  // TrowbridgeReitzDistribution::new's arguments (plastic.cpp / metal.cpp)
+    void set_roughness(Float u, Float v, bool remap) {
+        u_roughness = u, v_roughness = v, remap_roughness = remap;
+        alpha_u = remap ? TrowbridgeReitzDistribution::roughness_to_alpha(u) : u;
+        alpha_v = remap ? TrowbridgeReitzDistribution::roughness_to_alpha(v) : v;
+    }
+    static MaterialDesc from_row(const float* m) {  // {type, kd rgb, kt rgb, eta}
+        MaterialDesc d;
+        d.type = (int)m[0];
+        d.kd = Spectrum(m[1], m[2], m[3]);
+        d.kt = Spectrum(m[4], m[5], m[6]);
+        d.eta = m[7];
+        d.set_roughness(m[7], m[7], true);
+        return d;
+    }
 };
 
 // src/core/material.rs:16-55 trait Material::compute_scattering_functions
@@ -299,6 +355,23 @@ inline std::shared_ptr<BSDF> compute_scattering_functions(const MaterialDesc& m,
     if (m.type == MAT_MIRROR) {
         auto bsdf = std::make_shared<BSDF>(si, 1.0f, quirks);
         if (!m.kd.is_black()) bsdf->add(std::make_shared<SpecularReflection>(m.kd, true));
+        return bsdf;
+    }
+    if (m.type == MAT_PLASTIC || m.type == MAT_METAL) {
+        // pbrt-v3 PlasticMaterial / MetalMaterial on the reference's BxDFs (src/materials/*.rs are empty stubs):
+        //   plastic = LambertianReflection(Kd) if Kd is not black, then
+        //             MicrofacetReflection(Ks, TrowbridgeReitz(a, a), FresnelDielectric(1.5, 1)) if Ks is not black
+        //   metal   = MicrofacetReflection(1, TrowbridgeReitz(a_u, a_v), FresnelConductor(1, eta, k))
+        auto bsdf = std::make_shared<BSDF>(si, 1.0f, quirks);
+        TrowbridgeReitzDistribution distrib(m.alpha_u, m.alpha_v);
+        if (m.type == MAT_PLASTIC) {
+            if (!m.kd.is_black()) bsdf->add(std::make_shared<LambertianReflection>(m.kd));
+            if (!m.kt.is_black())
+                bsdf->add(std::make_shared<MicrofacetReflection>(m.kt, distrib, std::make_shared<FresnelDielectric>(1.5f, 1.0f)));
+        } else {
+            bsdf->add(std::make_shared<MicrofacetReflection>(
+                Spectrum(1.0f), distrib, std::make_shared<FresnelConductor>(Spectrum(1.0f), m.kd, m.kt)));
+        }
         return bsdf;
     }
     // glass (pbrt-v3 GlassMaterial, roughness 0)

@@ -5,8 +5,9 @@
 // Follows:
 //   src/core/light.rs:18-72, 114-135     LightFlags, is_delta_light, trait Light, VisibilityTester::un_occluded
 //   src/lights/diffuse.rs:19-90, 150-156 DiffuseAreaLight::{sample_li, pdf_li, l, power}
-//   src/lights/infinite.rs:23-155        InfiniteAreaLight (constant 1x1 map only; le :84-88,
-//                                        sample_li :96-129, pdf_li :140-151, power :131-133, pre_process :135-139)
+//   src/lights/infinite.rs:23-155        InfiniteAreaLight (le :84-88, sample_li :96-129, pdf_li :140-151, power :131-133,
+//                                        pre_process :135-139), constant or with an image map's tables
+//   src/core/mipmap.rs:195-218, 283-295  MIPMap::texel (Repeat) / lookup at width 0 / triangle on level 0
 //   src/core/scene.rs:11-46              Scene
 //   src/core/lightdistrib.rs:21-69, 222-232  Uniform / Power light distributions
 //   src/core/integrator.rs:44-90         uniform_sample_all_lights
@@ -106,15 +107,29 @@ inline Float spherical_phi(const Vector3f& v) {
     return p < 0.0f ? p + 2.0f * PI : p;
 }
 
-// lights/infinite.rs with a 1x1 (constant) map and identity light_to_world. The reference's
-// constructor builds a 2x2 sin-weighted Distribution2D from the 1x1 MIPMap (:59-73); the
-// MIPMap's bilinear lookup of a single texel (mipmap.rs:283-295) is taken as that texel.
+// lights/infinite.rs. Without a map (`has_map` false) this is the 1x1 constant map with identity light_to_world: the
+// constructor builds the 2x2 sin-weighted Distribution2D from the 1x1 MIPMap (:59-73), the MIPMap's bilinear lookup of a
+// single texel (mipmap.rs:283-295) is taken as that texel, and the identity transform is not multiplied through.
+// With a map (set_map; orc_scene_set_environment_map) the caller hands over what InfiniteAreaLight::new (:36-82) builds —
+// level 0 of the MIPMap (texels x L, resampled to powers of two), the 2W x 2H sin-weighted luminance image and
+// lookup((0.5, 0.5), 0.5) for power() — and this restates what runs per sample:
+//   MIPMap::lookup at width 0 = triangle on level 0 (mipmap.rs:215-218, 283-295; level < 0 since log2(1e-8) < -levels),
+//     ImageWrap::Repeat (:195-201), D60: a signed floor, wrapped;
+//   Distribution2D::{sample_continuous, pdf} (sampling.rs:168-213; D40, D48), the sums per DESIGN.md D62;
+//   le / sample_li / pdf_li / power (infinite.rs:84-151; D33: le is the light's le; D61: a black map has pdf 0).
+// world_to_light is the inverse of light_to_world's upper 3x3, inverted in double (D62); le normalises world_to_light * d,
+// sample_li returns light_to_world * v unnormalised and pdf_li takes world_to_light * wi as it is (infinite.rs:85, 116, 148).
 struct InfiniteAreaLight : Light {
     Spectrum l_const;
     Point3f world_center;
     Float world_radius = 0.0f;
     Distribution2D distribution;
-    InfiniteAreaLight(const Spectrum& power, int ns) : Light(LIGHT_INFINITE, ns), l_const(power) {
+    bool has_map = false;
+    int map_w = 1, map_h = 1;
+    std::vector<Spectrum> texels;  // level 0, row t = 0 is theta = 0
+    Spectrum power_rgb;
+    Float l2w[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, w2l[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    InfiniteAreaLight(const Spectrum& power, int ns) : Light(LIGHT_INFINITE, ns), l_const(power), power_rgb(power) {
         const int width = 2, height = 2;
         Float img[width * height];
         for (int v = 0; v < height; ++v) {
@@ -127,8 +142,56 @@ struct InfiniteAreaLight : Light {
         }
         distribution = Distribution2D(img, width, height);
     }
+    // the tables of InfiniteAreaLight::new for an image map; light_to_world16 row-major
+    void set_map(const Float* level0_rgb, int res_w, int res_h, const Float* dist_func, const Float* power3,
+                 const Float* light_to_world16) {
+        has_map = true;
+        map_w = res_w;
+        map_h = res_h;
+        texels.resize((size_t)res_w * res_h);
+        for (size_t i = 0; i < texels.size(); ++i) texels[i] = Spectrum(level0_rgb[3 * i], level0_rgb[3 * i + 1], level0_rgb[3 * i + 2]);
+        distribution = Distribution2D(dist_func, 2 * res_w, 2 * res_h, Distribution1D::DoubleSums());
+        power_rgb = Spectrum(power3[0], power3[1], power3[2]);
+        double a[9];
+        for (int r = 0; r < 3; ++r)
+            for (int c = 0; c < 3; ++c) a[3 * r + c] = (double)light_to_world16[4 * r + c];
+        const double adj[9] = {a[4] * a[8] - a[5] * a[7], a[2] * a[7] - a[1] * a[8], a[1] * a[5] - a[2] * a[4],
+                               a[5] * a[6] - a[3] * a[8], a[0] * a[8] - a[2] * a[6], a[2] * a[3] - a[0] * a[5],
+                               a[3] * a[7] - a[4] * a[6], a[1] * a[6] - a[0] * a[7], a[0] * a[4] - a[1] * a[3]};
+        const double det = a[0] * adj[0] + a[1] * adj[3] + a[2] * adj[6];
+        for (int k = 0; k < 9; ++k) {
+            l2w[k] = (Float)a[k];
+            w2l[k] = (Float)(adj[k] / det);
+        }
+    }
+    static Vector3f mul3(const Float* m, const Vector3f& v) {  // transform.rs:366-385 Transform * Vector
+        return Vector3f(m[0] * v.x + m[1] * v.y + m[2] * v.z, m[3] * v.x + m[4] * v.y + m[5] * v.z,
+                        m[6] * v.x + m[7] * v.y + m[8] * v.z);
+    }
+    // mipmap.rs:195-201 (Repeat; D60 signed)
+    const Spectrum& texel(int s, int t) const {
+        s %= map_w;
+        if (s < 0) s += map_w;
+        t %= map_h;
+        if (t < 0) t += map_h;
+        return texels[(size_t)t * map_w + s];
+    }
+    // mipmap.rs:215-218, 283-295: lookup(st, 0) = triangle(0, st)
+    Spectrum lookup(const Point2f& st) const {
+        if (!has_map) return l_const;
+        Float s = st.x * (Float)map_w - 0.5f, t = st.y * (Float)map_h - 0.5f;
+        Float fs = std::floor(s), ft = std::floor(t);
+        int s0 = (int)fs, t0 = (int)ft;
+        Float ds = s - fs, dt = t - ft;
+        return texel(s0, t0) * ((1.0f - ds) * (1.0f - dt)) + texel(s0, t0 + 1) * ((1.0f - ds) * dt) +
+               texel(s0 + 1, t0) * (ds * (1.0f - dt)) + texel(s0 + 1, t0 + 1) * (ds * dt);
+    }
     // infinite.rs:84-88
-    Spectrum le(const Ray&) const override { return l_const; }
+    Spectrum le(const Ray& ray) const override {
+        if (!has_map) return l_const;
+        Vector3f w = mul3(w2l, ray.d).normalize();
+        return lookup(Point2f(spherical_phi(w) * INV_2_PI, spherical_theta(w) * INV_PI));
+    }
     // infinite.rs:96-129
     Spectrum sample_li(const BaseInteraction& ref, const Point2f& u, Vector3f* wi, Float* pdf,
                        VisibilityTester* vis) const override {
@@ -140,23 +203,26 @@ struct InfiniteAreaLight : Light {
         det_sincos(theta, &sin_theta, &cos_theta);
         det_sincos(phi, &sin_phi, &cos_phi);
         *wi = Vector3f(sin_theta * cos_phi, sin_theta * sin_phi, cos_theta);
+        if (has_map) *wi = mul3(l2w, *wi);
         *pdf = map_pdf / (2.0f * PI * PI * sin_theta);
         if (sin_theta == 0.0f) *pdf = 0.0f;
         vis->p0 = ref;
         vis->p1 = BaseInteraction();
         vis->p1.p = ref.p + *wi * (2.0f * world_radius);
         vis->p1.time = ref.time;
-        return l_const;
+        return lookup(uv);
     }
     // infinite.rs:131-133
-    Spectrum power() const override { return l_const * (PI * world_radius * world_radius); }
+    Spectrum power() const override { return power_rgb * (PI * world_radius * world_radius); }
     // infinite.rs:135-139
     void pre_process(const Scene& scene) override;
     // infinite.rs:140-151
-    Float pdf_li(const BaseInteraction&, const Vector3f& w) const override {
+    Float pdf_li(const BaseInteraction&, const Vector3f& w_world) const override {
+        Vector3f w = has_map ? mul3(w2l, w_world) : w_world;
         Float theta = spherical_theta(w), phi = spherical_phi(w);
         Float sin_theta = det_sin(theta);
         if (sin_theta == 0.0f) return 0.0f;
+        if (distribution.marginal.func_int == 0.0f) return 0.0f;  // D61
         return distribution.pdf(Point2f(phi * INV_2_PI, theta * INV_PI)) / (2.0f * PI * PI * sin_theta);
     }
 };

@@ -513,6 +513,18 @@ struct Distribution1D {
             for (int i = 1; i < n + 1; ++i) cdf[i] /= func_int;
         }
     }
+    // an image map's distributions are accumulated in double and stored as float — c[i] = c[i-1] +
+    // (double)f[i-1] / n, func_int = c[n], cdf[i] = (float)(c[i] / func_int) (or i / n when func_int is 0), and func_int
+    // itself rounded to float last. Sampling and pdf then run on the stored floats like any other Distribution1D.
+    struct DoubleSums {};
+    Distribution1D(const Float* f, int n, DoubleSums) : func(f, f + n), cdf(n + 1) {
+        std::vector<double> c(n + 1);
+        c[0] = 0.0;
+        for (int i = 1; i < n + 1; ++i) c[i] = c[i - 1] + (double)func[i - 1] / (double)n;
+        const double fi = c[n];
+        for (int i = 0; i < n + 1; ++i) cdf[i] = (Float)(fi == 0.0 ? (double)i / (double)n : c[i] / fi);
+        func_int = (Float)fi;
+    }
     int count() const { return (int)func.size(); }
     Float sample_continuous(Float u, Float* pdf, int* off) const {
         int offset = find_interval((int)cdf.size(), [&](int i) { return cdf[i] < u; });
@@ -540,6 +552,12 @@ struct Distribution2D {
         std::vector<Float> mf;
         for (int v = 0; v < nv; ++v) mf.push_back(conditional[v].func_int);
         marginal = Distribution1D(mf.data(), nv);
+    }
+    Distribution2D(const Float* data, int nu, int nv, Distribution1D::DoubleSums tag) {
+        for (int v = 0; v < nv; ++v) conditional.emplace_back(data + v * nu, nu, tag);
+        std::vector<Float> mf;
+        for (int v = 0; v < nv; ++v) mf.push_back(conditional[v].func_int);
+        marginal = Distribution1D(mf.data(), nv, tag);
     }
     Point2f sample_continuous(const Point2f& u, Float* pdf) const {
         Float pdfs[2];

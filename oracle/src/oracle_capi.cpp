@@ -95,13 +95,7 @@ void* orc_scene_create_with_spheres(const float* positions, int n_verts, const i
     Scene& sc = os->scene;
     sc.quirks = quirks;
     for (int i = 0; i < n_mat; ++i) {
-        const float* m = materials + 8 * i;
-        MaterialDesc d;
-        d.type = (int)m[0];
-        d.kd = Spectrum(m[1], m[2], m[3]);
-        d.kt = Spectrum(m[4], m[5], m[6]);
-        d.eta = m[7];
-        sc.materials.push_back(d);
+        sc.materials.push_back(MaterialDesc::from_row(materials + 8 * i));
     }
     const int n_prims = n_tris + n_spheres;
     std::vector<std::shared_ptr<Shape>> shapes(n_prims);
@@ -154,13 +148,7 @@ void* orc_scene_create_instanced(const float* positions, int n_verts, const int3
     Scene& sc = os->scene;
     sc.quirks = quirks;
     for (int i = 0; i < n_mat; ++i) {
-        const float* m = materials + 8 * i;
-        MaterialDesc d;
-        d.type = (int)m[0];
-        d.kd = Spectrum(m[1], m[2], m[3]);
-        d.kt = Spectrum(m[4], m[5], m[6]);
-        d.eta = m[7];
-        sc.materials.push_back(d);
+        sc.materials.push_back(MaterialDesc::from_row(materials + 8 * i));
     }
     for (int i = 0; i < n_light; ++i) {
         const float* l = lights + kLightStride * i;
@@ -213,13 +201,7 @@ void* orc_scene_create_two_level(const float* positions, int n_verts, const int3
     Scene& sc = os->scene;
     sc.quirks = quirks;
     for (int i = 0; i < n_mat; ++i) {
-        const float* m = materials + 8 * i;
-        MaterialDesc d;
-        d.type = (int)m[0];
-        d.kd = Spectrum(m[1], m[2], m[3]);
-        d.kt = Spectrum(m[4], m[5], m[6]);
-        d.eta = m[7];
-        sc.materials.push_back(d);
+        sc.materials.push_back(MaterialDesc::from_row(materials + 8 * i));
     }
     const int world0 = obj_tri_offset[n_objects];
     sc.prim_material.assign(n_tris, 0);
@@ -532,6 +514,101 @@ void orc_scene_set_tangents(void* h, const float* tangents, int n_verts) {
     os->mesh->s.resize(n_verts);
     for (int i = 0; i < n_verts; ++i) os->mesh->s[i] = Vector3f(tangents[3 * i], tangents[3 * i + 1], tangents[3 * i + 2]);
 }
+
+// TrowbridgeReitzDistribution::new(alpha_u, alpha_v) of plastic / metal material `material`: roughness_to_alpha of (u, v)
+// when remap != 0, else (u, v) as they are (pbrt-v3's remaproughness). Returns 0, or 1 for a bad index / another type.
+int orc_scene_set_material_roughness(void* h, int material, float u, float v, int remap) {
+    Scene& sc = ((OracleScene*)h)->scene;
+    if (material < 0 || material >= (int)sc.materials.size()) return 1;
+    MaterialDesc& m = sc.materials[material];
+    if (m.type != MAT_PLASTIC && m.type != MAT_METAL) return 1;
+    m.set_roughness(u, v, remap != 0);
+    return 0;
+}
+// InfiniteAreaLight::new's tables for light `light` (PBRT_LIGHT_INFINITE): level 0 of the MIPMap (res_w x res_h x 3,
+// texels x L), the 2 res_w x 2 res_h sin-weighted luminance image, lookup((0.5, 0.5), 0.5) and light_to_world (row-major
+// 4x4). The oracle neither resamples nor builds the pyramid. Returns 0, or 1 for a bad index / a light of another type.
+int orc_scene_set_environment_map(void* h, int light, const float* level0_rgb, int res_w, int res_h, const float* dist_func,
+                                  const float* power_rgb, const float* light_to_world16) {
+    Scene& sc = ((OracleScene*)h)->scene;
+    if (light < 0 || light >= (int)sc.lights.size()) return 1;
+    auto* l = dynamic_cast<InfiniteAreaLight*>(sc.lights[light].get());
+    if (!l) return 1;
+    l->set_map(level0_rgb, res_w, res_h, dist_func, power_rgb, light_to_world16);
+    return 0;
+}
+// Probe of a mapped (or constant) InfiniteAreaLight outside any integrator: for n entries, wi[3 i ..] a world direction and
+// u[2 i ..] a sample; le[3 i ..] = le(ray along wi), pdf[i] = pdf_li(wi), and of sample_li(u): wi_s[3 i ..], li_s[3 i ..],
+// pdf_s[i]. world_radius stays what the scene gave it.
+int orc_envmap_probe(void* h, int light, int64_t n, const float* wi, const float* u, float* le, float* pdf, float* wi_s,
+                     float* li_s, float* pdf_s) {
+    Scene& sc = ((OracleScene*)h)->scene;
+    if (light < 0 || light >= (int)sc.lights.size()) return 1;
+    auto* l = dynamic_cast<InfiniteAreaLight*>(sc.lights[light].get());
+    if (!l) return 1;
+    BaseInteraction ref;
+    for (int64_t i = 0; i < n; ++i) {
+        Vector3f w(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]);
+        Spectrum e = l->le(Ray(Point3f(0.0f, 0.0f, 0.0f), w, FLOAT_INF, 0.0f));
+        Vector3f ws;
+        Float ps = 0.0f;
+        VisibilityTester vis;
+        Spectrum ls = l->sample_li(ref, Point2f(u[2 * i], u[2 * i + 1]), &ws, &ps, &vis);
+        pdf[i] = l->pdf_li(ref, w);
+        pdf_s[i] = ps;
+        for (int k = 0; k < 3; ++k) le[3 * i + k] = e.c[k], li_s[3 * i + k] = ls.c[k], wi_s[3 * i + k] = ws[k];
+    }
+    return 0;
+}
+// BSDF::f / pdf / sample_f (reflection.rs:264-446) of one material row {type, kd rgb, kt rgb, eta} with the roughness call
+// (u, v, remap) of orc_scene_set_material_roughness, in the shading frame ns = ng = +z, dpdu = +x: the arguments and outputs
+// of pbrt_hip_bsdf_query (include/pbrt_hip.h). All lobes (BSDF_ALL), TransportMode::Radiance, allow_multiple_lobes.
+void orc_bsdf_query(const float* material8, float u_roughness, float v_roughness, int remap, int64_t n, const float* wo,
+                    const float* wi, const float* u, float* f, float* pdf, float* wi_s, float* f_s, float* pdf_s,
+                    int32_t* sampled_flags) {
+    MaterialDesc m = MaterialDesc::from_row(material8);
+    if (m.type == MAT_PLASTIC || m.type == MAT_METAL) m.set_roughness(u_roughness, v_roughness, remap != 0);
+    SurfaceInteraction si;
+    si.n = Normal3f(0.0f, 0.0f, 1.0f);
+    si.shading.n = si.n;
+    si.dpdu = si.shading.dpdu = Vector3f(1.0f, 0.0f, 0.0f);
+    si.dpdv = si.shading.dpdv = Vector3f(0.0f, 1.0f, 0.0f);
+    std::shared_ptr<BSDF> bsdf = compute_scattering_functions(m, si, MODE_RADIANCE, true, 0);
+    for (int64_t i = 0; i < n; ++i) {
+        Vector3f o(wo[3 * i], wo[3 * i + 1], wo[3 * i + 2]), w(wi[3 * i], wi[3 * i + 1], wi[3 * i + 2]);
+        Spectrum fv(0.0f), fs(0.0f);
+        Float p = 0.0f, ps = 0.0f;
+        Vector3f ws;
+        uint8_t flags = BSDF_NONE;
+        if (bsdf) {
+            fv = bsdf->f(o, w, BSDF_ALL);
+            p = bsdf->pdf(o, w, BSDF_ALL);
+            fs = bsdf->sample_f(o, &ws, Point2f(u[2 * i], u[2 * i + 1]), &ps, BSDF_ALL, &flags);
+            if (ps == 0.0f || flags == BSDF_NONE) fs = Spectrum(0.0f), ws = Vector3f(), ps = 0.0f, flags = BSDF_NONE;
+        }
+        for (int k = 0; k < 3; ++k) {
+            if (f) f[3 * i + k] = fv.c[k];
+            if (wi_s) wi_s[3 * i + k] = ws[k];
+            if (f_s) f_s[3 * i + k] = fs.c[k];
+        }
+        if (pdf) pdf[i] = p;
+        if (pdf_s) pdf_s[i] = ps;
+        if (sampled_flags) sampled_flags[i] = flags;
+    }
+}
+// reflection.rs:42-67 and microfacet.rs:176-199, 18-20 for known-answer tests: out3 = fr_conductor(cos, 1, eta, k);
+// out3 = {d(wh), lambda(w), g(w, w2)}
+void orc_fr_conductor(float cos_theta_i, const float* eta3, const float* k3, float* out3) {
+    Spectrum r = fr_conductor(cos_theta_i, Spectrum(1.0f), Spectrum(eta3[0], eta3[1], eta3[2]), Spectrum(k3[0], k3[1], k3[2]));
+    for (int k = 0; k < 3; ++k) out3[k] = r.c[k];
+}
+void orc_trowbridge_reitz(float alpha_x, float alpha_y, const float* wh, const float* w, const float* w2, float* out3) {
+    TrowbridgeReitzDistribution d(alpha_x, alpha_y);
+    out3[0] = d.d(Vector3f(wh[0], wh[1], wh[2]));
+    out3[1] = d.lambda(Vector3f(w[0], w[1], w[2]));
+    out3[2] = d.g(Vector3f(w[0], w[1], w[2]), Vector3f(w2[0], w2[1], w2[2]));
+}
+float orc_roughness_to_alpha(float r) { return TrowbridgeReitzDistribution::roughness_to_alpha(r); }
 
 // HaltonSampler probe: out = {index of pixel (px, py)'s sample_num-th sample as double, sample_dimension(index, dim),
 // unscrambled radical inverse of the index in base 2 and in base 3, base_scales x, y}

@@ -17,8 +17,21 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "pbrt-rs_amd"))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.dirname(HERE))
 import oracle  # noqa: E402
 from pbrt_hip import scenes  # noqa: E402
+
+
+def glossy_envmap():
+    """(viii) the glossy mixed scene (matte / mirror / glass / plastic / metal) under a small image map, path, depth 8"""
+    from glossy_cases import glossy_envmap_golden
+    sc, cam, w, h, spp, kw, light, rgb, l2w = glossy_envmap_golden()
+    osc = oracle.OracleScene(sc)
+    osc.set_environment_map(light, rgb, l2w)
+    film, st = osc.render(scenes.camera_dict_to_floats(cam), w, h, spp, n_threads=1, **kw)
+    np.savez_compressed(os.path.join(HERE, "glossy_envmap_64x64x4.npz"), film=film,
+                        stats=np.array([st["rays"], st["node_tests"], st["prim_tests"], st["camera_samples"]], dtype=np.uint64))
+    osc.close()
 
 
 def main():
@@ -92,6 +105,7 @@ def main():
         out[name] = film
         out[name + "__rays"] = np.array([st["rays"], st["camera_samples"]], dtype=np.uint64)
     np.savez_compressed(os.path.join(HERE, "variants_48x32.npz"), **out)
+    glossy_envmap()
     print("golden fixtures written to", HERE)
 
 

@@ -414,3 +414,112 @@ def test_fresnel_and_refraction_against_float64():
         # Snell: the tangential parts are antiparallel with ratio eta
         tan_i, tan_t = W - ci * N, wt.astype(np.float64) - float(np.dot(wt, N)) * N
         assert np.max(np.abs(tan_t + eta * tan_i)) <= 1e-5
+
+
+def _oracle_fr_conductor(cos_i, eta, k):
+    out = np.zeros(3, dtype=np.float32)
+    e, kk = np.asarray(eta, np.float32), np.asarray(k, np.float32)
+    L.orc_fr_conductor.argtypes = [ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    L.orc_fr_conductor.restype = None
+    L.orc_fr_conductor(ctypes.c_float(cos_i), e.ctypes.data, kk.ctypes.data, out.ctypes.data)
+    return out.astype(np.float64)
+
+
+def test_fr_conductor_against_the_complex_fresnel_equations():
+    """reflection.rs:42-67 (fr_conductor, eta_i = 1) against the Fresnel equations for a complex index n = eta + i k evaluated
+    from scratch in complex128: cos_t = sqrt(1 - sin_i^2 / n^2), r_s = (cos_i - n cos_t) / (cos_i + n cos_t),
+    r_p = (n cos_i - cos_t) / (n cos_i + cos_t), F = (|r_s|^2 + |r_p|^2) / 2. The float32 routine is some 25 operations on
+    values of order 1 to eta^2 + k^2 whose result lies in [0, 1]: the bound of the dielectric pin, 64 u absolute (u = 2^-24).
+    One cancellation is the formula's own: a^2 = (sqrt(t0^2 + 4 eta^2 k^2) + t0) / 2 with t0 = eta^2 - k^2 - sin^2 < 0 loses
+    sqrt(..) / (sqrt(..) + t0) of its precision (past total reflection of a nearly real index below 1, a^2 -> eta^2 k^2 /
+    |t0|); a enters r_s and r_p through 2 a cos_i, so the bound is scaled by that ratio, evaluated in float64. It is 1 to 2 for
+    the metals the scenes use (eta, k of order 1). Exact properties: F in [0, 1]; F -> 1 at grazing incidence; k = 0 is the dielectric formula."""
+    rng = np.random.default_rng(23)
+    u = 2.0 ** -24
+    worst = 0.0
+    for i in range(4000):
+        cos_i = float(f32(rng.uniform(0, 1)))
+        eta = rng.uniform(0.1, 4.0, 3).astype(f32)
+        k = rng.uniform(0.0, 5.0, 3).astype(f32)
+        if i % 8 == 0:
+            k[:] = 0
+            eta = rng.uniform(1.05, 2.5, 3).astype(f32)
+        got = _oracle_fr_conductor(cos_i, eta, k)
+        n = eta.astype(np.float64) + 1j * k.astype(np.float64)
+        si2 = 1.0 - cos_i * cos_i
+        ct = np.sqrt(1.0 - si2 / (n * n))
+        rs = (cos_i - n * ct) / (cos_i + n * ct)
+        rp = (n * cos_i - ct) / (n * cos_i + ct)
+        want = 0.5 * (np.abs(rs) ** 2 + np.abs(rp) ** 2)
+        e64, k64 = eta.astype(np.float64), k.astype(np.float64)
+        t0 = e64 ** 2 - k64 ** 2 - si2
+        root = np.sqrt(t0 ** 2 + 4 * e64 ** 2 * k64 ** 2)
+        amp = np.where(t0 < 0, root / np.maximum(root + t0, 1e-300), 1.0)
+        worst = max(worst, float(np.max(np.abs(got - want) / amp)) / u)
+        assert np.all(np.abs(got - want) <= 64 * u * amp), (cos_i, eta, k, got, want)
+        assert np.all((got >= 0.0) & (got <= 1.0 + 2 * u))
+        if i % 8 == 0:   # k = 0: fr_dielectric(cos_i, 1, eta)
+            for c in range(3):
+                d = float(L.orc_fr_dielectric(ctypes.c_float(cos_i), ctypes.c_float(1.0), ctypes.c_float(float(eta[c]))))
+                assert abs(got[c] - d) <= 64 * u
+    print(f"fr_conductor: worst |F32 - F64| / amplification = {worst:.1f} u")
+    assert np.all(_oracle_fr_conductor(0.0, (0.2, 0.92, 1.1), (3.9, 2.45, 2.14)) == 1.0)  # grazing
+    # normal incidence: ((eta - 1)^2 + k^2) / ((eta + 1)^2 + k^2)
+    eta, k = np.array([0.2, 0.92, 1.1], f32).astype(np.float64), np.array([3.9, 2.45, 2.14], f32).astype(np.float64)
+    want = ((eta - 1) ** 2 + k ** 2) / ((eta + 1) ** 2 + k ** 2)
+    assert np.all(np.abs(_oracle_fr_conductor(1.0, eta, k) - want) <= 64 * u)
+
+
+def _oracle_tr(ax, ay, wh, w, w2):
+    out = np.zeros(3, dtype=np.float32)
+    a, b, c = (np.asarray(v, np.float32) for v in (wh, w, w2))
+    L.orc_trowbridge_reitz.argtypes = [ctypes.c_float, ctypes.c_float] + [ctypes.c_void_p] * 4
+    L.orc_trowbridge_reitz.restype = None
+    L.orc_trowbridge_reitz(ctypes.c_float(ax), ctypes.c_float(ay), a.ctypes.data, b.ctypes.data, c.ctypes.data, out.ctypes.data)
+    return out.astype(np.float64)
+
+
+def test_trowbridge_reitz_d_lambda_g_at_exact_points():
+    """microfacet.rs:176-199, 18-20 at points where the closed form is elementary. Normal incidence: D = 1 / (pi ax ay),
+    Lambda = 0, G = 1. alpha = 1: D = 1 / pi at every angle, Lambda = (1 / cos - 1) / 2. 45 degrees (tan = 1) along x and
+    along y: D = 4 a^2 / (pi (a^2 + 1)^2) with the other axis' alpha in the normalisation, Lambda = (sqrt(1 + a^2) - 1) / 2,
+    G = 1 / (1 + Lambda_o + Lambda_i). The closed forms are evaluated in float64 at the float32 inputs (tan^2 from the rounded
+    z); the float32 routine rounds about a dozen times with no cancellation at these points (1 - cos^2 at cos^2 = 1/2): 16 u
+    relative (u = 2^-24). roughness_to_alpha is the quartic in log(r) evaluated in double, clamped at 1e-3."""
+    u = 2.0 ** -24
+    z = (0.0, 0.0, 1.0)
+    for ax, ay in ((0.5, 0.5), (0.15, 0.6), (1.0, 1.0), (1e-3, 1e-3)):
+        ax32, ay32 = float(f32(ax)), float(f32(ay))
+        d, lam, g = _oracle_tr(ax, ay, z, z, z)
+        assert abs(d - 1 / (np.pi * ax32 * ay32)) <= 16 * u * d and lam == 0.0 and g == 1.0
+    s = float(f32(np.sqrt(0.5)))
+    for ax, ay in ((0.5, 0.5), (0.15, 0.6), (1.0, 1.0), (0.05, 0.3)):
+        ax32, ay32 = float(f32(ax)), float(f32(ay))
+        for w, a in (((s, 0.0, s), ax32), ((0.0, s, s), ay32), ((-s, 0.0, s), ax32), ((0.0, -s, -s), ay32)):
+            t2 = (1 - s * s) / (s * s)                 # tan^2 of the rounded direction
+            d, lam, g = _oracle_tr(ax, ay, w, w, z)
+            want_d = 1 / (np.pi * ax32 * ay32 * s ** 4 * (1 + t2 / a ** 2) ** 2)
+            want_l = (np.sqrt(1 + a * a * t2) - 1) / 2
+            assert abs(d - want_d) <= 16 * u * want_d, (ax, ay, w, d, want_d)
+            assert abs(lam - want_l) <= 16 * u * max(want_l, 1.0), (ax, ay, w, lam, want_l)
+            assert abs(g - 1 / (1 + want_l)) <= 16 * u
+            g2 = _oracle_tr(ax, ay, w, w, w)[2]
+            assert abs(g2 - 1 / (1 + 2 * want_l)) <= 16 * u
+    for cos_t in (0.9, 0.5, 0.1):
+        c = float(f32(cos_t))
+        w = (float(f32(np.sqrt(1 - c * c))), 0.0, c)
+        d, lam, _ = _oracle_tr(1.0, 1.0, w, w, z)
+        sin2 = max(0.0, 1 - c * c)
+        # alpha = 1: 1 / (pi cos^4 (1 + tan^2)^2) = 1 / pi (1 - cos^2 + cos^2 = 1 up to the float32 roundings of cos^2)
+        assert abs(d - 1 / np.pi) <= 16 * u / np.pi
+        want_l = (np.sqrt(1 + sin2 / (c * c)) - 1) / 2
+        assert abs(lam - want_l) <= 16 * u * max(want_l, 1.0)
+    # grazing: tan is infinite -> D = 0, Lambda = 0 (microfacet.rs:178-180, 190-192)
+    d, lam, _ = _oracle_tr(0.5, 0.5, (1.0, 0.0, 0.0), (1.0, 0.0, 0.0), z)
+    assert d == 0.0 and lam == 0.0
+    L.orc_roughness_to_alpha.argtypes = [ctypes.c_float]
+    L.orc_roughness_to_alpha.restype = ctypes.c_float
+    for r in (1e-4, 1e-3, 0.01, 0.1, 0.5, 1.0):
+        x = np.log(max(float(f32(r)), 1e-3))
+        want = 1.62142 + 0.819955 * x + 0.1734 * x ** 2 + 0.0171201 * x ** 3 + 0.000640711 * x ** 4
+        assert float(L.orc_roughness_to_alpha(ctypes.c_float(r))) == float(f32(want))

@@ -57,6 +57,24 @@ def test_images(hip_ctx, name):
     gsc.close()
 
 
+def test_glossy_envmap_image(hip_ctx):
+    """The device against the committed film of the glossy mixed scene under an image map, held as the images above."""
+    from glossy_cases import glossy_envmap_golden
+    sc, cam, w, h, spp, kw, light, rgb, l2w = glossy_envmap_golden()
+    d = np.load(os.path.join(G, "glossy_envmap_64x64x4.npz"))
+    gsc = pbrt_hip.Scene(hip_ctx, sc)
+    gsc.set_environment_map(light, rgb, l2w)
+    film, st = gsc.render(cam, w, h, spp, **kw)
+    exp = d["film"]
+    assert np.array_equal(film[..., 3], exp[..., 3])
+    rgb_g, rgb_e = pbrt_hip.film_to_rgb(film), pbrt_hip.film_to_rgb(exp)
+    assert np.all(np.abs(rgb_g - rgb_e) <= 1e-5 * np.maximum(1.0, np.abs(rgb_e)))
+    assert float(np.sqrt(np.mean((rgb_g.astype(np.float64) - rgb_e) ** 2))) <= 1e-6
+    assert st["rays_closest"] + st["rays_shadow"] == int(d["stats"][0])
+    assert st["camera_samples"] == int(d["stats"][3])
+    gsc.close()
+
+
 def test_thin_lens_camera(hip_ctx):
     """PerspectiveCamera with lens_radius > 0 (perspective.rs:99-105) vs the oracle."""
     import oracle

@@ -1,7 +1,9 @@
 """Fuzz campaign: random small scenes through Integrator::render on the GPU and in the oracle, same seed; every film must agree
 to the parity tests' tolerance and every ray count exactly. What the fixed scenes of tests/test_gpu_render.py cannot reach:
 random mixes of geometry scale, shared-vertex meshes, materials, light kinds, integrators, samplers, depths, crop windows.
-usage: python tools/fuzz_render.py [n_cases] [first_seed]   (GPU box; prints one line per failing case, exits 1 if any)"""
+usage: python tools/fuzz_render.py [n_cases] [first_seed] [--glossy-envmap]   (GPU box; prints one line per failing case, exits 1 if any)
+--glossy-envmap adds plastic / metal rows (on triangles, spheres and instances; sometimes anisotropic or unremapped through
+set_material_roughness) and image maps on the infinite lights to the cases; without it every seed is the case it always was."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "pbrt-rs_amd")); sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -21,8 +23,47 @@ def grid_mesh(rng, n, scale):
     return (g * scale).astype(np.float32), idx
 
 
-def make_case(seed):
+def glossy_rows(grng):
+    """2-3 plastic / metal rows with random Kd / Ks / eta / k and a roughness from 1e-3 to 1, and the roughness calls
+    (row offset, u, v, remap) some of them get afterwards"""
+    rows, calls = [], []
+    for k in range(int(grng.integers(2, 4))):
+        r = float(10.0 ** grng.uniform(-3, 0))
+        if k == 0 or (k == 2 and grng.random() < 0.5):
+            kd = (0.0, 0.0, 0.0) if grng.random() < 0.15 else tuple(grng.uniform(0.05, 0.7, 3))
+            ks = (0.0, 0.0, 0.0) if grng.random() < 0.15 else tuple(grng.uniform(0.1, 0.9, 3))
+            rows.append(scenes.plastic(kd, ks, r))
+            if grng.random() < 0.3:
+                calls.append((k, r, r, False))
+        else:
+            k_ = (0.0, 0.0, 0.0) if grng.random() < 0.1 else tuple(grng.uniform(0.0, 5.0, 3))
+            rows.append(scenes.metal(tuple(grng.uniform(0.1, 3.0, 3)), k_, r))
+            if grng.random() < 0.5:
+                calls.append((k, r, float(10.0 ** grng.uniform(-3, 0)), bool(grng.integers(0, 2))))
+    return rows, calls
+
+
+def environment_maps(grng, lights):
+    """image maps for some of the infinite lights: (light, rgb, light_to_world or None); 1x1 to 64x32, powers of two and not"""
+    maps = []
+    for i in np.nonzero(lights["type"] == scenes.LIGHT_INFINITE)[0]:
+        if grng.random() < 0.65:
+            w, h = [(1, 1), (2, 1), (4, 2), (8, 4), (16, 8), (64, 32), (3, 2), (5, 7), (24, 10), (50, 20), (64, 32), (33, 17)][int(grng.integers(0, 12))]
+            rgb = grng.uniform(0.05, 1.5, (h, w, 3)).astype(np.float32)
+            if grng.random() < 0.35:
+                rgb[int(grng.integers(0, h)), int(grng.integers(0, w))] = grng.uniform(50, 500, 3).astype(np.float32)
+            m = None
+            if grng.random() < 0.5:
+                m = np.eye(4, dtype=np.float32)
+                m[:3, :3] = scenes._random_rigid(grng.uniform(0, 1, 3))[:3, :3].astype(np.float32)
+            maps.append((int(i), rgb, m))
+    return maps
+
+
+def make_case(seed, glossy_envmap=False):
     rng = np.random.default_rng(seed)
+    grng = np.random.default_rng(seed ^ 0x910557e)   # --glossy-envmap: its own generator, the draws below stay what they were
+    roughness_calls, n_glossy = [], 0
     scale = float(rng.choice([0.01, 1.0, 1.0, 1.0, 300.0]))
     kind = rng.choice(["cloud", "grid", "cloud+grid", "cornell"])
     pos, idx = [], []
@@ -64,6 +105,13 @@ def make_case(seed):
             lights.append(scenes.spot_light(tuple(rng.uniform(1, 2, 3) * scale), (0.0, 0.0, 0.0), tuple(rng.uniform(2, 8, 3) * scale * scale)))
         if not lights:
             lights.append((scenes.LIGHT_INFINITE, (1.0, 1.0, 1.0), -1, 0, 1))
+        if glossy_envmap and grng.random() < 0.8:
+            rows, calls = glossy_rows(grng)
+            n_glossy = len(rows)
+            roughness_calls = [(len(mats) + k, u, v, remap) for k, u, v, remap in calls]
+            mats = np.concatenate([mats, scenes._materials(rows)])
+            pick = (grng.random(n_t) < float(grng.choice([0.1, 0.4, 0.9]))) & (tri_light < 0)
+            tri_material[pick] = (len(mats) - n_glossy + grng.integers(0, n_glossy, n_t))[pick].astype(np.int32)
         extra = {}
         r_extra = rng.random()
         if r_extra < 0.2:
@@ -76,6 +124,9 @@ def make_case(seed):
                     lights.append((scenes.LIGHT_DIFFUSE_AREA, tuple(rng.uniform(2, 12, 3)), n_t + k, 0, int(rng.integers(1, 3))))
                 sph.append([*(rng.uniform(-0.8, 0.8, 3) * scale), float(rng.uniform(0.1, 0.5)) * scale, 0 if light >= 0 else int(rng.integers(0, 3)), light, 0, 0])
             extra["spheres"] = np.array(sph, dtype=np.float32)
+            for row in extra["spheres"]:
+                if n_glossy and row[5] < 0 and grng.random() < 0.4:
+                    row[4] = len(mats) - n_glossy + int(grng.integers(0, n_glossy))
         elif r_extra < 0.35 and not any(tri_light >= 0):
             # TransformedPrimitive instances of the mesh, material by instance (primitive.rs:105-159; instances carry no area lights)
             n_inst = int(rng.integers(1, 12))
@@ -87,6 +138,9 @@ def make_case(seed):
             inst[:, :, 3, :] = (0, 0, 0, 1)
             extra["instances"] = inst
             extra["instance_material"] = rng.integers(-1, 3, n_inst).astype(np.int32)
+            if n_glossy:
+                pick = grng.random(n_inst) < 0.3
+                extra["instance_material"][pick] = (len(mats) - n_glossy + grng.integers(0, n_glossy, n_inst))[pick]
         sc = dict(positions=positions, indices=indices, tri_material=tri_material, materials=mats, tri_light=tri_light,
                   lights=scenes._lights(lights), **extra)
         if not extra and rng.random() < 0.12:
@@ -118,6 +172,9 @@ def make_case(seed):
                       instance_material=rng.integers(-1, 3, n_inst).astype(np.int32),
                       world=dict(positions=wp, indices=wi, tri_material=np.zeros(4, dtype=np.int32), tri_light=wl),
                       materials=mats, lights=scenes._lights(lts), positions=positions, indices=indices)
+            if n_glossy:
+                pick = grng.random(n_inst) < 0.3
+                sc["instance_material"][pick] = (len(mats) - n_glossy + grng.integers(0, n_glossy, n_inst))[pick]
         elif not extra and rng.random() < 0.25:
             # TriangleMesh n / s / uv (triangle.rs:17-26, 252-312): shading frames from per-vertex data
             sc = scenes.with_vertex_shading(sc, seq=int(rng.integers(1, 1000)), normals=bool(rng.integers(0, 2)), uvs=bool(rng.integers(0, 2)) or True,
@@ -177,18 +234,33 @@ def make_case(seed):
         # merges in the oracle — only the order of the additions differs (tests/test_gpu_render.py::test_reconstruction_filters)
         fk = [("gaussian", 2.0, 2.0, 0.0), ("mitchell", 2.0, 1 / 3, 1 / 3), ("triangle", 1.5, 0.0, 0.0), ("lanczos", 3.0, 3.0, 0.0)][int(rng.integers(0, 4))]
         kw["filter"] = pbrt_hip.filter_table(fk[0], fk[1], fk[1], fk[2], fk[3])
+    opts["roughness"] = roughness_calls
+    opts["maps"] = environment_maps(grng, sc["lights"]) if glossy_envmap else []
+    opts["glossy_used"] = bool(n_glossy and (np.any(sc.get("tri_material", np.zeros(0)) >= len(sc["materials"]) - n_glossy)
+                                             or any(np.any(o["tri_material"] >= len(sc["materials"]) - n_glossy) for o in sc.get("objects", []))
+                                             or np.any(sc.get("instance_material", np.zeros(0)) >= len(sc["materials"]) - n_glossy)
+                                             or ("spheres" in sc and np.any(sc["spheres"][:, 4] >= len(sc["materials"]) - n_glossy))))
     what = kind + (" +spheres" if "spheres" in sc else "") + (" two-level" if "objects" in sc else " instanced" if "instances" in sc else "")
     what += (" +vertex data" if ("normals" in sc or "uvs" in sc or "tangents" in sc) else "")
-    return sc, cam, w, h, spp, kw, gpu_only, opts, f"{what} scale {scale} tris {len(sc['indices'])} lights {len(sc['lights'])} {w}x{h}x{spp} {kw} {gpu_only} {opts}"
+    if glossy_envmap:
+        what += f" glossy rows {n_glossy} roughness calls {roughness_calls} maps {[(i, m.shape[1], m.shape[0], x is not None) for i, m, x in opts['maps']]}"
+    shown = {k: v for k, v in opts.items() if k not in ("roughness", "maps", "glossy_used")}
+    return sc, cam, w, h, spp, kw, gpu_only, opts, f"{what} scale {scale} tris {len(sc['indices'])} lights {len(sc['lights'])} {w}x{h}x{spp} {kw} {gpu_only} {shown}"
 
 
 def main():
-    n_cases = int(sys.argv[1]) if len(sys.argv) > 1 else 200
-    first = int(sys.argv[2]) if len(sys.argv) > 2 else 0
+    glossy_envmap = "--glossy-envmap" in sys.argv[1:]
+    args = [a for a in sys.argv[1:] if a != "--glossy-envmap"]
+    n_cases = int(args[0]) if len(args) > 0 else 200
+    first = int(args[1]) if len(args) > 1 else 0
     ctx = pbrt_hip.Context(0)
     bad, refused, t0 = 0, 0, time.time()
+    mix = dict(glossy=0, maps=0, both=0)
     for seed in range(first, first + n_cases):
-        sc, cam, w, h, spp, kw, gpu_only, opts, desc = make_case(seed)
+        sc, cam, w, h, spp, kw, gpu_only, opts, desc = make_case(seed, glossy_envmap)
+        mix["glossy"] += opts["glossy_used"]
+        mix["maps"] += bool(opts["maps"])
+        mix["both"] += bool(opts["glossy_used"] and opts["maps"])
         ctx.set_traversal(pbrt_hip.TRAVERSAL_AUTO)
         try:
             if opts["device_build"]:
@@ -201,6 +273,11 @@ def main():
                     gsc = pbrt_hip.Scene(ctx, sc)
                 finally:
                     ctx.set_wide_layout(pbrt_hip.WIDE_LAYOUT_AUTO)
+            for scene in (osc, gsc):   # --glossy-envmap: the same roughness calls and maps on both sides
+                for m_, u_, v_, remap_ in opts["roughness"]:
+                    scene.set_material_roughness(m_, u_, v_, remap=remap_)
+                for light_, rgb_, l2w_ in opts["maps"]:
+                    scene.set_environment_map(light_, rgb_, l2w_)
             okw = dict(kw)
             film_c, st_c = osc.render(scenes.camera_dict_to_floats(cam), w, h, spp, n_threads=4, **okw)
             ctx.set_traversal(opts["traversal"])
@@ -266,6 +343,9 @@ def main():
             print(f"ERROR seed {seed}: {desc}\n   {type(e).__name__}: {e}", flush=True)
         if (seed - first + 1) % 50 == 0:
             print(f"... {seed - first + 1} cases, {bad} bad, {time.time() - t0:.0f} s", flush=True)
+    if glossy_envmap:
+        print(f"fuzz_render --glossy-envmap: {mix['glossy']} cases with a glossy row in use, {mix['maps']} with an image map, {mix['both']} with both; "
+              f"{time.time() - t0:.0f} s", flush=True)
     print(f"fuzz_render: {n_cases} cases from seed {first}: {bad} mismatching"
           + (f" ({refused} refused where the reference panics: Halton arrays past 1000 dimensions)" if refused else ""), flush=True)
     sys.exit(1 if bad else 0)

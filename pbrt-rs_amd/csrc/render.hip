@@ -688,16 +688,21 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
     if (export_mode) rp.spp_per_pass = rp.spp;  // one pass: the export is indexed by the paths of that pass
     int spp_pass = rp.spp_per_pass > 0 ? rp.spp_per_pass : 0;
     if (spp_pass == 0) {
-        // As many samples of a pixel in flight as half of the free HBM holds (about 400 B of path state, queue and
-        // sort slots per path; the stage machine of the other integrators adds its frame stack): a whole 64-spp
-        // 1080p frame is 133 M paths = 50 GB of the 288 GB and runs 6 large wavefronts instead of 48 small ones
-        // (+10 % on config 3: fewer launches and host round trips, shorter tails).
+        // As many samples of a pixel in flight as two thirds of the free HBM hold (the other integrators: half of it, as
+        // ever). The path integrator takes 524 B per path:
+        // 192 B rays (two generations) + 96 B hits + 104 B pending estimates (two generations) + 52 B persistent state +
+        // 32 B queues + 48 B sort and special-list slots; 550 leaves room for the sampler tables. The others keep one
+        // generation and add their stage machine's frame stack. A whole 64-spp 1080p frame is 133 M paths = 70 GB of the
+        // 288 GB and runs 6 large wavefronts instead of 48 small ones (+10 % on config 3: fewer launches and host round
+        // trips, shorter tails). The share was one half while a path took 376 B; at 524 B a half no longer admits the
+        // 265 M paths (145 GB) of a 32-spp pass of a 4K frame, two thirds (of 280 GB free: 340 M paths) do.
         size_t free_b = 0, total_b = 0;
         HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
         for (const auto& b : ctx->block_cache)
             if (!b.in_use) free_b += b.bytes;  // blocks kept from the previous render are available to this one
-        const int64_t per_path = 400 + (rp.integrator != PBRT_INTEGRATOR_PATH ? 24 + 48ll * std::max(1, rp.max_depth) : 0);
-        const int64_t target_paths = std::max<int64_t>(1ll << 20, std::min<int64_t>(1ll << 28, (int64_t)(free_b / 2) / per_path));
+        const int64_t per_path = rp.integrator == PBRT_INTEGRATOR_PATH ? 550 : 400 + 24 + 48ll * std::max(1, rp.max_depth);
+        const size_t share = rp.integrator == PBRT_INTEGRATOR_PATH ? free_b / 3 * 2 : free_b / 2;
+        const int64_t target_paths = std::max<int64_t>(1ll << 20, std::min<int64_t>(1ll << 28, (int64_t)share / per_path));
         spp_pass = (int)std::max<int64_t>(1, std::min<int64_t>(rp.spp, target_paths / n_pix));
     }
     spp_pass = std::min(spp_pass, rp.spp);
@@ -720,6 +725,12 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
     ps.nee_b = buf.alloc<float4>(N, &ok);
     ps.nee_light = buf.alloc<int>(N, &ok);
     ps.pfilm = buf.alloc<float2>(N, &ok);
+    // the path integrator keeps two generations of the rays and the pending estimates (wf_state.h); the others one
+    ps.ray_next = direct ? ps.ray : buf.alloc<float4>(N * 6, &ok);
+    ps.nee_a_next = direct ? ps.nee_a : buf.alloc<float4>(N, &ok);
+    ps.nee_f_next = direct ? ps.nee_f : buf.alloc<float4>(N, &ok);
+    ps.nee_b_next = direct ? ps.nee_b : buf.alloc<float4>(N, &ok);
+    ps.nee_light_next = direct ? ps.nee_light : buf.alloc<int>(N, &ok);
     Queues q[2];
     for (int k = 0; k < 2; ++k) {
         q[k].trace = buf.alloc<uint32_t>(N * 3, &ok);
@@ -759,14 +770,15 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
     if (rp.shade_order < 0 || rp.shade_order > 2) return invalid("shade_order must be 0 (queue order), 1 (by material inside blocks) or 2 (sorted queue)");
     const bool sort_shade = rp.shade_order == 2 && rp.integrator == PBRT_INTEGRATOR_PATH;
     const bool bin_shade = rp.shade_order == 1 && rp.integrator == PBRT_INTEGRATOR_PATH;
-    uint32_t *shade_keys[2] = {nullptr, nullptr}, *shade_sorted = nullptr;
+    uint32_t *shade_keys[2] = {nullptr, nullptr}, *shade_positions = nullptr, *shade_sorted = nullptr;
     void* shade_tmp = nullptr;
     size_t shade_tmp_bytes = 0;
     if (sort_shade) {
         shade_keys[0] = buf.alloc<uint32_t>(N, &ok);
         shade_keys[1] = buf.alloc<uint32_t>(N, &ok);
+        shade_positions = buf.alloc<uint32_t>(N, &ok);
         shade_sorted = buf.alloc<uint32_t>(N, &ok);
-        if (pb::sort_pairs_u32(st, nullptr, &shade_tmp_bytes, shade_keys[0], shade_keys[1], shade_sorted, shade_sorted, N, 3) != 0)
+        if (pb::sort_pairs_u32(st, nullptr, &shade_tmp_bytes, shade_keys[0], shade_keys[1], shade_positions, shade_sorted, N, 3) != 0)
             return invalid("rocPRIM radix sort: size query failed");
         shade_tmp = buf.alloc<char>(shade_tmp_bytes, &ok);
     }
@@ -1096,27 +1108,34 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
                     hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_AO, false>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
             }
             else {
-                Queues qin = q[cur];
+                const Queues qin = q[cur];
+                const uint32_t* order = nullptr;  // shade_order 2: the queue positions in material order
                 if (sort_shade && wavefront >= 1 && n_shade >= (1u << 10)) {  // the first wavefront is all camera hits in pixel order
                     hipLaunchKernelGGL(k_shade_sort_keys, dim3((n_shade + 255) / 256), dim3(256), 0, st, sc, ps, q[cur].shade, n_shade,
-                                       pp.max_depth, shade_keys[0]);
+                                       pp.max_depth, shade_keys[0], shade_positions);
                     size_t tb = shade_tmp_bytes;
-                    if (pb::sort_pairs_u32(st, shade_tmp, &tb, shade_keys[0], shade_keys[1], q[cur].shade, shade_sorted, n_shade, 3) != 0 &&
+                    if (pb::sort_pairs_u32(st, shade_tmp, &tb, shade_keys[0], shade_keys[1], shade_positions, shade_sorted, n_shade, 3) != 0 &&
                         rc == PBRT_HIP_OK) {
                         ctx->last_error = "rocPRIM radix sort failed";
                         rc = PBRT_HIP_ERR_DEVICE;
                     }
-                    qin.shade = shade_sorted;
+                    order = shade_sorted;
                 }
                 const dim3 sg((n_shade + 255) / 256), sb(256);
                 if (bin_shade && wavefront >= 1 && s->glossy)
-                    hipLaunchKernelGGL((k_shade<true, true>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade);
+                    hipLaunchKernelGGL((k_shade<true, true>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
                 else if (bin_shade && wavefront >= 1)
-                    hipLaunchKernelGGL((k_shade<true, false>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade);
+                    hipLaunchKernelGGL((k_shade<true, false>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
                 else if (s->glossy)
-                    hipLaunchKernelGGL((k_shade<false, true>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade);
+                    hipLaunchKernelGGL((k_shade<false, true>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
                 else
-                    hipLaunchKernelGGL((k_shade<false, false>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade);
+                    hipLaunchKernelGGL((k_shade<false, false>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
+                // what this launch wrote is the generation the next trace and shade launches read
+                std::swap(ps.ray, ps.ray_next);
+                std::swap(ps.nee_a, ps.nee_a_next);
+                std::swap(ps.nee_f, ps.nee_f_next);
+                std::swap(ps.nee_b, ps.nee_b_next);
+                std::swap(ps.nee_light, ps.nee_light_next);
             }
             RENDER_TRY(hipGetLastError());
             RENDER_TRY(hipMemcpyAsync(ctx->h_counts, q[nxt].counts64, sizeof(counts), hipMemcpyDeviceToHost, st));
@@ -1149,7 +1168,8 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
                 local.trace_ms += ms;
                 local.trace_launches += 1;
                 if (ctx->trace_log)
-                    std::fprintf(stderr, "[pbrt_hip] k_trace: %u rays %.3f ms (%.0f Mrays/s)\n", n_trace, ms, n_trace / ms * 1e-3);
+                    std::fprintf(stderr, "[pbrt_hip] k_trace: %u rays %.3f ms (%.0f Mrays/s), k_shade: %u paths\n", n_trace, ms, n_trace / ms * 1e-3,
+                                 n_shade);
                 ctx->trace_ms += ms;
                 ctx->trace_launches += 1;
             }

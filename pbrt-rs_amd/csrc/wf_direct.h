@@ -251,10 +251,10 @@ __global__ void __launch_bounds__(256, (GLOSSY && MODE == PBRT_INTEGRATOR_DIRECT
                 int nee_flags;
                 if (GLOSSY) {
                     NsBsdf nsb = ns_bsdf(sc.materials[sf.material]);
-                    nee_flags = estimate_direct_emit(sc, ps, p, sf, fr, nsb.n > 0, nsb, light_num, ul0, ul1, us0, us1, pick_pdf, T);
+                    nee_flags = estimate_direct_emit(sc, RecordSink{ps, p}, sf, fr, nsb.n > 0, nsb, light_num, ul0, ul1, us0, us1, pick_pdf, T);
                 } else {
                     bool matte = (mat.type == PBRT_MAT_MATTE) && !is_black(kd);
-                    nee_flags = estimate_direct_emit(sc, ps, p, sf, fr, matte, MatteBsdf{kd}, light_num, ul0, ul1, us0, us1, pick_pdf, T);
+                    nee_flags = estimate_direct_emit(sc, RecordSink{ps, p}, sf, fr, matte, MatteBsdf{kd}, light_num, ul0, ul1, us0, us1, pick_pdf, T);
                 }
                 stage += 1;
                 if (nee_flags) {

@@ -169,7 +169,7 @@ struct WavefrontRayIO {
     int n_segments;
     PB_DEV uint32_t n() const { return count; }
     PB_DEV int segments() const { return n_segments; }
-    // The traversal kernels keep a ray's TOKEN from load to store — here the queue entry itself (path << 2 | ray slot), not
+    // The traversal kernels keep a ray's TOKEN from load to store — here the queue entry itself (record << 2 | ray slot), not
     // its position: the store then needs no second look at the queue (one dependent load less in the refill path every
     // idle lane of the wave waits in).
     PB_DEV uint32_t token(uint32_t i) const { return queue[i]; }

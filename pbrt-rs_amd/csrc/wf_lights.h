@@ -276,11 +276,12 @@ __global__ void k_spatial_light_tables(ShadeConsts sc, float* __restrict__ table
 
 // estimate_direct (integrator.rs:136-266), first part: sample the light, evaluate the BSDF, sample the
 // BSDF, evaluate the light pdf. Writes the shadow ray (slot 2), the MIS ray (slot 1) and the pending
-// terms into the path state; returns PF_NEE_* flags for the rays that must be traced. `nonspecular` = the
+// terms through `out` (wf_state.h: RecordSink = into the path state at a known record index, StageSink = k_shade's LDS
+// staging until the index is known); returns PF_NEE_* flags for the rays that must be traced. `nonspecular` = the
 // BSDF has a non-specular lobe, `bsdf` its lobes (MatteBsdf: matte only; NsBsdf: matte, plastic or metal); otherwise f == 0
 // and nothing is emitted.
-template <class Bsdf>
-PB_DEV int estimate_direct_emit(const ShadeConsts& sc, const PathState& ps, uint32_t p, const Surf& sf, const Frame& fr,
+template <class Bsdf, class Sink>
+PB_DEV int estimate_direct_emit(const ShadeConsts& sc, const Sink& out, const Surf& sf, const Frame& fr,
                                 bool nonspecular, const Bsdf& bsdf, int light_num, float ul0, float ul1, float us0, float us1,
                                 float pick_pdf, V3 beta) {
     if (!nonspecular) return 0;
@@ -301,7 +302,7 @@ PB_DEV int estimate_direct_emit(const ShadeConsts& sc, const PathState& ps, uint
             V3 origin = offset_ray_origin(sf.p, sf.p_error, sf.n, p1 - sf.p);
             V3 target = offset_ray_origin(p1, p1_err, p1_n, origin - p1);
             V3 d = target - origin;
-            store_ray(ps, p, RS_SHADOW, origin, d, 1.0f - kShadowEpsilon);
+            out.ray(RS_SHADOW, origin, d, 1.0f - kShadowEpsilon);
             if (lt.delta) {
                 A = mulv(li, f) / light_pdf;  // integrator.rs:196-198: no MIS weight for a delta light
             } else {
@@ -378,34 +379,35 @@ PB_DEV int estimate_direct_emit(const ShadeConsts& sc, const PathState& ps, uint
         if (lpdf != 0.0f) {
             float weight = power_heuristic1(spdf, lpdf);
             V3 o2 = offset_ray_origin(sf.p, sf.p_error, sf.n, wi2);
-            store_ray(ps, p, RS_MIS, o2, wi2, kInf);
-            ps.nee_f[p] = make_float4(f2.x, f2.y, f2.z, weight);
+            out.ray(RS_MIS, o2, wi2, kInf);
+            out.nee_f(make_float4(f2.x, f2.y, f2.z, weight));
             nee_flags |= PF_NEE_MIS;
             // only an area light looks at WHAT the ray hit (integrator.rs:247-256); for the others `found` is enough
             if (sc.mis_bool && lt.type != PBRT_LIGHT_DIFFUSE_AREA) nee_flags |= NEE_MIS_BOOL;
         }
     }
     if (nee_flags) {
-        ps.nee_a[p] = make_float4(A.x, A.y, A.z, pick_pdf);
-        ps.nee_b[p] = make_float4(beta.x, beta.y, beta.z, spdf);
-        ps.nee_light[p] = light_num;
+        out.nee_a(make_float4(A.x, A.y, A.z, pick_pdf));
+        out.nee_b(make_float4(beta.x, beta.y, beta.z, spdf));
+        out.nee_light(light_num);
     }
     return nee_flags;
 }
 
 // estimate_direct, second part: combine the traced shadow / MIS results into Ld (before the division
-// by the light-pick pdf). Also returns the pick pdf and the throughput stored with the estimate.
-PB_DEV V3 estimate_direct_resolve(const ShadeConsts& sc, const PathState& ps, uint32_t p, int flags, float* pick_pdf,
+// by the light-pick pdf). Also returns the pick pdf and the throughput stored with the estimate. `rec` = the record index
+// of the path's rays, hits and pending terms (k_shade: its shade-queue position; k_shade_direct: the path's number).
+PB_DEV V3 estimate_direct_resolve(const ShadeConsts& sc, const PathState& ps, uint32_t rec, int flags, float* pick_pdf,
                                   V3* beta_at_vertex) {
-    float4 na = ps.nee_a[p], nf = ps.nee_f[p], nb = ps.nee_b[p];
-    int light_id = ps.nee_light[p];
+    float4 na = ps.nee_a[rec], nf = ps.nee_f[rec], nb = ps.nee_b[rec];
+    int light_id = ps.nee_light[rec];
     V3 ld = V3{0.0f, 0.0f, 0.0f};
     if (flags & PF_NEE_SHADOW) {
-        bool occluded = ps.hit[hit_index(ps, p, RS_SHADOW)].x != 0.0f;
+        bool occluded = ps.hit[hit_index(ps, rec, RS_SHADOW)].x != 0.0f;
         if (!occluded) ld = ld + V3{na.x, na.y, na.z};
     }
     if (flags & PF_NEE_MIS) {
-        int hslot = __float_as_int(ps.hit[hit_index(ps, p, RS_MIS)].x);
+        int hslot = __float_as_int(ps.hit[hit_index(ps, rec, RS_MIS)].x);
         DevLight lt = sc.lights[light_id];
         V3 li = V3{0.0f, 0.0f, 0.0f};
         if (hslot >= 0) {
@@ -414,15 +416,15 @@ PB_DEV V3 estimate_direct_resolve(const ShadeConsts& sc, const PathState& ps, ui
             int hl = lt.type == PBRT_LIGHT_DIFFUSE_AREA ? (__float_as_int(sc.bvh.tris[3 * (size_t)hslot + 2].w) & kPrimLightMask) - 1 : -2;
             if (hl == light_id) {
                 // (the MIS ray's direction and the hit's barycentrics are read only here: an area light's emitter was hit)
-                float4 r0 = ps.ray[ray_index(ps, p, RS_MIS)], r1 = ps.ray[ray_index(ps, p, RS_MIS) + 1];
+                float4 r0 = ps.ray[ray_index(ps, rec, RS_MIS)], r1 = ps.ray[ray_index(ps, rec, RS_MIS) + 1];
                 V3 wi = V3{r0.w, r1.x, r1.y};
-                float4 hb = ps.hit[hit_index(ps, p, RS_MIS)];
+                float4 hb = ps.hit[hit_index(ps, rec, RS_MIS)];
                 V3 n = tri_interaction_normal(sc.bvh, hslot, hb.y, hb.z, hb.w);
                 if (lt.two_sided || dot(n, -wi) > 0.0f) li = V3{lt.L[0], lt.L[1], lt.L[2]};
             }
         } else if (lt.type == PBRT_LIGHT_INFINITE) {
             if (lt.slot >= 0) {  // the MIS ray escaped: the map's le along it
-                float4 r0 = ps.ray[ray_index(ps, p, RS_MIS)], r1 = ps.ray[ray_index(ps, p, RS_MIS) + 1];
+                float4 r0 = ps.ray[ray_index(ps, rec, RS_MIS)], r1 = ps.ray[ray_index(ps, rec, RS_MIS) + 1];
                 li = env_le(sc.env_maps[lt.slot], V3{r0.w, r1.x, r1.y});
             } else {
                 li = V3{lt.L[0], lt.L[1], lt.L[2]};

@@ -12,13 +12,15 @@ namespace pb {
 //      before shading, so a wave shades (mostly) one material while the block still touches the same 256 paths' state —
 //      the reads stay as coalesced as the queue is (round 3),
 //   2  the whole queue radix-sorted by key (round 2's experiment: lane utilisation doubles, the 290 B of path state per
-//      path become scattered gathers and the kernel gets slower).
+//      path become scattered gathers and the kernel gets slower). What is sorted are the queue POSITIONS (`order`): an
+//      entry's position is the index of its transient records, the path number is looked up from it.
 // Films are bit-identical in all three: a path's arithmetic does not depend on which lane runs it.
-PB_DEV uint32_t shade_key(const ShadeConsts& sc, const PathState& ps, uint32_t p, int max_depth) {
+// p = the path, rec = its position in the shade queue (where its hit record is)
+PB_DEV uint32_t shade_key(const ShadeConsts& sc, const PathState& ps, uint32_t p, uint32_t rec, int max_depth) {
     int fb = __float_as_int(ps.beta[p].w);
     uint32_t key = 0;
     if ((fb & PF_ALIVE) && (fb >> 8) < max_depth) {
-        const size_t hb = hit_index(ps, p, RS_CONT);
+        const size_t hb = hit_index(ps, rec, RS_CONT);
         int slot = __float_as_int(ps.hit[hb].x), inst = hit_instance(ps, hb);
         if (slot >= 0) {
             int mat = __float_as_int(sc.bvh.tris[3 * (size_t)slot + 2].z);
@@ -32,10 +34,11 @@ PB_DEV uint32_t shade_key(const ShadeConsts& sc, const PathState& ps, uint32_t p
     return key;
 }
 __global__ void k_shade_sort_keys(ShadeConsts sc, PathState ps, const uint32_t* __restrict__ shade_queue, uint32_t n, int max_depth,
-                                  uint32_t* __restrict__ keys) {
+                                  uint32_t* __restrict__ keys, uint32_t* __restrict__ positions) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    keys[i] = shade_key(sc, ps, shade_queue[i], max_depth);
+    keys[i] = shade_key(sc, ps, shade_queue[i], i, max_depth);
+    positions[i] = i;
 }
 
 // keys: 0 nothing to shade, 1 + PBRT_MAT_* (none, matte, mirror, glass; the glossy instantiations: plastic, metal as well),
@@ -45,6 +48,7 @@ template <int KEYS>
 struct ShadeBins {
     uint32_t count[4][KEYS];  // per wave of the block, per key
     uint32_t path[256];
+    uint32_t rec[256];  // the entry's queue position travels with it
 };
 
 #ifndef PB_SHADE_WAVES
@@ -52,18 +56,24 @@ struct ShadeBins {
 #endif
 // GLOSSY: the scene's material table holds plastic or metal (MicrofacetReflection lobes, wf_microfacet.h); matte then goes
 // through the same general BSDF (bit for bit the Lambertian code), and the instantiations without it stay as they were.
+// Thread i takes the shade-queue entry at position rec = i (order: rec = order[i], the queue in material order): the path
+// p = qin.shade[rec] with its persistent state at p, and the transient records of this generation at rec. What the path
+// hands to the next launch is staged in LDS and written to the next generation at its position in qout.shade.
 template <bool BIN, bool GLOSSY>
 __global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
-                                                 TileList tiles, uint32_t n_in) {
+                                                 TileList tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
     constexpr int kShadeKeys = shade_keys(GLOSSY);
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool active = i < n_in;
-    uint32_t p = active ? qin.shade[i] : 0u;
+    uint32_t rec = (active && order) ? order[i] : i;
+    uint32_t p = active ? qin.shade[rec] : 0u;
+    __shared__ StagedRecords staged;
+    const StageSink stage{staged};
     if (BIN) {
         // counting sort of the block's 256 entries by key: rank inside the wave by ballot + mbcnt, waves and keys through LDS
         __shared__ ShadeBins<kShadeKeys> bins;
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const uint32_t key = active ? shade_key(sc, ps, p, pp.max_depth) : (uint32_t)(kShadeKeys - 1);
+        const uint32_t key = active ? shade_key(sc, ps, p, rec, pp.max_depth) : (uint32_t)(kShadeKeys - 1);
         uint32_t rank = 0;
 #pragma unroll
         for (int k = 0; k < kShadeKeys; ++k) {
@@ -77,11 +87,13 @@ __global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, P
             for (int w = 0; w < 4; ++w)
                 before += ((uint32_t)k < key || ((uint32_t)k == key && w < wave)) ? bins.count[w][k] : 0u;
         bins.path[before + rank] = p;
+        bins.rec[before + rank] = rec;
         uint32_t n_active = 0;
         for (int k = 0; k < kShadeKeys - 1; ++k)
             for (int w = 0; w < 4; ++w) n_active += bins.count[w][k];
         __syncthreads();
         p = bins.path[threadIdx.x];
+        rec = bins.rec[threadIdx.x];
         active = threadIdx.x < n_active;
     }
     bool emit_cont = false, emit_mis = false, emit_shadow = false, mis_bool = false;
@@ -94,13 +106,13 @@ __global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, P
         V3 beta = V3{bq.x, bq.y, bq.z};
         int fb = __float_as_int(bq.w);
         int flags = fb & 0xff, bounces = fb >> 8;
-        size_t rbase = ray_index(ps, p, RS_CONT), hbase = hit_index(ps, p, RS_CONT);
+        size_t rbase = ray_index(ps, rec, RS_CONT), hbase = hit_index(ps, rec, RS_CONT);
 
         // ---- (1) resolve the pending direct-lighting estimate (integrator.rs:136-266) ----
         if (flags & (PF_NEE_SHADOW | PF_NEE_MIS)) {
             float pick_pdf;
             V3 beta_v;
-            V3 ld = estimate_direct_resolve(sc, ps, p, flags, &pick_pdf, &beta_v);
+            V3 ld = estimate_direct_resolve(sc, ps, rec, flags, &pick_pdf, &beta_v);
             ld = ld / pick_pdf;                 // integrator.rs:133
             L = L + mulv(beta_v, ld);           // path.rs:113-120
             flags &= ~(PF_NEE_SHADOW | PF_NEE_MIS);
@@ -137,7 +149,7 @@ __global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, P
                 if (mat.type == PBRT_MAT_NONE) {
                     // path.rs:95-98: no BSDF -> continue through the surface, bounces unchanged
                     V3 o = offset_ray_origin(sf.p, sf.p_error, sf.n, rd);
-                    store_ray(ps, p, RS_CONT, o, rd, kInf);
+                    stage.ray(RS_CONT, o, rd, kInf);
                     flags |= PF_ALIVE;
                     emit_cont = true;
                 } else {
@@ -171,9 +183,9 @@ __global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, P
                             float ul0, ul1, us0, us1;
                             samp_2d(pp, sm, &ul0, &ul1);
                             samp_2d(pp, sm, &us0, &us1);
-                            int nee_flags = GLOSSY ? estimate_direct_emit(sc, ps, p, sf, fr, true, nsb, light_num, ul0, ul1, us0,
+                            int nee_flags = GLOSSY ? estimate_direct_emit(sc, stage, sf, fr, true, nsb, light_num, ul0, ul1, us0,
                                                                           us1, pick_pdf, beta)
-                                                   : estimate_direct_emit(sc, ps, p, sf, fr, true, MatteBsdf{kd}, light_num, ul0, ul1,
+                                                   : estimate_direct_emit(sc, stage, sf, fr, true, MatteBsdf{kd}, light_num, ul0, ul1,
                                                                           us0, us1, pick_pdf, beta);
                             flags |= nee_flags & 0xff;
                             emit_shadow = (nee_flags & PF_NEE_SHADOW) != 0;
@@ -226,7 +238,7 @@ __global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, P
                             else beta = beta / (1.0f - qq);
                         }
                         if (alive) {
-                            store_ray(ps, p, RS_CONT, o, wi, kInf);
+                            stage.ray(RS_CONT, o, wi, kInf);
                             flags |= PF_ALIVE;
                             emit_cont = true;
                             bounces += 1;
@@ -240,10 +252,12 @@ __global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, P
         ps.beta[p] = make_float4(beta.x, beta.y, beta.z, __int_as_float((bounces << 8) | flags));
     }
 
-    // ---- queue appends (block-aggregated) ----
+    // ---- queue appends (block-aggregated): reserve, move the staged records to the reserved position, write the entries ----
     __shared__ BlockAppend sh;
     const bool again = emit_cont || emit_mis || emit_shadow;
-    block_append(sh, qout, p, emit_cont, emit_mis, emit_shadow, again, cell, mis_bool);
+    const AppendSlots slots = block_reserve(sh, qout, emit_cont, emit_mis, emit_shadow, again);
+    stage.flush(ps, slots.shade, emit_cont, emit_mis, emit_shadow);
+    block_write(qout, slots, p, slots.shade, emit_cont, emit_mis, emit_shadow, again, cell, mis_bool);
 }
 
 }  // namespace pb

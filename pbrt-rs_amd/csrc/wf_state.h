@@ -19,8 +19,10 @@ enum PathFlags : int {
     PF_VALID = 16,      // the path belongs to a pixel inside pixel_bounds
 };
 enum RaySlot : int { RS_CONT = 0, RS_MIS = 1, RS_SHADOW = 2 };
-// A trace-queue entry is path << 2 | what: the three ray slots, and RS_MIS_BOOL = the path's MIS ray (slot RS_MIS) of which
-// only `found` is wanted. estimate_direct (integrator.rs:232-262) calls scene.intersect for the BSDF-sampled direction and
+// A trace-queue entry is record << 2 | what. `record` is the index of the path's transient records (PathState: rays, hits,
+// pending estimate): the path's position in the shade queue of the launch that will read them, NOT the path number — the
+// traversal kernels only ever use it as an index into ps.ray / ps.hit. `what`: the three ray slots, and RS_MIS_BOOL = the
+// path's MIS ray (slot RS_MIS) of which only `found` is wanted. estimate_direct (integrator.rs:232-262) calls scene.intersect for the BSDF-sampled direction and
 // then looks at the hit only if the light is an area light (`light_isect.primitive.get_area_light() == light`); for an
 // infinite light everything that follows depends on `found_surface_interaction` alone. BVHAccel::intersect finds its first
 // hit under the ray's original t_max, walking exactly as intersect_p walks, so `found` = "some leaf whose box passes holds a
@@ -31,23 +33,36 @@ constexpr uint32_t RS_MIS_BOOL = 3;
 // estimate_direct_emit's return value carries this beside the PF_NEE_* bits (it is not a path flag)
 constexpr int NEE_MIS_BOOL = 0x100;
 
+// Two kinds of per-path data. PERSISTENT state (L, beta, rng, samp, pfilm) lives for the whole pass at the path's number p:
+// the film kernels and the sampler find it there. TRANSIENT records (the three rays, their hit records, the pending
+// direct-lighting estimate nee_*) live for one bounce: shade launch k-1 writes them, trace launch k and shade launch k read
+// them, nothing looks at them again. In the path integrator they are indexed by the path's POSITION j IN THE SHADE QUEUE of
+// launch k (the position block_reserve hands out), so that they stay dense while the paths die: at index p a survivor of
+// bounce 3 sat alone in its cache line. Generation 0 is the identity (k_generate: j = p). Launch k reads generation k at its
+// own thread index while it writes generation k+1 at other indices, so rays and nee_* exist twice (`*_next`; the host
+// swaps the two after every launch); the hit records do not: trace launch k writes them after shade launch k-1 has read the
+// previous ones. The stage machine of the other integrators (k_shade_direct) keeps all of it at p and uses no `*_next`.
 struct PathState {
-    float4* ray;     // [ray_index(p, slot) + k]: (o.xyz, d.x) (d.yz, t_max, -)
-    // [hit_index(p, slot)]: (leaf slot of the hit or -1 as int bits, b0, b1, b2) — t is not kept: nothing downstream reads it
+    float4* ray;     // [ray_index(j, slot) + k]: (o.xyz, d.x) (d.yz, t_max, -)
+    // [hit_index(j, slot)]: (leaf slot of the hit or -1 as int bits, b0, b1, b2) — t is not kept: nothing downstream reads it
     // (the hit point comes from the barycentrics, triangle.rs:160-178) and ONE 16-B store per closest-hit ray is one memory
     // instruction less on the traversal kernel's refill path; [.. + 1]: (instance slot, -, -, -), written and read in two-level
     // scenes only; shadow slot: .x = occluded
     float4* hit;
     size_t n_paths;  // paths of a pass (the stride between the three slots' arrays)
-    uint64_t* rng;   // PCG32 state (inc is recomputed from the sample index)
-    float4* L;       // L.rgb, eta_scale
-    float4* beta;    // beta.rgb, (bounces << 8 | flags) as int bits
-    float4* nee_a;   // light-sampling contribution (if unoccluded) rgb, light pick pdf
-    float4* nee_f;   // BSDF-sampled f * |cos| rgb, MIS weight
-    float4* nee_b;   // beta at the NEE vertex rgb, scattering pdf
-    int* nee_light;  // light index of the pending estimate
-    float2* pfilm;   // CameraSample::p_film
-    int* samp;       // sampler counters: current_1d_dimension (Halton: dimension) | current_2d_dimension << 10 | array_2d_offset << 16
+    uint64_t* rng;   // [p] PCG32 state (inc is recomputed from the sample index)
+    float4* L;       // [p] L.rgb, eta_scale
+    float4* beta;    // [p] beta.rgb, (bounces << 8 | flags) as int bits
+    float4* nee_a;   // [j] light-sampling contribution (if unoccluded) rgb, light pick pdf
+    float4* nee_f;   // [j] BSDF-sampled f * |cos| rgb, MIS weight
+    float4* nee_b;   // [j] beta at the NEE vertex rgb, scattering pdf
+    int* nee_light;  // [j] light index of the pending estimate
+    float2* pfilm;   // [p] CameraSample::p_film
+    int* samp;       // [p] sampler counters: current_1d_dimension (Halton: dimension) | current_2d_dimension << 10 | array_2d_offset << 16
+    // the generation k_shade writes (path integrator only)
+    float4* ray_next;
+    float4 *nee_a_next, *nee_f_next, *nee_b_next;
+    int* nee_light_next;
     int two_level;   // the scene has instances: hit records carry the instance slot in their second float4
 };
 // the instance slot of a hit record (-1: none)
@@ -62,11 +77,11 @@ PB_DEV int hit_instance(const PathState& ps, size_t hit_base) { return ps.two_le
 #ifndef PB_HIT_PATH_MAJOR
 #define PB_HIT_PATH_MAJOR 0
 #endif
-PB_DEV size_t ray_index(const PathState& ps, uint32_t p, int slot) {
-    return PB_RAY_PATH_MAJOR ? ((size_t)p * 3 + slot) * 2 : ((size_t)slot * ps.n_paths + p) * 2;
+PB_DEV size_t ray_index(const PathState& ps, uint32_t j, int slot) {
+    return PB_RAY_PATH_MAJOR ? ((size_t)j * 3 + slot) * 2 : ((size_t)slot * ps.n_paths + j) * 2;
 }
-PB_DEV size_t hit_index(const PathState& ps, uint32_t p, int slot) {
-    return PB_HIT_PATH_MAJOR ? ((size_t)p * 3 + slot) * 2 : ((size_t)slot * ps.n_paths + p) * 2;
+PB_DEV size_t hit_index(const PathState& ps, uint32_t j, int slot) {
+    return PB_HIT_PATH_MAJOR ? ((size_t)j * 3 + slot) * 2 : ((size_t)slot * ps.n_paths + j) * 2;
 }
 
 // PixelSampler tables (sampler.rs:252-318) of this GPU's pixels, one column per pixel:
@@ -130,8 +145,8 @@ PB_DEV uint32_t sample_pixel_to_path(const PassParams& pp, int s_local, uint32_t
 }
 
 struct Queues {
-    uint32_t* trace;   // entries: path*4 + slot
-    uint32_t* shade;   // entries: path
+    uint32_t* trace;   // entries: record*4 + slot (record = the path's position in `shade`; k_shade_direct: the path)
+    uint32_t* shade;   // entries: path; entry j's transient records are at index j (k_shade_direct: at the path's number)
     // counts64[0]: low 32 bits = trace-queue length, high 32 bits = shadow rays among them;
     // counts64[1]: shade-queue length
     unsigned long long* counts64;
@@ -180,11 +195,13 @@ struct BlockAppend {
 PB_DEV uint32_t lane_prefix(unsigned long long mask) {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0));
 }
-// Every thread of the block must call this. n_cont/n_mis/n_shadow in {0,1}; again = path stays in the shade queue.
-// cell = ray_sort_cell of the point the path's rays leave from (used only when q.keys is set). mis_bool: the MIS ray is
-// queued as RS_MIS_BOOL.
-PB_DEV void block_append(BlockAppend& sh, const Queues& q, uint32_t p, bool cont, bool mis, bool shadow, bool again,
-                         uint32_t cell = 0, bool mis_bool = false) {
+// Every thread of the block must call block_reserve. cont/mis/shadow: the path queues that ray; again = it stays in the
+// shade queue. Returns where the thread's entries go; `shade` is the path's position in the output shade queue, i.e. the
+// record index of everything it hands to the next launch (known only here, after the block-wide count).
+struct AppendSlots {
+    uint32_t cont, mis, shadow, shade;
+};
+PB_DEV AppendSlots block_reserve(BlockAppend& sh, const Queues& q, bool cont, bool mis, bool shadow, bool again) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_waves = (blockDim.x + 63) >> 6;
     unsigned long long mc = __ballot(cont), mm = __ballot(mis), ms = __ballot(shadow), ma = __ballot(again);
     uint32_t wc = (uint32_t)__popcll(mc), wm = (uint32_t)__popcll(mm), ws = (uint32_t)__popcll(ms);
@@ -212,23 +229,98 @@ PB_DEV void block_append(BlockAppend& sh, const Queues& q, uint32_t p, bool cont
     __syncthreads();
     uint32_t rbase = sh.base_rays + sh.wave_rays[wave];
     // within the wave: all continuation rays, then MIS rays, then shadow rays
-    uint32_t ic = rbase + lane_prefix(mc), im = rbase + wc + lane_prefix(mm), is = rbase + wc + wm + lane_prefix(ms);
-    if (cont) q.trace[ic] = p * 4u + RS_CONT;
-    if (mis) q.trace[im] = p * 4u + (mis_bool ? RS_MIS_BOOL : (uint32_t)RS_MIS);
-    if (shadow) q.trace[is] = p * 4u + RS_SHADOW;
+    AppendSlots a;
+    a.cont = rbase + lane_prefix(mc);
+    a.mis = rbase + wc + lane_prefix(mm);
+    a.shadow = rbase + wc + wm + lane_prefix(ms);
+    a.shade = sh.base_paths + sh.wave_paths[wave] + lane_prefix(ma);
+    return a;
+}
+// The queue writes that go with a reservation: path p into the shade queue, its rays (records at index `rec`) into the
+// trace queue. cell = ray_sort_cell of the point the path's rays leave from (used only when q.keys is set). mis_bool: the
+// MIS ray is queued as RS_MIS_BOOL.
+PB_DEV void block_write(const Queues& q, const AppendSlots& a, uint32_t p, uint32_t rec, bool cont, bool mis, bool shadow, bool again,
+                        uint32_t cell, bool mis_bool) {
+    if (cont) q.trace[a.cont] = rec * 4u + RS_CONT;
+    if (mis) q.trace[a.mis] = rec * 4u + (mis_bool ? RS_MIS_BOOL : (uint32_t)RS_MIS);
+    if (shadow) q.trace[a.shadow] = rec * 4u + RS_SHADOW;
     if (q.keys) {  // the three rays leave from the same surface point: one cell, the any-hit flag on top
-        if (cont) q.keys[ic] = cell;
-        if (mis) q.keys[im] = mis_bool ? (cell | (1u << (kSortKeyBits - 1))) : cell;
-        if (shadow) q.keys[is] = cell | (1u << (kSortKeyBits - 1));
+        if (cont) q.keys[a.cont] = cell;
+        if (mis) q.keys[a.mis] = mis_bool ? (cell | (1u << (kSortKeyBits - 1))) : cell;
+        if (shadow) q.keys[a.shadow] = cell | (1u << (kSortKeyBits - 1));
     }
-    if (again) q.shade[sh.base_paths + sh.wave_paths[wave] + lane_prefix(ma)] = p;
+    if (again) q.shade[a.shade] = p;
+}
+// both at once, for a kernel that keeps its records at the path's number (k_shade_direct)
+PB_DEV void block_append(BlockAppend& sh, const Queues& q, uint32_t p, bool cont, bool mis, bool shadow, bool again,
+                         uint32_t cell = 0, bool mis_bool = false) {
+    const AppendSlots a = block_reserve(sh, q, cont, mis, shadow, again);
+    block_write(q, a, p, p, cont, mis, shadow, again, cell, mis_bool);
 }
 
-PB_DEV void store_ray(const PathState& ps, uint32_t p, int slot, V3 o, V3 d, float tmax) {
-    size_t i = ray_index(ps, p, slot);
+PB_DEV void store_ray(const PathState& ps, uint32_t j, int slot, V3 o, V3 d, float tmax) {
+    size_t i = ray_index(ps, j, slot);
     ps.ray[i] = make_float4(o.x, o.y, o.z, d.x);
     ps.ray[i + 1] = make_float4(d.y, d.z, tmax, 0.0f);
 }
+
+// Where a shading kernel leaves the transient records it produces for the next launch (estimate_direct_emit writes through
+// one of these). RecordSink: straight into the path state at a known index (k_shade_direct: the path's number).
+struct RecordSink {
+    const PathState& ps;
+    uint32_t rec;
+    PB_DEV void ray(int slot, V3 o, V3 d, float tmax) const { store_ray(ps, rec, slot, o, d, tmax); }
+    PB_DEV void nee_a(float4 v) const { ps.nee_a[rec] = v; }
+    PB_DEV void nee_f(float4 v) const { ps.nee_f[rec] = v; }
+    PB_DEV void nee_b(float4 v) const { ps.nee_b[rec] = v; }
+    PB_DEV void nee_light(int v) const { ps.nee_light[rec] = v; }
+};
+// StagedRecords: k_shade learns a path's output position only after the block-wide count, long after the values were
+// computed; holding the up to 34 of them in registers would push the kernel over its 168-VGPR budget (three waves per
+// SIMD), so they wait in LDS (37 KB per block of 256, three blocks per CU fit), each thread in its own column, and
+// flush() moves them to generation k+1 at the reserved index. Values pass through unchanged.
+struct StagedRecords {
+    float4 ray[3][2][256];
+    float4 nee_a[256], nee_f[256], nee_b[256];
+    int nee_light[256];
+};
+struct StageSink {
+    StagedRecords& st;
+    PB_DEV void ray(int slot, V3 o, V3 d, float tmax) const {
+        st.ray[slot][0][threadIdx.x] = make_float4(o.x, o.y, o.z, d.x);
+        st.ray[slot][1][threadIdx.x] = make_float4(d.y, d.z, tmax, 0.0f);
+    }
+    PB_DEV void nee_a(float4 v) const { st.nee_a[threadIdx.x] = v; }
+    PB_DEV void nee_f(float4 v) const { st.nee_f[threadIdx.x] = v; }
+    PB_DEV void nee_b(float4 v) const { st.nee_b[threadIdx.x] = v; }
+    PB_DEV void nee_light(int v) const { st.nee_light[threadIdx.x] = v; }
+    // the thread's own staged records -> the next generation at record index j (what the path emitted, nothing else:
+    // a specular bounce holds a slot with its continuation ray only)
+    PB_DEV void flush(const PathState& ps, uint32_t j, bool cont, bool mis, bool shadow) const {
+        const uint32_t t = threadIdx.x;
+        if (cont) {
+            size_t i = ray_index(ps, j, RS_CONT);
+            ps.ray_next[i] = st.ray[RS_CONT][0][t];
+            ps.ray_next[i + 1] = st.ray[RS_CONT][1][t];
+        }
+        if (mis) {
+            size_t i = ray_index(ps, j, RS_MIS);
+            ps.ray_next[i] = st.ray[RS_MIS][0][t];
+            ps.ray_next[i + 1] = st.ray[RS_MIS][1][t];
+            ps.nee_f_next[j] = st.nee_f[t];
+        }
+        if (shadow) {
+            size_t i = ray_index(ps, j, RS_SHADOW);
+            ps.ray_next[i] = st.ray[RS_SHADOW][0][t];
+            ps.ray_next[i + 1] = st.ray[RS_SHADOW][1][t];
+        }
+        if (mis || shadow) {
+            ps.nee_a_next[j] = st.nee_a[t];
+            ps.nee_b_next[j] = st.nee_b[t];
+            ps.nee_light_next[j] = st.nee_light[t];
+        }
+    }
+};
 
 // ---- camera: PerspectiveCamera::generate_ray (cameras/perspective.rs:90-112) ----
 struct DevCamera {

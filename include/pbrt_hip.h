@@ -313,6 +313,42 @@ int pbrt_hip_scene_set_environment_map(PbrtHipScene* scene, int32_t light, const
  * why, the scene unchanged) for a material index out of range or of another type, a non-finite or negative roughness, a
  * roughness of 0 with remap == 0, or u != v on plastic. */
 int pbrt_hip_scene_set_material_roughness(PbrtHipScene* scene, int32_t material, float u_roughness, float v_roughness, int32_t remap);
+/* Matte with sigma, glass with roughness and substrate: pbrt-v3's MatteMaterial, GlassMaterial and SubstrateMaterial on the
+ * reference's OrenNayar (reflection.rs:917-975), MicrofacetReflection / MicrofacetTransmission (:977-1192) and FresnelBlend
+ * (:1194-1280), which the eight floats of a PbrtMaterial row have no room for. pbrt_hip_scene_set_material replaces row
+ * `material` of an existing scene's table by the material a descriptor describes (triangles and instances keep naming the row):
+ *   PBRT_MATDESC_MATTE      kd, sigma (degrees, clamped to [0, 90]): no lobe if Kd is black; LambertianReflection(Kd) if
+ *                           sigma == 0 (the PBRT_MAT_MATTE row); else OrenNayar(Kd, sigma), reflection | diffuse;
+ *   PBRT_MATDESC_GLASS      kr, kt, eta, u_roughness, v_roughness: both roughnesses 0 is the PBRT_MAT_GLASS row (Kr, Kt, eta);
+ *                           else MicrofacetReflection(Kr, TR(a_u, a_v), FresnelDielectric(1, eta)) if Kr is not black, then
+ *                           MicrofacetTransmission(Kt, TR(a_u, a_v), 1, eta, Radiance) if Kt is not black, in that order
+ *                           (BSDF::sample_f picks a lobe by index); glossy lobes: neither is specular, so the path integrator
+ *                           takes next-event estimation through them and Whitted shows their direct lighting only;
+ *   PBRT_MATDESC_SUBSTRATE  kd, ks, u_roughness, v_roughness: FresnelBlend(Kd, Ks, TR(a_u, a_v)) unless both are black,
+ *                           reflection | glossy.
+ * a = roughness_to_alpha(roughness) (microfacet.rs:160-169, the roughness clamped at 1e-3, so one zero roughness of two is
+ * usable) when remap_roughness != 0, else a = roughness; u runs along the shading frame's dpdu. A row that an existing
+ * PbrtMaterialType expresses (sigma 0; both roughnesses 0) renders bit for bit what that row given at creation renders. The
+ * fields a type does not name are not read. Departures from the reference to pbrt-v3: OrenNayar takes
+ * sigma in radians and cos(phi_i - phi_o); MicrofacetTransmission::pdf divides by the squared denominator; FresnelBlend is
+ * pbrt-v3's as it stands. Two departures go beyond pbrt-v3, so rough glass is not pbrt-v3's BSDF there: MicrofacetTransmission's
+ * f and pdf are 0 for a zero generalised half vector (eta == 1, wi == -wo; D71) and for a microfacet that wo or wi sees from
+ * behind (pbrt-v4's check; D72: pbrt-v3's pdf gives those mass its sampler never returns). PBRT_HIP_ERR_INVALID (pbrt_hip_last_error says why, the scene unchanged) for a null descriptor, a
+ * material index out of range, an unknown type, a colour, roughness or sigma that is not finite or negative, eta <= 0 on
+ * glass, or a roughness of 0 with remap_roughness == 0 on a row that gets a microfacet lobe. The roughness of such a row is
+ * changed by setting the descriptor again (pbrt_hip_scene_set_material_roughness is for PBRT_MAT_PLASTIC / _METAL rows). */
+enum PbrtMaterialDescType { PBRT_MATDESC_MATTE = 1, PBRT_MATDESC_GLASS = 3, PBRT_MATDESC_SUBSTRATE = 6 };
+typedef struct PbrtMaterialDesc {
+    int32_t type;            /* PbrtMaterialDescType */
+    float kd[3];             /* matte Kd; substrate Kd */
+    float ks[3];             /* substrate Ks */
+    float kr[3], kt[3];      /* glass Kr, Kt */
+    float eta;               /* glass index of refraction (> 0) */
+    float sigma;             /* matte: Oren-Nayar sigma in degrees */
+    float u_roughness, v_roughness;
+    int32_t remap_roughness; /* != 0: TrowbridgeReitzDistribution::roughness_to_alpha, as for plastic / metal */
+} PbrtMaterialDesc;
+int pbrt_hip_scene_set_material(PbrtHipScene* scene, int32_t material, const PbrtMaterialDesc* desc);
 /* BSDF::f, BSDF::pdf and BSDF::sample_f (reflection.rs:264-446) of material `material` of the scene, in batch form, evaluated
  * on the device by the functions the shading kernels inline (any material type). Directions are in the shading frame
  * (ns = ng = +z, dpdu = +x): wo[3 i ..], wi[3 i ..], u[2 i ..] the sample_f sample. Outputs: f[3 i ..] = f(wo, wi),

@@ -1190,6 +1190,78 @@ extern "C" int pbrt_hip_scene_set_material_roughness(PbrtHipScene* s, int32_t ma
 }
 PB_ABI_CATCH
 
+// pbrt-v3's MatteMaterial (sigma), GlassMaterial (roughness) and SubstrateMaterial on the reference's OrenNayar,
+// MicrofacetReflection / MicrofacetTransmission and FresnelBlend (reflection.rs:917-975, 977-1192, 1194-1280): row `material`
+// of the device table and of its host copy is replaced by what the descriptor reduces to. A descriptor an existing
+// PbrtMaterialType expresses becomes that row; the others become a kMatOrenNayar / kMatRoughGlass / kMatSubstrate row
+// (scene.h), which the shading kernels' level-2 instantiations shade (wf_bxdfs.h).
+extern "C" int pbrt_hip_scene_set_material(PbrtHipScene* s, int32_t material, const PbrtMaterialDesc* desc) try {
+    if (!s) return PBRT_HIP_ERR_INVALID;
+    PbrtHipContext* ctx = s->ctx;
+    PB_ENTER(ctx);
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = "pbrt_hip_scene_set_material: " + why;
+        return PBRT_HIP_ERR_INVALID;
+    };
+    if (!desc) return invalid("null desc");
+    if (material < 0 || material >= (int32_t)s->h_materials.size()) return invalid("material index out of range");
+    const PbrtMaterialDesc& d = *desc;
+    if (d.type != PBRT_MATDESC_MATTE && d.type != PBRT_MATDESC_GLASS && d.type != PBRT_MATDESC_SUBSTRATE)
+        return invalid("unknown material descriptor type");
+    auto bad_colour = [](const float* c) {
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(c[k]) || c[k] < 0.0f) return true;
+        return false;
+    };
+    auto black = [](const float* c) { return c[0] == 0.0f && c[1] == 0.0f && c[2] == 0.0f; };
+    DevMaterial m{};
+    if (d.type == PBRT_MATDESC_MATTE) {
+        if (bad_colour(d.kd)) return invalid("Kd must be finite and >= 0");
+        if (!std::isfinite(d.sigma) || d.sigma < 0.0f) return invalid("sigma must be finite and >= 0");
+        std::memcpy(m.kd, d.kd, 12);
+        const double sigma = std::min((double)d.sigma, 90.0) * (3.14159265358979323846 / 180.0);  // MatteMaterial's clamp, then radians
+        if (sigma == 0.0) {
+            m.type = PBRT_MAT_MATTE;
+            m.eta = 1.0f;
+        } else {  // OrenNayar::new (reflection.rs:925-936), in double, rounded once
+            const double sigma2 = sigma * sigma;
+            m.type = kMatOrenNayar;
+            m.alpha_u = (float)(1.0 - sigma2 / (2.0 * (sigma2 + 0.33)));
+            m.alpha_v = (float)(0.45 * sigma2 / (sigma2 + 0.09));
+        }
+    } else {
+        const bool glass = d.type == PBRT_MATDESC_GLASS;
+        const float* c0 = glass ? d.kr : d.kd;
+        const float* c1 = glass ? d.kt : d.ks;
+        if (bad_colour(c0)) return invalid(glass ? "Kr must be finite and >= 0" : "Kd must be finite and >= 0");
+        if (bad_colour(c1)) return invalid(glass ? "Kt must be finite and >= 0" : "Ks must be finite and >= 0");
+        if (glass && !(std::isfinite(d.eta) && d.eta > 0.0f)) return invalid("glass needs a finite eta > 0");
+        const bool remap = d.remap_roughness != 0;
+        if (const char* why = roughness_invalid(d.u_roughness, d.v_roughness, true)) return invalid(why);
+        std::memcpy(m.kd, c0, 12);
+        std::memcpy(m.kt, c1, 12);
+        m.eta = glass ? d.eta : 1.0f;
+        if (glass && d.u_roughness == 0.0f && d.v_roughness == 0.0f) {
+            m.type = PBRT_MAT_GLASS;  // GlassMaterial's isSpecular: FresnelSpecular / the specular lobes
+        } else {
+            // alpha 0 is refused only where a microfacet lobe would carry it
+            if (!(black(c0) && black(c1)))
+                if (const char* why = roughness_invalid(d.u_roughness, d.v_roughness, remap)) return invalid(why);
+            m.type = glass ? kMatRoughGlass : kMatSubstrate;
+            m.alpha_u = remap ? roughness_to_alpha(d.u_roughness) : d.u_roughness;
+            m.alpha_v = remap ? roughness_to_alpha(d.v_roughness) : d.v_roughness;
+        }
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy((void*)(s->d.materials + material), &m, sizeof(DevMaterial), hipMemcpyHostToDevice));
+    s->h_materials[material] = m;
+    s->bxdfs = false;
+    for (const DevMaterial& row : s->h_materials) s->bxdfs = s->bxdfs || row.type >= kMatOrenNayar;
+    return PBRT_HIP_OK;
+}
+PB_ABI_CATCH
+
 // InfiniteAreaLight::new(light_to_world, L, n_samples, texmap) (lights/infinite.rs:36-82) with the texels in memory: the map's
 // tables (host_envmap.cpp) go to the device for light `light`, its power and the power distribution are recomputed, and a
 // spatial light table already built is dropped (the next render with that strategy builds it again).

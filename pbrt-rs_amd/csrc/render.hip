@@ -183,13 +183,13 @@ __global__ void k_bsdf_query(const DevMaterial* __restrict__ materials, int mate
     V3 f = V3{0.0f, 0.0f, 0.0f}, wi_s = f, f_s = f;
     float pdf = 0.0f, pdf_s = 0.0f;
     int sampled = 0;
-    const NsBsdf nsb = ns_bsdf(mat);
+    const GenBsdf nsb = gen_bsdf(mat);
     if (nsb.n > 0) {
-        ns_f_pdf(nsb, fr, wo, wi, &f, &pdf);
+        gen_f_pdf(nsb, fr, wo, wi, &f, &pdf);
         bool ok;
         float ps = 0.0f;
         V3 w;
-        V3 fs = ns_sample_f(nsb, fr, wo, u0, u1, &w, &ps, &ok, &sampled);
+        V3 fs = gen_sample_f(nsb, fr, wo, u0, u1, &w, &ps, &ok, &sampled);
         if (ok) {
             wi_s = w;
             f_s = fs;
@@ -1095,17 +1095,22 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
             if (direct)
 {
                 dim3 sg((n_shade + 255) / 256), sb(256);
-                // a plastic or metal material in the scene's table selects the glossy instantiations (AO reads no BSDF)
-                if (rp.integrator == PBRT_INTEGRATOR_DIRECT && s->glossy)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, true>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                // a plastic or metal material in the scene's table selects the level-1 instantiations, a row of
+                // pbrt_hip_scene_set_material the level-2 ones (AO reads no BSDF)
+                if (rp.integrator == PBRT_INTEGRATOR_DIRECT && s->bxdfs)
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, 2>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                else if (rp.integrator == PBRT_INTEGRATOR_DIRECT && s->glossy)
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, 1>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
                 else if (rp.integrator == PBRT_INTEGRATOR_DIRECT)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, false>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, 0>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                else if (rp.integrator == PBRT_INTEGRATOR_WHITTED && s->bxdfs)
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, 2>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
                 else if (rp.integrator == PBRT_INTEGRATOR_WHITTED && s->glossy)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, true>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, 1>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
                 else if (rp.integrator == PBRT_INTEGRATOR_WHITTED)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, false>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, 0>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
                 else
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_AO, false>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_AO, 0>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
             }
             else {
                 const Queues qin = q[cur];
@@ -1114,7 +1119,7 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
                     hipLaunchKernelGGL(k_shade_sort_keys, dim3((n_shade + 255) / 256), dim3(256), 0, st, sc, ps, q[cur].shade, n_shade,
                                        pp.max_depth, shade_keys[0], shade_positions);
                     size_t tb = shade_tmp_bytes;
-                    if (pb::sort_pairs_u32(st, shade_tmp, &tb, shade_keys[0], shade_keys[1], shade_positions, shade_sorted, n_shade, 3) != 0 &&
+                    if (pb::sort_pairs_u32(st, shade_tmp, &tb, shade_keys[0], shade_keys[1], shade_positions, shade_sorted, n_shade, s->bxdfs ? 4 : 3) != 0 &&
                         rc == PBRT_HIP_OK) {
                         ctx->last_error = "rocPRIM radix sort failed";
                         rc = PBRT_HIP_ERR_DEVICE;
@@ -1122,14 +1127,18 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
                     order = shade_sorted;
                 }
                 const dim3 sg((n_shade + 255) / 256), sb(256);
-                if (bin_shade && wavefront >= 1 && s->glossy)
-                    hipLaunchKernelGGL((k_shade<true, true>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
+                if (bin_shade && wavefront >= 1 && s->bxdfs)
+                    hipLaunchKernelGGL((k_shade<true, 2>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
+                else if (bin_shade && wavefront >= 1 && s->glossy)
+                    hipLaunchKernelGGL((k_shade<true, 1>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
                 else if (bin_shade && wavefront >= 1)
-                    hipLaunchKernelGGL((k_shade<true, false>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
+                    hipLaunchKernelGGL((k_shade<true, 0>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
+                else if (s->bxdfs)
+                    hipLaunchKernelGGL((k_shade<false, 2>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
                 else if (s->glossy)
-                    hipLaunchKernelGGL((k_shade<false, true>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
+                    hipLaunchKernelGGL((k_shade<false, 1>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
                 else
-                    hipLaunchKernelGGL((k_shade<false, false>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
+                    hipLaunchKernelGGL((k_shade<false, 0>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
                 // what this launch wrote is the generation the next trace and shade launches read
                 std::swap(ps.ray, ps.ray_next);
                 std::swap(ps.nee_a, ps.nee_a_next);

@@ -101,6 +101,9 @@ struct DevMaterial {
     float eta;
     float alpha_u, alpha_v;  // plastic / metal: TrowbridgeReitzDistribution's alphas, computed on the host
 };
+// DevMaterial::type past PbrtMaterialType: the rows pbrt_hip_scene_set_material writes (wf_bxdfs.h). kMatOrenNayar: kd,
+// OrenNayar's A / B in alpha_u / alpha_v; kMatRoughGlass: kd = Kr, kt = Kt, eta, the alphas; kMatSubstrate: kd, kt = Ks, the alphas
+constexpr int kMatOrenNayar = 6, kMatRoughGlass = 7, kMatSubstrate = 8;
 
 // Distribution1D (src/core/sampling.rs:62-154) flattened: func[n], cdf[n+1]
 struct DevDistribution1D {
@@ -152,6 +155,7 @@ struct PbrtHipScene {
     std::vector<pb::DevLight> h_lights;
     std::vector<pb::DevMaterial> h_materials;  // the device table's host copy (pbrt_hip_scene_set_material_roughness)
     bool glossy = false;  // a plastic or metal material in the table: the shading kernels' glossy instantiations run
+    bool bxdfs = false;   // a kMatOrenNayar / kMatRoughGlass / kMatSubstrate row in the table: their level-2 instantiations run
     std::vector<int> light_samples;  // max(1, n_samples) per light (light.rs:76)
     // image maps of infinite lights (pbrt_hip_scene_set_environment_map): per light its descriptor and its device arrays
     std::vector<pb::DevEnvMap> h_env;

@@ -26,15 +26,17 @@ struct DirectState {
 #define PB_DIRECT_WAVES 2  // 128 VGPRs: +5..9 % on direct lighting / Whitted / AO over the unconstrained 256-VGPR build
 #endif
 // MODE: PBRT_INTEGRATOR_DIRECT / _WHITTED / _AO: one instantiation each, the other integrators' stages compile away.
-// GLOSSY: the scene holds plastic or metal: the non-specular BSDF is the general one of wf_microfacet.h (matte included).
-// The glossy direct-lighting instantiation runs one wave per SIMD: at two it spills 19 registers.
-template <int MODE, bool GLOSSY>
-__global__ void __launch_bounds__(256, (GLOSSY && MODE == PBRT_INTEGRATOR_DIRECT) ? 1 : PB_DIRECT_WAVES) k_shade_direct(ShadeConsts sc, PathState ps, DirectState ds, Queues qin,
+// LEVEL as k_shade's: 1 (GLOSSY), the scene holds plastic or metal: the non-specular BSDF is the general one of
+// wf_microfacet.h (matte included); 2, a row of pbrt_hip_scene_set_material: that of wf_bxdfs.h.
+// The glossy direct-lighting instantiations run one wave per SIMD: at two level 1 spills 19 registers.
+template <int MODE, int LEVEL>
+__global__ void __launch_bounds__(256, (LEVEL >= 1 && MODE == PBRT_INTEGRATOR_DIRECT) ? 1 : PB_DIRECT_WAVES) k_shade_direct(ShadeConsts sc, PathState ps, DirectState ds, Queues qin,
                                                         Queues qout, PassParams pp, TileList tiles, uint32_t n_in) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool active = i < n_in;
     uint32_t p = active ? qin.shade[i] : 0u;
     bool emit_cont = false, emit_mis = false, emit_shadow = false, mis_bool = false;
+    constexpr bool GLOSSY = LEVEL >= 1;
     if (active && !(__float_as_int(ps.beta[p].w) & PF_VALID)) active = false;  // placeholder path outside pixel_bounds
 
     if (active) {
@@ -207,8 +209,9 @@ __global__ void __launch_bounds__(256, (GLOSSY && MODE == PBRT_INTEGRATOR_DIRECT
                 V3 f = V3{0.0f, 0.0f, 0.0f};
                 float spdf;
                 if (GLOSSY) {
-                    NsBsdf nsb = ns_bsdf(sc.materials[sf.material]);  // read again here: keeps the alphas out of the loop's registers
-                    if (nsb.n > 0) ns_f_pdf(nsb, fr, sf.wo, wi, &f, &spdf);  // BSDF::f, all lobes
+                    typename LevelBsdf<LEVEL>::type nsb;
+                    load_bsdf(sc.materials[sf.material], &nsb);  // read again here: keeps the alphas out of the loop's registers
+                    if (nsb.n > 0) bsdf_f_pdf(nsb, fr, sf.wo, wi, &f, &spdf);  // BSDF::f, all lobes
                 } else if (mat.type == PBRT_MAT_MATTE && !is_black(kd)) {
                     matte_f_pdf(fr, kd, sf.wo, wi, &f, &spdf);  // BSDF::f, all lobes
                 }
@@ -250,7 +253,8 @@ __global__ void __launch_bounds__(256, (GLOSSY && MODE == PBRT_INTEGRATOR_DIRECT
                 }
                 int nee_flags;
                 if (GLOSSY) {
-                    NsBsdf nsb = ns_bsdf(sc.materials[sf.material]);
+                    typename LevelBsdf<LEVEL>::type nsb;
+                    load_bsdf(sc.materials[sf.material], &nsb);
                     nee_flags = estimate_direct_emit(sc, RecordSink{ps, p}, sf, fr, nsb.n > 0, nsb, light_num, ul0, ul1, us0, us1, pick_pdf, T);
                 } else {
                     bool matte = (mat.type == PBRT_MAT_MATTE) && !is_black(kd);

@@ -41,9 +41,9 @@ __global__ void k_shade_sort_keys(ShadeConsts sc, PathState ps, const uint32_t* 
     positions[i] = i;
 }
 
-// keys: 0 nothing to shade, 1 + PBRT_MAT_* (none, matte, mirror, glass; the glossy instantiations: plastic, metal as well),
-// the last = no queue entry (block tail)
-constexpr int shade_keys(bool glossy) { return glossy ? 8 : 6; }
+// keys: 0 nothing to shade, 1 + DevMaterial::type (none, matte, mirror, glass; level 1: plastic, metal as well; level 2: the
+// three kinds of set_material rows as well), the last = no queue entry (block tail)
+constexpr int shade_keys(int level) { return level == 2 ? 11 : level == 1 ? 8 : 6; }
 template <int KEYS>
 struct ShadeBins {
     uint32_t count[4][KEYS];  // per wave of the block, per key
@@ -54,15 +54,19 @@ struct ShadeBins {
 #ifndef PB_SHADE_WAVES
 #define PB_SHADE_WAVES 3  // 162 VGPRs; 4 waves (128 VGPRs, spills) measured in profiles/r04_wide_kernel_ladder.txt
 #endif
-// GLOSSY: the scene's material table holds plastic or metal (MicrofacetReflection lobes, wf_microfacet.h); matte then goes
-// through the same general BSDF (bit for bit the Lambertian code), and the instantiations without it stay as they were.
+// LEVEL: which non-specular BSDFs the scene's material table needs. 0: matte only. 1 (GLOSSY): plastic or metal as well
+// (MicrofacetReflection lobes, wf_microfacet.h); matte then goes through the same general BSDF (bit for bit the Lambertian
+// code), and the instantiations without it stay as they were. 2: a row of pbrt_hip_scene_set_material as well (OrenNayar,
+// glossy transmission, FresnelBlend: GenBsdf, wf_bxdfs.h), the rows of level 1 through the functions of level 1. Level 2
+// fits the same launch bounds without scratch: 162 / 164 VGPRs (profiles/r08_bxdf_set.txt).
 // Thread i takes the shade-queue entry at position rec = i (order: rec = order[i], the queue in material order): the path
 // p = qin.shade[rec] with its persistent state at p, and the transient records of this generation at rec. What the path
 // hands to the next launch is staged in LDS and written to the next generation at its position in qout.shade.
-template <bool BIN, bool GLOSSY>
+template <bool BIN, int LEVEL>
 __global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
                                                  TileList tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
-    constexpr int kShadeKeys = shade_keys(GLOSSY);
+    constexpr bool GLOSSY = LEVEL >= 1;
+    constexpr int kShadeKeys = shade_keys(LEVEL);
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool active = i < n_in;
     uint32_t rec = (active && order) ? order[i] : i;
@@ -157,11 +161,11 @@ __global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, P
                     V3 kd = V3{mat.kd[0], mat.kd[1], mat.kd[2]};
                     V3 kt = V3{mat.kt[0], mat.kt[1], mat.kt[2]};
                     V3 wo = -rd;  // path.rs:122 `let wo = -ray.d` (estimate_direct uses isect.wo = sf.wo)
-                    bool has_lobe;  // which BxDFs the material adds: pbrt-v3 rules (matte / mirror / glass / plastic / metal)
+                    bool has_lobe;  // which BxDFs the material adds: pbrt-v3 rules (matte / mirror / glass / plastic / metal; level 2: Oren-Nayar / rough glass / substrate rows)
                     bool nonspecular;
-                    NsBsdf nsb;
+                    typename LevelBsdf<LEVEL>::type nsb;
                     if (GLOSSY) {
-                        nsb = ns_bsdf(mat);
+                        load_bsdf(mat, &nsb);
                         nonspecular = nsb.n > 0;
                         if (mat.type == PBRT_MAT_GLASS) has_lobe = !(is_black(kd) && is_black(kt));
                         else if (mat.type == PBRT_MAT_MIRROR) has_lobe = !is_black(kd);
@@ -201,7 +205,7 @@ __global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, P
                     float pdf = 0.0f;
                     bool sampled_specular = false, sampled_transmission = false;
                     if (has_lobe) {
-                        if (GLOSSY && nonspecular) {  // glossy lobes: not specular, PF_SPECULAR_BOUNCE stays clear
+                        if (GLOSSY && nonspecular) {  // glossy lobes, transmission included: not specular, PF_SPECULAR_BOUNCE stays clear
                             bool ok;
                             f = bsdf_sample_f(nsb, fr, wo, u0, u1, &wi, &pdf, &ok);
                             if (!ok) pdf = 0.0f;

@@ -40,6 +40,7 @@ EXPORTS = [
     "pbrt_hip_comm_last_error", "pbrt_hip_scene_wide_records", "pbrt_hip_get_wide_counters", "pbrt_hip_probe_gather", "pbrt_hip_probe_state_stream",
     "pbrt_hip_li", "pbrt_hip_li_device", "pbrt_hip_camera_rays", "pbrt_hip_scene_create_two_level", "pbrt_hip_debug_wide_export",
     "pbrt_hip_scene_set_environment_map", "pbrt_hip_envmap_tables", "pbrt_hip_scene_set_material_roughness", "pbrt_hip_bsdf_query",
+    "pbrt_hip_scene_set_material",
 ]
 MAT_NONE, MAT_MATTE, MAT_MIRROR, MAT_GLASS, MAT_PLASTIC, MAT_METAL = (scenes.MAT_NONE, scenes.MAT_MATTE, scenes.MAT_MIRROR,
                                                                       scenes.MAT_GLASS, scenes.MAT_PLASTIC, scenes.MAT_METAL)
@@ -73,6 +74,13 @@ class RenderStats(ctypes.Structure):
     _fields_ = [("camera_samples", ctypes.c_uint64), ("rays_closest", ctypes.c_uint64),
                 ("rays_shadow", ctypes.c_uint64), ("trace_launches", ctypes.c_uint64),
                 ("trace_ms", ctypes.c_double), ("total_ms", ctypes.c_double)]
+
+
+class MaterialDesc(ctypes.Structure):
+    """PbrtMaterialDesc (pbrt_hip_scene_set_material); scenes.matte_sigma / rough_glass / substrate give the keyword form"""
+    _fields_ = [("type", ctypes.c_int32), ("kd", ctypes.c_float * 3), ("ks", ctypes.c_float * 3), ("kr", ctypes.c_float * 3),
+                ("kt", ctypes.c_float * 3), ("eta", ctypes.c_float), ("sigma", ctypes.c_float), ("u_roughness", ctypes.c_float),
+                ("v_roughness", ctypes.c_float), ("remap_roughness", ctypes.c_int32)]
 
 
 class PbrtHipError(RuntimeError):
@@ -165,6 +173,7 @@ def lib():
                                              ctypes.POINTER(ctypes.c_char_p)]
         L.pbrt_hip_scene_set_material_roughness.argtypes = [vp, i32, ctypes.c_float, ctypes.c_float, i32]
         L.pbrt_hip_bsdf_query.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.pbrt_hip_scene_set_material.argtypes = [vp, i32, vp]
         L.pbrt_hip_film_to_rgb.restype = None
         _lib = L
     return _lib
@@ -380,7 +389,17 @@ class Scene:
 
     def __init__(self, ctx, scene, max_prims_in_node=4, split_method=SPLIT_SAH, bvh=None, device_build=False):
         """device_build=True: BVHAccel::new(HLBVH) built and laid out on the GPU (pbrt_hip_scene_create_hlbvh);
-        self.build_ms / self.layout_ms then hold the HIP-event times and self.nodes is None."""
+        self.build_ms / self.layout_ms then hold the HIP-event times and self.nodes is None.
+        scene["material_descs"] = {row: descriptor} (optional): set_material(row, descriptor) after creation."""
+        self._create(ctx, scene, max_prims_in_node, split_method, bvh, device_build)
+        try:
+            for row, desc in (scene.get("material_descs") or {}).items():
+                self.set_material(row, desc)
+        except Exception:
+            self.close()  # a refused descriptor: the scene that was just created does not outlive the constructor
+            raise
+
+    def _create(self, ctx, scene, max_prims_in_node, split_method, bvh, device_build):
         self.ctx = ctx
         if "objects" in scene:
             self._init_two_level(scene, max_prims_in_node, split_method, bvh)
@@ -646,6 +665,17 @@ class Scene:
         v = u if v is None else v
         self.ctx.check(lib().pbrt_hip_scene_set_material_roughness(self.h, int(m), float(u), float(v), int(bool(remap))),
                        "pbrt_hip_scene_set_material_roughness")
+
+    def set_material(self, m, desc):
+        """Replaces row m of the material table by a descriptor: scenes.matte_sigma(), scenes.rough_glass() or
+        scenes.substrate() (a dict of PbrtMaterialDesc's fields), or a MaterialDesc (pbrt_hip_scene_set_material)."""
+        if desc is not None and not isinstance(desc, MaterialDesc):
+            d = MaterialDesc()
+            for k, v in desc.items():
+                setattr(d, k, (ctypes.c_float * 3)(*[float(c) for c in v]) if k in ("kd", "ks", "kr", "kt") else v)
+            desc = d
+        self.ctx.check(lib().pbrt_hip_scene_set_material(self.h, int(m), None if desc is None else ctypes.byref(desc)),
+                       "pbrt_hip_scene_set_material")
 
     def bsdf_query(self, material, wo, wi, u):
         """BSDF::f / pdf / sample_f of a material on the device, in the shading frame (n = +z): wo, wi (n, 3), u (n, 2).

@@ -81,6 +81,30 @@ def metal(eta, k, roughness=0.01):
     return (MAT_METAL, eta, k, roughness)
 
 
+MATDESC_MATTE, MATDESC_GLASS, MATDESC_SUBSTRATE = 1, 3, 6  # PbrtMaterialDescType
+
+
+def matte_sigma(kd, sigma):
+    """Descriptor (Scene.set_material, scene["material_descs"]) of pbrt-v3's MatteMaterial: OrenNayar(Kd, sigma), sigma in
+    degrees (clamped to [0, 90]); sigma 0 is the Lambertian matte row."""
+    return dict(type=MATDESC_MATTE, kd=tuple(kd), sigma=float(sigma))
+
+
+def rough_glass(kr, kt, eta, u_roughness, v_roughness=None, remap=True):
+    """Descriptor of pbrt-v3's GlassMaterial: Trowbridge-Reitz reflection (FresnelDielectric(1, eta)) and transmission lobes;
+    both roughnesses 0 is the specular glass row. v_roughness None: isotropic."""
+    v_roughness = u_roughness if v_roughness is None else v_roughness
+    return dict(type=MATDESC_GLASS, kr=tuple(kr), kt=tuple(kt), eta=float(eta), u_roughness=float(u_roughness),
+                v_roughness=float(v_roughness), remap_roughness=int(bool(remap)))
+
+
+def substrate(kd, ks, u_roughness, v_roughness=None, remap=True):
+    """Descriptor of pbrt-v3's SubstrateMaterial: FresnelBlend(Kd, Ks) over Trowbridge-Reitz. v_roughness None: isotropic."""
+    v_roughness = u_roughness if v_roughness is None else v_roughness
+    return dict(type=MATDESC_SUBSTRATE, kd=tuple(kd), ks=tuple(ks), u_roughness=float(u_roughness), v_roughness=float(v_roughness),
+                remap_roughness=int(bool(remap)))
+
+
 def _lights(rows):
     """rows: (type, L, prim, two_sided, n_samples) tuples or ready LIGHT_DTYPE records (point_light() ...)."""
     l = np.zeros(len(rows), dtype=LIGHT_DTYPE)

@@ -349,6 +349,36 @@ typedef struct PbrtMaterialDesc {
     int32_t remap_roughness; /* != 0: TrowbridgeReitzDistribution::roughness_to_alpha, as for plastic / metal */
 } PbrtMaterialDesc;
 int pbrt_hip_scene_set_material(PbrtHipScene* scene, int32_t material, const PbrtMaterialDesc* desc);
+/* pbrt-v3's DisneyMaterial (the Disney "principled" BSDF) without subsurface scattering: pbrt_hip_scene_set_disney_material
+ * replaces row `material` of an existing scene's table (triangles and instance overrides keep naming the row); setting the row
+ * again, with this call or with pbrt_hip_scene_set_material, replaces it. Every parameter is a constant of the row. The lobes,
+ * in this order (BSDF::sample_f picks one by index; DESIGN.md "Disney" writes every formula out), with
+ * dw = (1 - metallic)(1 - spec_trans) and dt = diff_trans / 2:
+ *   dw > 0, not thin   DisneyDiffuse(dw color), DisneyRetro(dw color, roughness)
+ *   dw > 0, thin       DisneyDiffuse(dw (1 - flatness)(1 - dt) color), DisneyFakeSS(dw flatness (1 - dt) color, roughness),
+ *                      DisneyRetro(dw color, roughness)
+ *   dw > 0, sheen > 0  DisneySheen(dw sheen lerp(sheen_tint, 1, color / luminance))
+ *   always             MicrofacetReflection(1, Trowbridge-Reitz(ax, ay) with G = G1(wo) G1(wi), DisneyFresnel(metallic, eta,
+ *                      Cspec0)), ax = max(1e-3, roughness^2 / aspect), ay = max(1e-3, roughness^2 aspect),
+ *                      aspect = sqrt(1 - 0.9 anisotropic)
+ *   clearcoat > 0      DisneyClearcoat(clearcoat, lerp(clearcoat_gloss, 0.1, 0.001)): GTR1, reflection | glossy
+ *   spec_trans > 0     MicrofacetTransmission(spec_trans sqrt(color), 1, eta, Radiance) over the same distribution; thin: over
+ *                      Trowbridge-Reitz (its own G) with the roughness scaled by 0.65 eta - 0.35
+ *   thin               LambertianTransmission(dt color)
+ * No lobe is specular: the path integrator estimates direct lighting at every Disney hit, never sets the specular-bounce flag
+ * there and leaves eta_scale alone; Whitted shows the surface's direct lighting only. Subsurface scattering (scatter_distance,
+ * the BSSRDF) is not offered (DESIGN.md D73-D78 for this and the other choices). PBRT_HIP_ERR_INVALID (pbrt_hip_last_error says
+ * why, the scene unchanged) for a null descriptor, a row out of range, a value that is not finite or negative, eta <= 0,
+ * diff_trans > 2, or metallic, roughness, specular_tint, anisotropic, sheen_tint, clearcoat_gloss, spec_trans or flatness
+ * above 1; sheen and clearcoat only have to be >= 0. pbrt-v3's defaults: metallic 0, eta 1.5, roughness 0.5, specular_tint 0,
+ * anisotropic 0, sheen 0, sheen_tint 0.5, clearcoat 0, clearcoat_gloss 1, spec_trans 0, flatness 0, diff_trans 1, thin 0. */
+typedef struct PbrtDisneyDesc {
+    float color[3];
+    float metallic, eta, roughness, specular_tint, anisotropic, sheen, sheen_tint,
+          clearcoat, clearcoat_gloss, spec_trans, flatness, diff_trans;
+    int32_t thin;
+} PbrtDisneyDesc;
+int pbrt_hip_scene_set_disney_material(PbrtHipScene* scene, int32_t material, const PbrtDisneyDesc* desc);
 /* BSDF::f, BSDF::pdf and BSDF::sample_f (reflection.rs:264-446) of material `material` of the scene, in batch form, evaluated
  * on the device by the functions the shading kernels inline (any material type). Directions are in the shading frame
  * (ns = ng = +z, dpdu = +x): wo[3 i ..], wi[3 i ..], u[2 i ..] the sample_f sample. Outputs: f[3 i ..] = f(wo, wi),

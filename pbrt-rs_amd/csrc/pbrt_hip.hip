@@ -1064,6 +1064,10 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
         d.slot_prim = dev_upload(s, local.data(), local.size(), &ok);
     }
     d.materials = dev_upload(s, dm.data(), dm.size(), &ok);
+    {
+        std::vector<DevDisney> dz(n_materials, DevDisney{});  // pbrt_hip_scene_set_disney_material fills a row's block
+        d.disney = dev_upload(s, dz.data(), dz.size(), &ok);
+    }
     d.lights = dev_upload(s, dl.data(), dl.size(), &ok);
     d.n_lights = n_lights;
     d.n_materials = n_materials;
@@ -1190,6 +1194,15 @@ extern "C" int pbrt_hip_scene_set_material_roughness(PbrtHipScene* s, int32_t ma
 }
 PB_ABI_CATCH
 
+// which shading-kernel level the table needs beyond plastic / metal, after a row was replaced
+static void refresh_material_levels(PbrtHipScene* s) {
+    s->bxdfs = s->disney = false;
+    for (const DevMaterial& row : s->h_materials) {
+        s->bxdfs = s->bxdfs || (row.type >= kMatOrenNayar && row.type <= kMatSubstrate);
+        s->disney = s->disney || row.type == kMatDisney;
+    }
+}
+
 // pbrt-v3's MatteMaterial (sigma), GlassMaterial (roughness) and SubstrateMaterial on the reference's OrenNayar,
 // MicrofacetReflection / MicrofacetTransmission and FresnelBlend (reflection.rs:917-975, 977-1192, 1194-1280): row `material`
 // of the device table and of its host copy is replaced by what the descriptor reduces to. A descriptor an existing
@@ -1256,8 +1269,95 @@ extern "C" int pbrt_hip_scene_set_material(PbrtHipScene* s, int32_t material, co
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy((void*)(s->d.materials + material), &m, sizeof(DevMaterial), hipMemcpyHostToDevice));
     s->h_materials[material] = m;
-    s->bxdfs = false;
-    for (const DevMaterial& row : s->h_materials) s->bxdfs = s->bxdfs || row.type >= kMatOrenNayar;
+    refresh_material_levels(s);
+    return PBRT_HIP_OK;
+}
+PB_ABI_CATCH
+
+// pbrt-v3's DisneyMaterial without subsurface (include/pbrt_hip.h): row `material` becomes a kMatDisney row
+// and its DevDisney block (scene.h) gets the lobes' constants, computed here in double and rounded once. The shading kernels'
+// level-3 instantiations shade it (wf_disney.h).
+extern "C" int pbrt_hip_scene_set_disney_material(PbrtHipScene* s, int32_t material, const PbrtDisneyDesc* desc) try {
+    if (!s) return PBRT_HIP_ERR_INVALID;
+    PbrtHipContext* ctx = s->ctx;
+    PB_ENTER(ctx);
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = "pbrt_hip_scene_set_disney_material: " + why;
+        return PBRT_HIP_ERR_INVALID;
+    };
+    if (!desc) return invalid("null desc");
+    if (material < 0 || material >= (int32_t)s->h_materials.size()) return invalid("material index out of range");
+    const PbrtDisneyDesc& p = *desc;
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(p.color[k]) || p.color[k] < 0.0f) return invalid("color must be finite and >= 0");
+    const struct {
+        const char* name;
+        float v, max;
+    } scalars[] = {{"metallic", p.metallic, 1.0f}, {"eta", p.eta, INFINITY}, {"roughness", p.roughness, 1.0f},
+                   {"specular_tint", p.specular_tint, 1.0f}, {"anisotropic", p.anisotropic, 1.0f}, {"sheen", p.sheen, INFINITY},
+                   {"sheen_tint", p.sheen_tint, 1.0f}, {"clearcoat", p.clearcoat, INFINITY}, {"clearcoat_gloss", p.clearcoat_gloss, 1.0f},
+                   {"spec_trans", p.spec_trans, 1.0f}, {"flatness", p.flatness, 1.0f}, {"diff_trans", p.diff_trans, 2.0f}};
+    for (const auto& sv : scalars) {
+        if (!std::isfinite(sv.v) || sv.v < 0.0f) return invalid(std::string(sv.name) + " must be finite and >= 0");
+        if (sv.v > sv.max) return invalid(std::string(sv.name) + (sv.max == 2.0f ? " must be <= 2" : " must be <= 1"));
+    }
+    if (!(p.eta > 0.0f)) return invalid("eta must be > 0");
+
+    const bool thin = p.thin != 0;
+    const double c[3] = {p.color[0], p.color[1], p.color[2]};
+    const double lum = 0.212671 * c[0] + 0.715160 * c[1] + 0.072169 * c[2];
+    const double metallic = p.metallic, eta = p.eta, rough = p.roughness, strans = p.spec_trans, flat = p.flatness;
+    const double dw = (1.0 - metallic) * (1.0 - strans), dt = p.diff_trans / 2.0;
+    const double aspect = std::sqrt(1.0 - 0.9 * p.anisotropic);
+    const double r0 = ((eta - 1.0) / (eta + 1.0)) * ((eta - 1.0) / (eta + 1.0));
+    auto lerp = [](double t, double a, double b) { return (1.0 - t) * a + t * b; };
+    DevDisney z{};
+    z.metallic = p.metallic;
+    z.eta = p.eta;
+    z.roughness = p.roughness;
+    z.ax = (float)std::max(1e-3, rough * rough / aspect);
+    z.ay = (float)std::max(1e-3, rough * rough * aspect);
+    z.tax = z.ax;
+    z.tay = z.ay;
+    z.sep_trans = thin ? 0 : 1;
+    z.lobes = kDzMicro;
+    if (dw > 0.0) z.lobes |= kDzDiffuse | kDzRetro | (thin ? kDzFakeSS : 0) | (p.sheen > 0.0f ? kDzSheen : 0);
+    if (p.clearcoat > 0.0f) z.lobes |= kDzClearcoat;
+    if (p.spec_trans > 0.0f) z.lobes |= kDzTrans;
+    if (thin) z.lobes |= kDzLambertT;
+    for (int k = 0; k < 3; ++k) {
+        const double tint = lum > 0.0 ? c[k] / lum : 1.0;
+        z.cspec0[k] = (float)lerp(metallic, r0 * lerp(p.specular_tint, 1.0, tint), c[k]);
+        if (z.lobes & kDzDiffuse) z.diffuse[k] = (float)(thin ? dw * (1.0 - flat) * (1.0 - dt) * c[k] : dw * c[k]);
+        if (z.lobes & kDzFakeSS) z.fakess[k] = (float)(dw * flat * (1.0 - dt) * c[k]);
+        if (z.lobes & kDzRetro) z.retro[k] = (float)(dw * c[k]);
+        if (z.lobes & kDzSheen) z.sheen[k] = (float)(dw * p.sheen * lerp(p.sheen_tint, 1.0, tint));
+        if (z.lobes & kDzTrans) z.trans[k] = (float)(strans * std::sqrt(c[k]));
+        if (z.lobes & kDzLambertT) z.lambert_t[k] = (float)(dt * c[k]);
+    }
+    {
+        const double g = lerp(p.clearcoat_gloss, 0.1, 0.001), a2 = g * g;
+        z.clearcoat = p.clearcoat;
+        z.cc_a2 = (float)a2;
+        z.cc_ln_a2 = (float)std::log(a2);
+        z.cc_norm = (float)((a2 - 1.0) / (3.14159265358979323846 * std::log(a2)));
+    }
+    if ((z.lobes & kDzTrans) && thin) {
+        const double rs = (0.65 * eta - 0.35) * rough;
+        z.tax = (float)std::max(1e-3, rs * rs / aspect);
+        z.tay = (float)std::max(1e-3, rs * rs * aspect);
+    }
+    z.n = __builtin_popcount((unsigned)z.lobes);
+    DevMaterial m{};
+    m.type = kMatDisney;
+    std::memcpy(m.kd, p.color, 12);
+    m.eta = p.eta;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy((void*)(s->d.disney + material), &z, sizeof(DevDisney), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy((void*)(s->d.materials + material), &m, sizeof(DevMaterial), hipMemcpyHostToDevice));
+    s->h_materials[material] = m;
+    refresh_material_levels(s);
     return PBRT_HIP_OK;
 }
 PB_ABI_CATCH

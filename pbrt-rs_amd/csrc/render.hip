@@ -229,6 +229,48 @@ __global__ void k_bsdf_query(const DevMaterial* __restrict__ materials, int mate
     o[11] = __int_as_float(sampled);
 }
 
+// the same for a Disney row (wf_disney.h): `d` is the row's block
+__global__ void k_bsdf_query_disney(const DevDisney* __restrict__ d, int64_t n, const float* __restrict__ wo_in, const float* __restrict__ wi_in,
+                                    const float* __restrict__ u_in, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Frame fr;
+    fr.ss = V3{1.0f, 0.0f, 0.0f};
+    fr.ts = V3{0.0f, 1.0f, 0.0f};
+    fr.ns = V3{0.0f, 0.0f, 1.0f};
+    fr.ng = fr.ns;
+    const V3 wo = V3{wo_in[3 * i], wo_in[3 * i + 1], wo_in[3 * i + 2]};
+    const V3 wi = V3{wi_in[3 * i], wi_in[3 * i + 1], wi_in[3 * i + 2]};
+    V3 f, wi_s = V3{0.0f, 0.0f, 0.0f}, f_s = wi_s;
+    float pdf, pdf_s = 0.0f;
+    int sampled = 0;
+    dz_f_pdf(d, fr, wo, wi, &f, &pdf);
+    bool ok;
+    float ps = 0.0f;
+    V3 w;
+    V3 fs = dz_sample_f(d, fr, wo, u_in[2 * i], u_in[2 * i + 1], &w, &ps, &ok, &sampled);
+    if (ok) {
+        wi_s = w;
+        f_s = fs;
+        pdf_s = ps;
+    } else {
+        sampled = 0;
+    }
+    float* o = out + 12 * i;
+    o[0] = f.x;
+    o[1] = f.y;
+    o[2] = f.z;
+    o[3] = pdf;
+    o[4] = wi_s.x;
+    o[5] = wi_s.y;
+    o[6] = wi_s.z;
+    o[7] = f_s.x;
+    o[8] = f_s.y;
+    o[9] = f_s.z;
+    o[10] = pdf_s;
+    o[11] = __int_as_float(sampled);
+}
+
 extern "C" int pbrt_hip_bsdf_query(PbrtHipScene* s, int32_t material, int64_t n, const float* wo, const float* wi, const float* u, float* f,
                                    float* pdf, float* wi_s, float* f_s, float* pdf_s, int32_t* sampled_flags) try {
     if (!s) return PBRT_HIP_ERR_INVALID;
@@ -255,8 +297,12 @@ extern "C" int pbrt_hip_bsdf_query(PbrtHipScene* s, int32_t material, int64_t n,
         rc = PBRT_HIP_ERR_DEVICE;
     std::vector<float> h;
     if (rc == PBRT_HIP_OK) {
-        hipLaunchKernelGGL(k_bsdf_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, s->d.materials, material, n, d_in,
-                           d_in + 3 * un, d_in + 6 * un, d_out);
+        if (s->h_materials[material].type == kMatDisney)
+            hipLaunchKernelGGL(k_bsdf_query_disney, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, s->d.disney + material, n,
+                               d_in, d_in + 3 * un, d_in + 6 * un, d_out);
+        else
+            hipLaunchKernelGGL(k_bsdf_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, s->d.materials, material, n, d_in,
+                               d_in + 3 * un, d_in + 6 * un, d_out);
         h.resize(un * 12);
         if (!hip_ok(ctx, hipGetLastError(), "k_bsdf_query") || !hip_ok(ctx, hipStreamSynchronize(ctx->stream), "k_bsdf_query") ||
             !hip_ok(ctx, hipMemcpy(h.data(), d_out, un * 12 * sizeof(float), hipMemcpyDeviceToHost), "D2H"))
@@ -918,6 +964,7 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
     sc.spatial = nullptr;
     sc.n_voxel[0] = sc.n_voxel[1] = sc.n_voxel[2] = 1;
     sc.mis_bool = ctx->count_traversal != 1 ? 1 : 0;  // wf_state.h: RS_MIS_BOOL
+    sc.disney = s->d.disney;
     if (rp.integrator == PBRT_INTEGRATOR_PATH && rp.light_strategy == 2 && s->d.n_lights > 1) {
         // create_light_sample_distribution("spatial") -> SpatialLightDistribution::new(scene, 64) (lightdistrib.rs:85-107, 228)
         if (!s->d_spatial) {
@@ -1096,8 +1143,12 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
 {
                 dim3 sg((n_shade + 255) / 256), sb(256);
                 // a plastic or metal material in the scene's table selects the level-1 instantiations, a row of
-                // pbrt_hip_scene_set_material the level-2 ones (AO reads no BSDF)
-                if (rp.integrator == PBRT_INTEGRATOR_DIRECT && s->bxdfs)
+                // pbrt_hip_scene_set_material the level-2 ones, a Disney row the level-3 ones (AO reads no BSDF)
+                if (rp.integrator == PBRT_INTEGRATOR_DIRECT && s->disney)
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, 3>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                else if (rp.integrator == PBRT_INTEGRATOR_WHITTED && s->disney)
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, 3>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                else if (rp.integrator == PBRT_INTEGRATOR_DIRECT && s->bxdfs)
                     hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, 2>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
                 else if (rp.integrator == PBRT_INTEGRATOR_DIRECT && s->glossy)
                     hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, 1>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
@@ -1119,7 +1170,7 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
                     hipLaunchKernelGGL(k_shade_sort_keys, dim3((n_shade + 255) / 256), dim3(256), 0, st, sc, ps, q[cur].shade, n_shade,
                                        pp.max_depth, shade_keys[0], shade_positions);
                     size_t tb = shade_tmp_bytes;
-                    if (pb::sort_pairs_u32(st, shade_tmp, &tb, shade_keys[0], shade_keys[1], shade_positions, shade_sorted, n_shade, s->bxdfs ? 4 : 3) != 0 &&
+                    if (pb::sort_pairs_u32(st, shade_tmp, &tb, shade_keys[0], shade_keys[1], shade_positions, shade_sorted, n_shade, (s->bxdfs || s->disney) ? 4 : 3) != 0 &&
                         rc == PBRT_HIP_OK) {
                         ctx->last_error = "rocPRIM radix sort failed";
                         rc = PBRT_HIP_ERR_DEVICE;
@@ -1127,12 +1178,16 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
                     order = shade_sorted;
                 }
                 const dim3 sg((n_shade + 255) / 256), sb(256);
-                if (bin_shade && wavefront >= 1 && s->bxdfs)
+                if (bin_shade && wavefront >= 1 && s->disney)
+                    hipLaunchKernelGGL((k_shade<true, 3>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
+                else if (bin_shade && wavefront >= 1 && s->bxdfs)
                     hipLaunchKernelGGL((k_shade<true, 2>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
                 else if (bin_shade && wavefront >= 1 && s->glossy)
                     hipLaunchKernelGGL((k_shade<true, 1>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
                 else if (bin_shade && wavefront >= 1)
                     hipLaunchKernelGGL((k_shade<true, 0>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
+                else if (s->disney)
+                    hipLaunchKernelGGL((k_shade<false, 3>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
                 else if (s->bxdfs)
                     hipLaunchKernelGGL((k_shade<false, 2>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
                 else if (s->glossy)

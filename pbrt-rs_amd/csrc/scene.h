@@ -104,6 +104,28 @@ struct DevMaterial {
 // DevMaterial::type past PbrtMaterialType: the rows pbrt_hip_scene_set_material writes (wf_bxdfs.h). kMatOrenNayar: kd,
 // OrenNayar's A / B in alpha_u / alpha_v; kMatRoughGlass: kd = Kr, kt = Kt, eta, the alphas; kMatSubstrate: kd, kt = Ks, the alphas
 constexpr int kMatOrenNayar = 6, kMatRoughGlass = 7, kMatSubstrate = 8;
+// kMatDisney: a row of pbrt_hip_scene_set_disney_material (wf_disney.h). The DevMaterial row keeps the colour in kd and eta; what
+// the lobes read is the DevDisney block of the same index in DevSceneData::disney, computed on the host in double and rounded once.
+constexpr int kMatDisney = 9;
+// DevDisney::lobes, in the order DisneyMaterial adds them (BSDF::sample_f picks a lobe by index)
+constexpr int kDzDiffuse = 1, kDzFakeSS = 2, kDzRetro = 4, kDzSheen = 8, kDzMicro = 16, kDzClearcoat = 32, kDzTrans = 64, kDzLambertT = 128;
+struct DevDisney {
+    float diffuse[3];    // DisneyDiffuse R
+    float fakess[3];     // DisneyFakeSS R (thin)
+    float retro[3];      // DisneyRetro R
+    float sheen[3];      // DisneySheen R
+    float cspec0[3];     // DisneyFresnel R0
+    float trans[3];      // MicrofacetTransmission T
+    float lambert_t[3];  // LambertianTransmission T (thin)
+    float metallic, eta, roughness;
+    float ax, ay;        // the reflection lobe's alphas
+    float tax, tay;      // the transmission lobe's (thin: the scaled roughness)
+    float clearcoat;     // DisneyClearcoat weight
+    float cc_a2, cc_ln_a2, cc_norm;  // its gloss g: g^2, ln g^2, (g^2 - 1) / (pi ln g^2)
+    int lobes;           // kDz* bits
+    int n;               // number of lobes, 1..8
+    int sep_trans;       // the transmission lobe masks with G1(wo) G1(wi) (not thin)
+};
 
 // Distribution1D (src/core/sampling.rs:62-154) flattened: func[n], cdf[n+1]
 struct DevDistribution1D {
@@ -142,6 +164,7 @@ struct DevSceneData {
     float world_center[3], world_radius;  // lights/infinite.rs:135-139
     DevDistribution1D light_distrib_uniform, light_distrib_power;
     const DevEnvMap* env_maps;  // [n_lights] once a map was set (DevLight::slot names the entry), else null
+    const DevDisney* disney;    // [n_materials]: the blocks of the kMatDisney rows
 };
 
 }  // namespace pb
@@ -156,6 +179,7 @@ struct PbrtHipScene {
     std::vector<pb::DevMaterial> h_materials;  // the device table's host copy (pbrt_hip_scene_set_material_roughness)
     bool glossy = false;  // a plastic or metal material in the table: the shading kernels' glossy instantiations run
     bool bxdfs = false;   // a kMatOrenNayar / kMatRoughGlass / kMatSubstrate row in the table: their level-2 instantiations run
+    bool disney = false;  // a kMatDisney row in the table: their level-3 instantiations run
     std::vector<int> light_samples;  // max(1, n_samples) per light (light.rs:76)
     // image maps of infinite lights (pbrt_hip_scene_set_environment_map): per light its descriptor and its device arrays
     std::vector<pb::DevEnvMap> h_env;

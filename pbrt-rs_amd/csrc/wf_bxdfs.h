@@ -241,7 +241,7 @@ PB_DEV V3 bsdf_sample_f(const GenBsdf& b, const Frame& fr, V3 wo_w, float u0, fl
 }
 
 // The BSDF type of a shading-kernel instantiation level: 0 matte only (MatteBsdf, built in place), 1 plus plastic / metal,
-// 2 plus the rows of pbrt_hip_scene_set_material
+// 2 plus the rows of pbrt_hip_scene_set_material, 3 plus Disney rows (wf_disney.h, load_bsdf there)
 template <int LEVEL>
 struct LevelBsdf {
     typedef NsBsdf type;
@@ -250,7 +250,5 @@ template <>
 struct LevelBsdf<2> {
     typedef GenBsdf type;
 };
-PB_DEV void load_bsdf(const DevMaterial& m, NsBsdf* b) { *b = ns_bsdf(m); }
-PB_DEV void load_bsdf(const DevMaterial& m, GenBsdf* b) { *b = gen_bsdf(m); }
 
 }  // namespace pb

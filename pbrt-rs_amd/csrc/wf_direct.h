@@ -27,7 +27,7 @@ struct DirectState {
 #endif
 // MODE: PBRT_INTEGRATOR_DIRECT / _WHITTED / _AO: one instantiation each, the other integrators' stages compile away.
 // LEVEL as k_shade's: 1 (GLOSSY), the scene holds plastic or metal: the non-specular BSDF is the general one of
-// wf_microfacet.h (matte included); 2, a row of pbrt_hip_scene_set_material: that of wf_bxdfs.h.
+// wf_microfacet.h (matte included); 2, a row of pbrt_hip_scene_set_material: that of wf_bxdfs.h; 3, a Disney row: that of wf_disney.h.
 // The glossy direct-lighting instantiations run one wave per SIMD: at two level 1 spills 19 registers.
 template <int MODE, int LEVEL>
 __global__ void __launch_bounds__(256, (LEVEL >= 1 && MODE == PBRT_INTEGRATOR_DIRECT) ? 1 : PB_DIRECT_WAVES) k_shade_direct(ShadeConsts sc, PathState ps, DirectState ds, Queues qin,
@@ -210,7 +210,7 @@ __global__ void __launch_bounds__(256, (LEVEL >= 1 && MODE == PBRT_INTEGRATOR_DI
                 float spdf;
                 if (GLOSSY) {
                     typename LevelBsdf<LEVEL>::type nsb;
-                    load_bsdf(sc.materials[sf.material], &nsb);  // read again here: keeps the alphas out of the loop's registers
+                    load_bsdf(sc, sf.material, sc.materials[sf.material], &nsb);  // read again here: keeps the alphas out of the loop's registers
                     if (nsb.n > 0) bsdf_f_pdf(nsb, fr, sf.wo, wi, &f, &spdf);  // BSDF::f, all lobes
                 } else if (mat.type == PBRT_MAT_MATTE && !is_black(kd)) {
                     matte_f_pdf(fr, kd, sf.wo, wi, &f, &spdf);  // BSDF::f, all lobes
@@ -254,7 +254,7 @@ __global__ void __launch_bounds__(256, (LEVEL >= 1 && MODE == PBRT_INTEGRATOR_DI
                 int nee_flags;
                 if (GLOSSY) {
                     typename LevelBsdf<LEVEL>::type nsb;
-                    load_bsdf(sc.materials[sf.material], &nsb);
+                    load_bsdf(sc, sf.material, sc.materials[sf.material], &nsb);
                     nee_flags = estimate_direct_emit(sc, RecordSink{ps, p}, sf, fr, nsb.n > 0, nsb, light_num, ul0, ul1, us0, us1, pick_pdf, T);
                 } else {
                     bool matte = (mat.type == PBRT_MAT_MATTE) && !is_black(kd);

@@ -1,6 +1,6 @@
 // wf_lights.h — Light::sample_li for every light type, spatial light tables, estimate_direct (emit / resolve), specular lobes (part of wavefront.h)
 #pragma once
-#include "wf_bxdfs.h"
+#include "wf_disney.h"
 
 namespace pb {
 
@@ -278,7 +278,7 @@ __global__ void k_spatial_light_tables(ShadeConsts sc, float* __restrict__ table
 // BSDF, evaluate the light pdf. Writes the shadow ray (slot 2), the MIS ray (slot 1) and the pending
 // terms through `out` (wf_state.h: RecordSink = into the path state at a known record index, StageSink = k_shade's LDS
 // staging until the index is known); returns PF_NEE_* flags for the rays that must be traced. `nonspecular` = the
-// BSDF has a non-specular lobe, `bsdf` its lobes (MatteBsdf: matte only; NsBsdf: matte, plastic or metal; GenBsdf: any); otherwise f == 0
+// BSDF has a non-specular lobe, `bsdf` its lobes (MatteBsdf: matte only; NsBsdf: matte, plastic or metal; GenBsdf: any row of levels 0-2; DisneyBsdf: any); otherwise f == 0
 // and nothing is emitted.
 template <class Bsdf, class Sink>
 PB_DEV int estimate_direct_emit(const ShadeConsts& sc, const Sink& out, const Surf& sf, const Frame& fr,

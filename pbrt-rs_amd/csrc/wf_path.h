@@ -42,8 +42,8 @@ __global__ void k_shade_sort_keys(ShadeConsts sc, PathState ps, const uint32_t* 
 }
 
 // keys: 0 nothing to shade, 1 + DevMaterial::type (none, matte, mirror, glass; level 1: plastic, metal as well; level 2: the
-// three kinds of set_material rows as well), the last = no queue entry (block tail)
-constexpr int shade_keys(int level) { return level == 2 ? 11 : level == 1 ? 8 : 6; }
+// three kinds of set_material rows as well; level 3: Disney rows as well), the last = no queue entry (block tail)
+constexpr int shade_keys(int level) { return level == 3 ? 12 : level == 2 ? 11 : level == 1 ? 8 : 6; }
 template <int KEYS>
 struct ShadeBins {
     uint32_t count[4][KEYS];  // per wave of the block, per key
@@ -58,12 +58,14 @@ struct ShadeBins {
 // (MicrofacetReflection lobes, wf_microfacet.h); matte then goes through the same general BSDF (bit for bit the Lambertian
 // code), and the instantiations without it stay as they were. 2: a row of pbrt_hip_scene_set_material as well (OrenNayar,
 // glossy transmission, FresnelBlend: GenBsdf, wf_bxdfs.h), the rows of level 1 through the functions of level 1. Level 2
-// fits the same launch bounds without scratch: 162 / 164 VGPRs (profiles/r08_bxdf_set.txt).
+// fits the same launch bounds without scratch: 162 / 164 VGPRs (profiles/r08_bxdf_set.txt). 3: a Disney row as well (DisneyBsdf,
+// wf_disney.h). At three waves per SIMD the binned level 3 spills 12 bytes, so level 3 alone is bounded at two
+// (profiles/r09_disney.txt).
 // Thread i takes the shade-queue entry at position rec = i (order: rec = order[i], the queue in material order): the path
 // p = qin.shade[rec] with its persistent state at p, and the transient records of this generation at rec. What the path
 // hands to the next launch is staged in LDS and written to the next generation at its position in qout.shade.
 template <bool BIN, int LEVEL>
-__global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
+__global__ void __launch_bounds__(256, LEVEL == 3 ? 2 : PB_SHADE_WAVES) k_shade(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
                                                  TileList tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
     constexpr bool GLOSSY = LEVEL >= 1;
     constexpr int kShadeKeys = shade_keys(LEVEL);
@@ -165,7 +167,7 @@ __global__ void __launch_bounds__(256, PB_SHADE_WAVES) k_shade(ShadeConsts sc, P
                     bool nonspecular;
                     typename LevelBsdf<LEVEL>::type nsb;
                     if (GLOSSY) {
-                        load_bsdf(mat, &nsb);
+                        load_bsdf(sc, sf.material, mat, &nsb);
                         nonspecular = nsb.n > 0;
                         if (mat.type == PBRT_MAT_GLASS) has_lobe = !(is_black(kd) && is_black(kt));
                         else if (mat.type == PBRT_MAT_MIRROR) has_lobe = !is_black(kd);

@@ -328,6 +328,7 @@ struct ShadeConsts {
     // MIS rays towards lights that are not area lights are queued as RS_MIS_BOOL (wf_state.h); off while the reference's
     // loops are being counted (pbrt_hip_set_counting(1): the reference walks those rays to their closest hit)
     int mis_bool;
+    const DevDisney* disney;  // [n_materials]: the blocks of the kMatDisney rows (wf_disney.h)
 };
 
 // ---- InfiniteAreaLight with an image map (DevEnvMap): one lookup and one Distribution2D for le, sample_li and pdf_li ----

@@ -40,7 +40,7 @@ EXPORTS = [
     "pbrt_hip_comm_last_error", "pbrt_hip_scene_wide_records", "pbrt_hip_get_wide_counters", "pbrt_hip_probe_gather", "pbrt_hip_probe_state_stream",
     "pbrt_hip_li", "pbrt_hip_li_device", "pbrt_hip_camera_rays", "pbrt_hip_scene_create_two_level", "pbrt_hip_debug_wide_export",
     "pbrt_hip_scene_set_environment_map", "pbrt_hip_envmap_tables", "pbrt_hip_scene_set_material_roughness", "pbrt_hip_bsdf_query",
-    "pbrt_hip_scene_set_material",
+    "pbrt_hip_scene_set_material", "pbrt_hip_scene_set_disney_material",
 ]
 MAT_NONE, MAT_MATTE, MAT_MIRROR, MAT_GLASS, MAT_PLASTIC, MAT_METAL = (scenes.MAT_NONE, scenes.MAT_MATTE, scenes.MAT_MIRROR,
                                                                       scenes.MAT_GLASS, scenes.MAT_PLASTIC, scenes.MAT_METAL)
@@ -81,6 +81,11 @@ class MaterialDesc(ctypes.Structure):
     _fields_ = [("type", ctypes.c_int32), ("kd", ctypes.c_float * 3), ("ks", ctypes.c_float * 3), ("kr", ctypes.c_float * 3),
                 ("kt", ctypes.c_float * 3), ("eta", ctypes.c_float), ("sigma", ctypes.c_float), ("u_roughness", ctypes.c_float),
                 ("v_roughness", ctypes.c_float), ("remap_roughness", ctypes.c_int32)]
+
+
+class DisneyDesc(ctypes.Structure):
+    """PbrtDisneyDesc (pbrt_hip_scene_set_disney_material); scenes.disney gives the keyword form"""
+    _fields_ = [("color", ctypes.c_float * 3)] + [(k, ctypes.c_float) for k in scenes.DISNEY_SCALARS] + [("thin", ctypes.c_int32)]
 
 
 class PbrtHipError(RuntimeError):
@@ -174,6 +179,7 @@ def lib():
         L.pbrt_hip_scene_set_material_roughness.argtypes = [vp, i32, ctypes.c_float, ctypes.c_float, i32]
         L.pbrt_hip_bsdf_query.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.pbrt_hip_scene_set_material.argtypes = [vp, i32, vp]
+        L.pbrt_hip_scene_set_disney_material.argtypes = [vp, i32, vp]
         L.pbrt_hip_film_to_rgb.restype = None
         _lib = L
     return _lib
@@ -390,11 +396,14 @@ class Scene:
     def __init__(self, ctx, scene, max_prims_in_node=4, split_method=SPLIT_SAH, bvh=None, device_build=False):
         """device_build=True: BVHAccel::new(HLBVH) built and laid out on the GPU (pbrt_hip_scene_create_hlbvh);
         self.build_ms / self.layout_ms then hold the HIP-event times and self.nodes is None.
-        scene["material_descs"] = {row: descriptor} (optional): set_material(row, descriptor) after creation."""
+        scene["material_descs"] = {row: descriptor} (optional): set_material(row, descriptor) after creation;
+        scene["disney_descs"] = {row: descriptor} (optional): set_disney_material(row, descriptor) after that."""
         self._create(ctx, scene, max_prims_in_node, split_method, bvh, device_build)
         try:
             for row, desc in (scene.get("material_descs") or {}).items():
                 self.set_material(row, desc)
+            for row, desc in (scene.get("disney_descs") or {}).items():
+                self.set_disney_material(row, desc)
         except Exception:
             self.close()  # a refused descriptor: the scene that was just created does not outlive the constructor
             raise
@@ -676,6 +685,17 @@ class Scene:
             desc = d
         self.ctx.check(lib().pbrt_hip_scene_set_material(self.h, int(m), None if desc is None else ctypes.byref(desc)),
                        "pbrt_hip_scene_set_material")
+
+    def set_disney_material(self, m, desc):
+        """Replaces row m of the material table by pbrt-v3's DisneyMaterial without subsurface: scenes.disney() (a dict of
+        PbrtDisneyDesc's fields) or a DisneyDesc (pbrt_hip_scene_set_disney_material)."""
+        if desc is not None and not isinstance(desc, DisneyDesc):
+            d = DisneyDesc()
+            for k, v in desc.items():
+                setattr(d, k, (ctypes.c_float * 3)(*[float(c) for c in v]) if k == "color" else v)
+            desc = d
+        self.ctx.check(lib().pbrt_hip_scene_set_disney_material(self.h, int(m), None if desc is None else ctypes.byref(desc)),
+                       "pbrt_hip_scene_set_disney_material")
 
     def bsdf_query(self, material, wo, wi, u):
         """BSDF::f / pdf / sample_f of a material on the device, in the shading frame (n = +z): wo, wi (n, 3), u (n, 2).

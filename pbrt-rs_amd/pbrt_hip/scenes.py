@@ -105,6 +105,39 @@ def substrate(kd, ks, u_roughness, v_roughness=None, remap=True):
                 remap_roughness=int(bool(remap)))
 
 
+DISNEY_SCALARS = ("metallic", "eta", "roughness", "specular_tint", "anisotropic", "sheen", "sheen_tint", "clearcoat", "clearcoat_gloss",
+                  "spec_trans", "flatness", "diff_trans")  # PbrtDisneyDesc's floats after color, in order
+
+
+def disney(color, metallic=0.0, eta=1.5, roughness=0.5, specular_tint=0.0, anisotropic=0.0, sheen=0.0, sheen_tint=0.5, clearcoat=0.0,
+           clearcoat_gloss=1.0, spec_trans=0.0, flatness=0.0, diff_trans=1.0, thin=False):
+    """Descriptor (Scene.set_disney_material, scene["disney_descs"]) of pbrt-v3's DisneyMaterial without subsurface, with
+    pbrt-v3's defaults."""
+    return dict(color=tuple(float(c) for c in color), metallic=float(metallic), eta=float(eta), roughness=float(roughness),
+                specular_tint=float(specular_tint), anisotropic=float(anisotropic), sheen=float(sheen), sheen_tint=float(sheen_tint),
+                clearcoat=float(clearcoat), clearcoat_gloss=float(clearcoat_gloss), spec_trans=float(spec_trans), flatness=float(flatness),
+                diff_trans=float(diff_trans), thin=int(bool(thin)))
+
+
+def disney_invalid(desc):
+    """Why pbrt_hip_scene_set_disney_material refuses the descriptor (the same rules, checked before the call), or None"""
+    if desc is None:
+        return "null desc"
+    if not all(np.isfinite(c) and c >= 0 for c in desc["color"]):
+        return "color must be finite and >= 0"
+    for k in DISNEY_SCALARS:
+        v = float(np.float32(desc[k]))
+        if not (np.isfinite(v) and v >= 0):
+            return f"{k} must be finite and >= 0"
+        if k == "diff_trans" and v > 2:
+            return "diff_trans must be <= 2"
+        if k not in ("eta", "sheen", "clearcoat", "diff_trans") and v > 1:
+            return f"{k} must be <= 1"
+    if not desc["eta"] > 0:
+        return "eta must be > 0"
+    return None
+
+
 def _lights(rows):
     """rows: (type, L, prim, two_sided, n_samples) tuples or ready LIGHT_DTYPE records (point_light() ...)."""
     l = np.zeros(len(rows), dtype=LIGHT_DTYPE)

@@ -399,6 +399,45 @@ int pbrt_hip_scene_create_with_spheres(PbrtHipContext* ctx, const float* positio
                                        int32_t n_lights, const float* spheres, const int32_t* sphere_material,
                                        const int32_t* sphere_light, int32_t n_spheres, const PbrtLinearBVHNode* nodes, int32_t n_nodes,
                                        const int32_t* prim_order, PbrtHipScene** out);
+/* Quadric shapes under a general affine transform next to the triangles: Sphere (src/shapes/sphere.rs, partial sweeps
+ * included), Disk (src/shapes/disk.rs) and Cylinder (src/shapes/cylinder.rs for the hit test; object_bound, area and sample,
+ * which the reference leaves unimplemented, after pbrt-v3: SURVEY.md D79-D82). A record mirrors the constructors' arguments:
+ * the z range is ordered (and for a sphere clamped to [-radius, radius]) and phi_max clamped to [0, 360] as they do it.
+ * to_object must be the inverse of to_world (the caller supplies it, as for PbrtInstance); both are affine.
+ * Limits, the same as for pbrt_hip_scene_create_with_spheres: one-level scenes only (no instancing), no per-vertex shading
+ * data in the same scene, binary-record traversal (pbrt_hip_scene_wide_records reports "scene with shapes", and
+ * PBRT_TRAVERSAL_STACKLESS refuses the scene). A shape may carry a DiffuseAreaLight: area() and the sampling pdfs are
+ * object-space quantities, as in pbrt-v3, so such a shape is meaningful only under a rigid transform (not checked). */
+enum PbrtShapeType { PBRT_SHAPE_SPHERE = 0, PBRT_SHAPE_DISK = 1, PBRT_SHAPE_CYLINDER = 2 };
+typedef struct PbrtShape {
+    int32_t type;                /* PbrtShapeType */
+    int32_t reverse_orientation;
+    int32_t material;            /* row of `materials` */
+    int32_t light;               /* index of its DiffuseAreaLight (whose `prim` is n_tris + i) or -1 */
+    float radius;
+    float z_min, z_max;          /* sphere, cylinder; disk: z_min = height */
+    float inner_radius;          /* disk */
+    float phi_max;               /* degrees */
+    float pad[3];
+    float to_world[16];          /* row-major, last row (0,0,0,1) */
+    float to_object[16];         /* its inverse */
+} PbrtShape;
+/* Shape::world_bound = object_to_world * object_bound() per shape (the union of the eight transformed corners, as
+ * pbrt_hip_instance_bounds): sphere and cylinder (-r,-r,z_min)..(r,r,z_max), disk (-r,-r,height)..(r,r,height).
+ * bounds: n x {min.xyz, max.xyz}. Host only, needs no GPU; what pbrt_hip_bvh_build_boxes is fed with. */
+int pbrt_hip_shape_world_bounds(const PbrtShape* shapes, int32_t n, float* bounds);
+/* As pbrt_hip_scene_create_with_spheres with the shape records in place of the sphere arrays: shape i is primitive
+ * n_tris + i in prim_order, and hit records of shapes carry the refined object-space hit point in (b0, b1, b2).
+ * PBRT_HIP_ERR_INVALID (pbrt_hip_last_error says why) for an unknown type, a radius that is not positive, a disk's
+ * inner_radius outside [0, radius), a cylinder with z_min == z_max, phi_max <= 0, a transform that is not affine, a
+ * material or light out of range, and a partial sphere (z range or phi_max short of the full sphere) that carries a
+ * light: Sphere::sample covers the full sphere only. */
+int pbrt_hip_scene_create_with_shapes(PbrtHipContext* ctx, const float* positions, int32_t n_verts, const int32_t* indices,
+                                      int32_t n_tris, const int32_t* tri_material, const PbrtMaterial* materials,
+                                      int32_t n_materials, const int32_t* tri_light, const PbrtLight* lights,
+                                      int32_t n_lights, const PbrtShape* shapes, int32_t n_shapes,
+                                      const PbrtLinearBVHNode* nodes, int32_t n_nodes, const int32_t* prim_order,
+                                      PbrtHipScene** out);
 /* Two-level scene of BASELINE config 5's shape: `n_instances` TransformedPrimitives of ONE object-space triangle
  * aggregate (pbrt_hip_scene_create_two_level with one object and no world-space triangles). blas_* = BVHAccel over the
  * triangles (object space); tlas_* = BVHAccel over the instances' world bounds, tlas_order[slot] = instance index.

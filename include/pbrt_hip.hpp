@@ -115,6 +115,46 @@ struct Sphere {
     int32_t material = 0;
     int32_t area_light = -1;
 };
+// The quadric shapes under a general transform (include/pbrt_hip.h: PbrtShape), with the reference's constructor arguments in
+// the reference's order: o2w, w2o, reverse_orientation, then the shape's own (row-major 4 x 4 affine matrices; w2o = nullptr:
+// the inverse of o2w, formed in double and rounded once). material / area_light as for Sphere above (`prim` of the light is
+// n_triangles + the shape's index). A shape that carries a light is meaningful only under a rigid transform: area() and the
+// sampling pdfs are object-space quantities, as in pbrt-v3.
+void inverse_affine(const double m[16], double inv[16]);
+struct Shape {
+    PbrtShape record;
+
+protected:
+    Shape(int32_t type, const double o2w[16], const double w2o[16], bool reverse_orientation, Float radius, Float z_min, Float z_max,
+          Float inner_radius, Float phi_max, int32_t material, int32_t area_light) {
+        std::memset(&record, 0, sizeof(record));
+        double inv[16];
+        if (!w2o) inverse_affine(o2w, inv);
+        for (int k = 0; k < 12; ++k) record.to_world[k] = (float)o2w[k], record.to_object[k] = (float)(w2o ? w2o[k] : inv[k]);
+        record.to_world[15] = record.to_object[15] = 1.0f;
+        record.type = type, record.reverse_orientation = reverse_orientation ? 1 : 0, record.material = material, record.light = area_light;
+        record.radius = radius, record.z_min = z_min, record.z_max = z_max, record.inner_radius = inner_radius, record.phi_max = phi_max;
+    }
+};
+// Sphere::new(o2w, w2o, reverse_orientation, radius, z_min, z_max, phi_max) (src/shapes/sphere.rs:208-226): the general form of
+// Sphere above, which stays the aggregate it was and keeps going through pbrt_hip_scene_create_with_spheres
+struct TransformedSphere : Shape {
+    TransformedSphere(const double o2w[16], const double w2o[16], bool reverse_orientation, Float radius, Float z_min, Float z_max, Float phi_max,
+                      int32_t material = 0, int32_t area_light = -1)
+        : Shape(PBRT_SHAPE_SPHERE, o2w, w2o, reverse_orientation, radius, z_min, z_max, 0, phi_max, material, area_light) {}
+};
+// Disk::new(o2w, w2o, reverse_orientation, height, radius, inner_radius, phi_max) (src/shapes/disk.rs:24-40)
+struct Disk : Shape {
+    Disk(const double o2w[16], const double w2o[16], bool reverse_orientation, Float height, Float radius, Float inner_radius, Float phi_max,
+         int32_t material = 0, int32_t area_light = -1)
+        : Shape(PBRT_SHAPE_DISK, o2w, w2o, reverse_orientation, radius, height, height, inner_radius, phi_max, material, area_light) {}
+};
+// Cylinder::new(o2w, w2o, reverse_orientation, radius, z_min, z_max, phi_max) (src/shapes/cylinder.rs:23-39)
+struct Cylinder : Shape {
+    Cylinder(const double o2w[16], const double w2o[16], bool reverse_orientation, Float radius, Float z_min, Float z_max, Float phi_max,
+             int32_t material = 0, int32_t area_light = -1)
+        : Shape(PBRT_SHAPE_CYLINDER, o2w, w2o, reverse_orientation, radius, z_min, z_max, 0, phi_max, material, area_light) {}
+};
 struct BuildOnDevice {};  // tag: BVHAccel::new(HLBVH) built and laid out on the GPU (bvh.rs:475-568), nothing of the tree crosses PCIe
 
 // src/core/primitive.rs:17-30
@@ -135,19 +175,22 @@ enum class SplitMethod { SAH = 0, HLBVH = 1, Middle = 2, EqualCounts = 3 };  // 
 // TransformedPrimitive::new(primitive, primitive_to_world) with a static transform (primitive.rs:105-123): the record the
 // instanced BVHAccel constructor takes. to_world row-major 4 x 4 with last row (0, 0, 0, 1); the inverse is formed in double.
 // material >= 0 overrides the object's materials for this instance.
-inline PbrtInstance TransformedPrimitive(const double to_world[16], int32_t material = -1) {
-    PbrtInstance inst;
-    std::memset(&inst, 0, sizeof(inst));
-    const double* m = to_world;
+inline void inverse_affine(const double m[16], double inv[16]) {  // of a row-major 4 x 4 with last row (0, 0, 0, 1), in double
     const double det = m[0] * (m[5] * m[10] - m[6] * m[9]) - m[1] * (m[4] * m[10] - m[6] * m[8]) + m[2] * (m[4] * m[9] - m[5] * m[8]);
     if (det == 0.0) throw Error("TransformedPrimitive::new: singular transform", PBRT_HIP_ERR_INVALID);
-    double inv[16] = {0};
+    for (int k = 0; k < 16; ++k) inv[k] = 0.0;
     const double id = 1.0 / det;
     inv[0] = (m[5] * m[10] - m[6] * m[9]) * id, inv[1] = (m[2] * m[9] - m[1] * m[10]) * id, inv[2] = (m[1] * m[6] - m[2] * m[5]) * id;
     inv[4] = (m[6] * m[8] - m[4] * m[10]) * id, inv[5] = (m[0] * m[10] - m[2] * m[8]) * id, inv[6] = (m[2] * m[4] - m[0] * m[6]) * id;
     inv[8] = (m[4] * m[9] - m[5] * m[8]) * id, inv[9] = (m[1] * m[8] - m[0] * m[9]) * id, inv[10] = (m[0] * m[5] - m[1] * m[4]) * id;
     for (int r = 0; r < 3; ++r) inv[4 * r + 3] = -(inv[4 * r] * m[3] + inv[4 * r + 1] * m[7] + inv[4 * r + 2] * m[11]);
     inv[15] = 1.0;
+}
+inline PbrtInstance TransformedPrimitive(const double to_world[16], int32_t material = -1) {
+    PbrtInstance inst;
+    std::memset(&inst, 0, sizeof(inst));
+    double inv[16];
+    inverse_affine(to_world, inv);
     for (int k = 0; k < 16; ++k) {
         inst.to_world[k] = (float)to_world[k];
         inst.to_object[k] = (float)inv[k];
@@ -228,6 +271,37 @@ public:
                                                 nodes, n_nodes, order, &h_);
         pbrt_hip_free(nodes), pbrt_hip_free(order);
         ctx_->check(rc, "BVHAccel::new: pbrt_hip_scene_create_with_spheres");
+    }
+    // Triangles and quadric shapes (TransformedSphere, Disk, Cylinder) side by side under one BVHAccel: the tree over the
+    // primitives' world bounds, triangles first, the shapes' from pbrt_hip_shape_world_bounds (Shape::world_bound)
+    BVHAccel(std::shared_ptr<Context> ctx, const TriangleMesh& mesh, const std::vector<Shape>& shapes, int max_prims_in_node = 4,
+             SplitMethod split_method = SplitMethod::SAH)
+        : ctx_(std::move(ctx)) {
+        const size_t nt = (size_t)mesh.n_triangles(), ns = shapes.size();
+        std::vector<float> lo(3 * (nt + ns)), hi(3 * (nt + ns)), box(6 * ns);
+        std::vector<PbrtShape> records(ns);
+        for (size_t t = 0; t < nt; ++t)
+            for (int k = 0; k < 3; ++k) {
+                const float a = mesh.p[3 * (size_t)mesh.vertex_indices[3 * t] + k], b = mesh.p[3 * (size_t)mesh.vertex_indices[3 * t + 1] + k],
+                            c = mesh.p[3 * (size_t)mesh.vertex_indices[3 * t + 2] + k];
+                lo[3 * t + k] = std::fmin(a, std::fmin(b, c)), hi[3 * t + k] = std::fmax(a, std::fmax(b, c));
+            }
+        for (size_t i = 0; i < ns; ++i) records[i] = shapes[i].record;
+        int rc = pbrt_hip_shape_world_bounds(records.data(), (int32_t)ns, box.data());
+        if (rc != PBRT_HIP_OK) throw Error("BVHAccel::new: pbrt_hip_shape_world_bounds failed", rc);
+        for (size_t i = 0; i < ns; ++i)
+            for (int k = 0; k < 3; ++k) lo[3 * (nt + i) + k] = box[6 * i + k], hi[3 * (nt + i) + k] = box[6 * i + 3 + k];
+        PbrtLinearBVHNode* nodes = nullptr;
+        int32_t n_nodes = 0, *order = nullptr;
+        rc = pbrt_hip_bvh_build_boxes(lo.data(), hi.data(), (int32_t)(nt + ns), max_prims_in_node, (int)split_method, &nodes, &n_nodes, &order);
+        if (rc != PBRT_HIP_OK) throw Error("BVHAccel::new: pbrt_hip_bvh_build_boxes failed", rc);
+        for (int k = 0; k < 3; ++k) (&bound_.min.x)[k] = nodes[0].bounds_min[k], (&bound_.max.x)[k] = nodes[0].bounds_max[k];
+        n_nodes_ = n_nodes;
+        rc = pbrt_hip_scene_create_with_shapes(ctx_->handle(), mesh.p.data(), mesh.n_vertices(), mesh.vertex_indices.data(), mesh.n_triangles(),
+                                               mesh.material.data(), mesh.materials.data(), (int32_t)mesh.materials.size(), mesh.area_light.data(),
+                                               mesh.lights.data(), (int32_t)mesh.lights.size(), records.data(), (int32_t)ns, nodes, n_nodes, order, &h_);
+        pbrt_hip_free(nodes), pbrt_hip_free(order);
+        ctx_->check(rc, "BVHAccel::new: pbrt_hip_scene_create_with_shapes");
     }
     // The top-level aggregate of a scene of TransformedPrimitives (primitive.rs:105-159): BVHAccel::new over the object's
     // triangles (object space), TransformedPrimitive::new(object, to_world) per instance, BVHAccel::new over their world bounds.

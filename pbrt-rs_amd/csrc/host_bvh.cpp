@@ -604,4 +604,40 @@ extern "C" int pbrt_hip_instance_bounds(const float object_min[3], const float o
 }
 PB_ABI_CATCH
 
+// Shape::world_bound (shape.rs: object_to_world * object_bound()) of the quadrics: Sphere::object_bound (sphere.rs), Disk::object_bound
+// (disk.rs:78-83), Cylinder::object_bound after pbrt-v3 (unimplemented in the reference, D79); z ordered as the constructors do
+extern "C" int pbrt_hip_shape_world_bounds(const PbrtShape* shapes, int32_t n, float* bounds) try {
+    if (n < 0 || (n > 0 && (!shapes || !bounds))) return PBRT_HIP_ERR_INVALID;
+    for (int32_t i = 0; i < n; ++i) {
+        const PbrtShape& s = shapes[i];
+        const float r = s.radius;
+        float z0 = s.z_min < s.z_max ? s.z_min : s.z_max, z1 = s.z_max > s.z_min ? s.z_max : s.z_min;
+        if (s.type == PBRT_SHAPE_SPHERE) {
+            z0 = z0 < -r ? -r : (z0 > r ? r : z0);
+            z1 = z1 < -r ? -r : (z1 > r ? r : z1);
+        } else if (s.type == PBRT_SHAPE_DISK) {
+            z0 = z1 = s.z_min;
+        } else if (s.type != PBRT_SHAPE_CYLINDER) {
+            return PBRT_HIP_ERR_INVALID;
+        }
+        const float omin[3] = {-r, -r, z0}, omax[3] = {r, r, z1};
+        const float* m = s.to_world;
+        float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+        for (int c = 0; c < 8; ++c) {
+            float x = (c & 1) ? omax[0] : omin[0];
+            float y = (c & 2) ? omax[1] : omin[1];
+            float z = (c & 4) ? omax[2] : omin[2];
+            for (int k = 0; k < 3; ++k) {
+                float p = m[4 * k] * x + m[4 * k + 1] * y + m[4 * k + 2] * z + m[4 * k + 3];
+                mn[k] = p < mn[k] ? p : mn[k];
+                mx[k] = p > mx[k] ? p : mx[k];
+            }
+        }
+        std::memcpy(bounds + 6 * (size_t)i, mn, 12);
+        std::memcpy(bounds + 6 * (size_t)i + 3, mx, 12);
+    }
+    return PBRT_HIP_OK;
+}
+PB_ABI_CATCH
+
 extern "C" void pbrt_hip_free(void* p) { std::free(p); }

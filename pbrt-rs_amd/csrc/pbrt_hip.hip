@@ -362,6 +362,9 @@ struct SphereArgs {
     const int32_t* material = nullptr;
     const int32_t* light = nullptr;  // per sphere: index of its DiffuseAreaLight or -1
     int32_t n = 0;
+    // or general quadric shapes (pbrt_hip_scene_create_with_shapes): primitive ids n_tris .. n_tris + n_shapes - 1
+    const PbrtShape* shapes = nullptr;
+    int32_t n_shapes = 0;
 };
 // Two-level scenes: the main geometry arguments of scene_create_impl are then the COMBINED mesh (every object's
 // triangles, object after object, then the world-space triangles) and prim_order the combined leaf order
@@ -459,6 +462,20 @@ extern "C" int pbrt_hip_scene_create_with_spheres(PbrtHipContext* ctx, const flo
     sa.material = sphere_material;
     sa.light = sphere_light;
     sa.n = n_spheres;
+    return scene_create_impl(ctx, positions, n_verts, indices, n_tris, tri_material, materials, n_materials, tri_light,
+                             lights, n_lights, nodes, n_nodes, prim_order, InstancingArgs(), out, nullptr, sa);
+}
+PB_ABI_CATCH
+
+extern "C" int pbrt_hip_scene_create_with_shapes(PbrtHipContext* ctx, const float* positions, int32_t n_verts,
+                                                 const int32_t* indices, int32_t n_tris, const int32_t* tri_material,
+                                                 const PbrtMaterial* materials, int32_t n_materials, const int32_t* tri_light,
+                                                 const PbrtLight* lights, int32_t n_lights, const PbrtShape* shapes,
+                                                 int32_t n_shapes, const PbrtLinearBVHNode* nodes, int32_t n_nodes,
+                                                 const int32_t* prim_order, PbrtHipScene** out) try {
+    SphereArgs sa;
+    sa.shapes = shapes;
+    sa.n_shapes = n_shapes;
     return scene_create_impl(ctx, positions, n_verts, indices, n_tris, tri_material, materials, n_materials, tri_light,
                              lights, n_lights, nodes, n_nodes, prim_order, InstancingArgs(), out, nullptr, sa);
 }
@@ -593,6 +610,83 @@ static const char* material_invalid(const PbrtMaterial& m) {
     return nullptr;
 }
 
+// ---- PbrtShape: what the constructors make of the arguments (Sphere::new sphere.rs:208-226, Disk::new disk.rs:24-40,
+// Cylinder::new cylinder.rs:23-39): z ordered (sphere: clamped to the radius), phi_max clamped and in radians ----
+static float shape_phi_max(const PbrtShape& sh) {
+    float deg = sh.phi_max < 0.0f ? 0.0f : (sh.phi_max > 360.0f ? 360.0f : sh.phi_max);
+    return deg * (kPi / 180.0f);
+}
+static void shape_z_range(const PbrtShape& sh, float* z0, float* z1) {
+    float lo = sh.z_min < sh.z_max ? sh.z_min : sh.z_max, hi = sh.z_max > sh.z_min ? sh.z_max : sh.z_min;
+    if (sh.type == PBRT_SHAPE_SPHERE) {
+        lo = lo < -sh.radius ? -sh.radius : (lo > sh.radius ? sh.radius : lo);
+        hi = hi < -sh.radius ? -sh.radius : (hi > sh.radius ? sh.radius : hi);
+    }
+    if (sh.type == PBRT_SHAPE_DISK) lo = hi = sh.z_min;
+    *z0 = lo;
+    *z1 = hi;
+}
+static const char* shape_invalid(const PbrtShape& sh, int32_t n_materials, int32_t n_lights) {
+    if (sh.type < PBRT_SHAPE_SPHERE || sh.type > PBRT_SHAPE_CYLINDER) return "unknown shape type";
+    if (!(sh.radius > 0.0f) || !std::isfinite(sh.radius)) return "shape radius must be positive";
+    if (sh.type == PBRT_SHAPE_DISK && !(sh.inner_radius >= 0.0f && sh.inner_radius < sh.radius))
+        return "disk inner_radius must lie in [0, radius)";
+    if (!std::isfinite(sh.z_min) || (sh.type != PBRT_SHAPE_DISK && !std::isfinite(sh.z_max))) return "shape z range must be finite";
+    if (sh.type == PBRT_SHAPE_CYLINDER && sh.z_min == sh.z_max) return "cylinder z_min and z_max must differ";
+    if (!(sh.phi_max > 0.0f)) return "shape phi_max must be positive";
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(sh.to_world[k]) || !std::isfinite(sh.to_object[k])) return "shape transforms must be finite";
+    if (sh.to_world[12] != 0.0f || sh.to_world[13] != 0.0f || sh.to_world[14] != 0.0f || sh.to_world[15] != 1.0f ||
+        sh.to_object[12] != 0.0f || sh.to_object[13] != 0.0f || sh.to_object[14] != 0.0f || sh.to_object[15] != 1.0f)
+        return "shape transforms must be affine (last row 0 0 0 1)";
+    if (sh.material < 0 || sh.material >= n_materials) return "shape material out of range";
+    if (sh.light < -1 || sh.light >= n_lights) return "shape light out of range";
+    if (sh.type == PBRT_SHAPE_SPHERE && sh.light >= 0) {
+        float z0, z1;
+        shape_z_range(sh, &z0, &z1);
+        if (z0 > -sh.radius || z1 < sh.radius || sh.phi_max < 360.0f)
+            return "a partial sphere cannot carry an area light (Sphere::sample covers the full sphere)";
+    }
+    return nullptr;
+}
+// Shape::area in object space: Sphere (sphere.rs:99-101), Disk (disk.rs:129-131), Cylinder after pbrt-v3 (D80)
+static float shape_area(const PbrtShape& sh) {
+    float z0, z1;
+    shape_z_range(sh, &z0, &z1);
+    const float phi_max = shape_phi_max(sh), r = sh.radius;
+    if (sh.type == PBRT_SHAPE_SPHERE) return phi_max * r * (z1 - z0);
+    if (sh.type == PBRT_SHAPE_DISK) return phi_max * 0.5f * (r * r - sh.inner_radius * sh.inner_radius);
+    return (z1 - z0) * r * phi_max;
+}
+static pb::DevShape shape_row(const PbrtShape& sh) {
+    pb::DevShape d;
+    std::memcpy(d.w2o, sh.to_object, 48);
+    std::memcpy(d.o2w, sh.to_world, 48);
+    d.radius = sh.radius;
+    shape_z_range(sh, &d.z_min, &d.z_max);
+    d.z_clip_min = (sh.type == PBRT_SHAPE_SPHERE && !(d.z_min > -sh.radius)) ? -INFINITY : d.z_min;
+    d.z_clip_max = (sh.type == PBRT_SHAPE_SPHERE && !(d.z_max < sh.radius)) ? INFINITY : d.z_max;
+    d.theta_min = d.theta_max = 0.0f;  // k_shape_angles
+    d.phi_max = shape_phi_max(sh);
+    d.inner_radius = sh.type == PBRT_SHAPE_DISK ? sh.inner_radius : 0.0f;
+    // Transform::swaps_handedness (transform.rs): the upper 3x3's determinant is negative
+    const float* m = sh.to_world;
+    const float det = m[0] * (m[5] * m[10] - m[6] * m[9]) - m[1] * (m[4] * m[10] - m[6] * m[8]) + m[2] * (m[4] * m[9] - m[5] * m[8]);
+    const bool reverse = sh.reverse_orientation != 0;
+    d.flags = sh.type | ((reverse != (det < 0.0f)) ? pb::kShapeFlipNormal : 0) | (reverse ? pb::kShapeReverse : 0);
+    return d;
+}
+namespace pb {
+// Sphere::new (sphere.rs:222-223): theta_min = acos(clamp(z_min / radius, -1, 1)), theta_max likewise, with the device's acos
+__global__ void k_shape_angles(DevShape* shapes, int n) {
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float r = shapes[i].radius;
+    shapes[i].theta_min = det_acos(clampf(shapes[i].z_min / r, -1.0f, 1.0f));
+    shapes[i].theta_max = det_acos(clampf(shapes[i].z_max / r, -1.0f, 1.0f));
+}
+}  // namespace pb
+
 static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_t n_verts, const int32_t* indices,
                              int32_t n_tris, const int32_t* tri_material, const PbrtMaterial* materials,
                              int32_t n_materials, const int32_t* tri_light, const PbrtLight* lights, int32_t n_lights,
@@ -614,12 +708,16 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
     if (n_lights < 0 || (n_lights > 0 && !lights)) return fail("bad light table");
     for (int64_t i = 0; i < 3 * (int64_t)n_tris; ++i)
         if (indices[i] < 0 || indices[i] >= n_verts) return fail("vertex index out of range");
-    const int32_t n_prims = n_tris + sa.n;
+    const int32_t n_prims = n_tris + sa.n + sa.n_shapes;
     if (sa.n < 0 || (sa.n > 0 && (!sa.spheres || dt || ia.n_instances > 0))) return fail("bad sphere arguments");
     for (int32_t i = 0; i < sa.n; ++i) {
         if (!(sa.spheres[4 * i + 3] > 0.0f)) return fail("sphere radius must be positive");
         if (sa.material && (sa.material[i] < 0 || sa.material[i] >= n_materials)) return fail("sphere material out of range");
         if (sa.light && (sa.light[i] < -1 || sa.light[i] >= n_lights)) return fail("sphere light out of range");
+    }
+    if (sa.n_shapes < 0 || (sa.n_shapes > 0 && (!sa.shapes || sa.n > 0 || dt || ia.n_instances > 0))) return fail("bad shape arguments");
+    for (int32_t i = 0; i < sa.n_shapes; ++i) {
+        if (const char* why = shape_invalid(sa.shapes[i], n_materials, n_lights)) return fail(why);
     }
     for (int32_t i = 0; i < n_prims && !dt; ++i)
         if (prim_order[i] < 0 || prim_order[i] >= n_prims) return fail("prim_order entry out of range");
@@ -633,7 +731,7 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
     for (int32_t i = 0; i < n_lights; ++i) {
         if (lights[i].type < PBRT_LIGHT_DIFFUSE_AREA || lights[i].type > PBRT_LIGHT_DISTANT) return fail("unknown light type");
         if (lights[i].type == PBRT_LIGHT_DIFFUSE_AREA &&
-            (lights[i].prim < 0 || lights[i].prim >= (ia.n_instances > 0 ? ia.n_world_tris : n_tris + sa.n)))
+            (lights[i].prim < 0 || lights[i].prim >= (ia.n_instances > 0 ? ia.n_world_tris : n_prims)))
             return fail("area light primitive out of range");
     }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -706,6 +804,14 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
             return fail("prim_order is not a permutation");
         }
         prim_slot[prim] = slot;
+        if (prim >= n_tris && sa.n_shapes > 0) {  // shape record: - | - | (row of DevBVH::shapes, prim, material, kPrimSphere)
+            const PbrtShape& sh = sa.shapes[prim - n_tris];
+            float* t = &tris[(size_t)slot * 12];
+            for (int k = 0; k < 8; ++k) t[k] = 0.0f;
+            int32_t meta[4] = {prim - n_tris, prim, sh.material, (sh.light + 1) | kPrimSphere};
+            std::memcpy(t + 8, meta, 16);
+            continue;
+        }
         if (prim >= n_tris) {  // sphere record: (centre.xyz, radius) | - | (-, prim, material, kPrimSphere)
             const float* sp = sa.spheres + 4 * (size_t)(prim - n_tris);
             float* t = &tris[(size_t)slot * 12];
@@ -763,7 +869,9 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
         if (l.type == PBRT_LIGHT_DIFFUSE_AREA) {
             int32_t prim = lights[i].prim + (instanced ? ia.world_tri_offset : 0);  // two-level: prim counts the world-space triangles
             l.slot = dt ? dt->light_slot[i] : prim_slot[prim];
-            if (prim >= n_tris) {
+            if (prim >= n_tris && sa.n_shapes > 0) {
+                l.area = shape_area(sa.shapes[prim - n_tris]);
+            } else if (prim >= n_tris) {
                 float r = sa.spheres[4 * (size_t)(prim - n_tris) + 3];
                 l.area = (360.0f * (kPi / 180.0f)) * r * (r - (-r));  // Sphere::area (sphere.rs:99-101)
             } else {
@@ -826,7 +934,17 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
     d.bvh.root_ref = top.root_ref;
     d.bvh.count_bits = top.count_bits;
     d.bvh.n_slots = n_prims;
-    d.bvh.has_spheres = sa.n > 0 ? 1 : 0;
+    d.bvh.has_spheres = sa.n_shapes > 0 ? 2 : (sa.n > 0 ? 1 : 0);
+    if (sa.n_shapes > 0) {
+        std::vector<DevShape> rows(sa.n_shapes);
+        for (int32_t i = 0; i < sa.n_shapes; ++i) rows[i] = shape_row(sa.shapes[i]);
+        DevShape* d_rows = dev_upload(s, rows.data(), rows.size(), &ok);
+        if (ok) {  // theta_min / theta_max with the kernels' own acos
+            hipLaunchKernelGGL(k_shape_angles, dim3((sa.n_shapes + 63) / 64), dim3(64), 0, ctx->stream, d_rows, sa.n_shapes);
+            ok = hip_ok(ctx, hipGetLastError(), "k_shape_angles") && hip_ok(ctx, hipStreamSynchronize(ctx->stream), "k_shape_angles");
+        }
+        d.bvh.shapes = d_rows;
+    }
     d.bvh.instanced = instanced ? 1 : 0;
     if (instanced) {
         d.bvh.blas_count_bits = obj.count_bits;
@@ -878,6 +996,8 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
     {
         if (ctx->wide_build == PBRT_WIDE_BUILD_NONE) {
             s->wide_reason = "disabled by PBRT_WIDE_BUILD_NONE";
+        } else if (sa.n_shapes > 0) {
+            s->wide_reason = "scene with shapes";
         } else if (sa.n > 0) {
             s->wide_reason = "scene with spheres";
         } else if (dt && dt->wide.n_records >= 0) {
@@ -1532,6 +1652,15 @@ __global__ void __launch_bounds__(kTraceBlock, (COUNT || SPH) ? 4 : (INST ? PB_I
                                                         blockIdx.x * kTraceBlock + threadIdx.x, counters);
 }
 
+// scenes with general quadric shapes (shapes_quadric.h): single level, the leaf loop dispatches on the shape table
+template <bool ANY, bool COUNT>
+__global__ void __launch_bounds__(kTraceBlock, 4)
+    k_intersect_batch_shapes(DevBVH bvh, BatchRayIO<ANY> io, unsigned int* work_counter, unsigned long long* counters) {
+    __shared__ uint2 lds_stack[kStackLds * kTraceBlock];
+    trace_persistent<BatchRayIO<ANY>, COUNT, 0, false, true>(bvh, io, work_counter, lds_stack + threadIdx.x,
+                                                             blockIdx.x * kTraceBlock + threadIdx.x, counters);
+}
+
 // the binary records without a stack (trace_stackless.h)
 template <bool ANY>
 __global__ void __launch_bounds__(kTraceBlock, PB_STACKLESS_WAVES)
@@ -1608,6 +1737,11 @@ static int launch_batch(PbrtHipScene* s, const PbrtRay* d_rays, int64_t n, PbrtH
                 if (count_wide) PB_LAUNCH_WIDE(true, 0); else PB_LAUNCH_WIDE(false, 0);
                 PB_LAUNCH_SPECIAL(0);
             }
+        } else if (s->d.bvh.has_spheres == 2) {  // general shapes; single-level scenes only (checked at creation)
+            if (count_ref)
+                hipLaunchKernelGGL((k_intersect_batch_shapes<ANY, true>), grid, block, 0, ctx->stream, s->d.bvh, io, ctx->d_work_counter, ctx->d_counters);
+            else
+                hipLaunchKernelGGL((k_intersect_batch_shapes<ANY, false>), grid, block, 0, ctx->stream, s->d.bvh, io, ctx->d_work_counter, ctx->d_counters);
         } else if (s->d.bvh.has_spheres) {  // single-level scenes only (checked at creation)
             if (count_ref) PB_LAUNCH_BINARY(true, 0, true); else PB_LAUNCH_BINARY(false, 0, true);
         } else if (inst == 2) {

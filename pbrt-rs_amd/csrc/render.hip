@@ -980,7 +980,10 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
             HIP_TRY(ctx, hipMalloc(&p, floats * sizeof(float)));
             s->allocs.push_back(p);
             for (int i = 0; i < 3; ++i) sc.n_voxel[i] = s->spatial_voxels[i];
-            hipLaunchKernelGGL(k_spatial_light_tables, dim3((unsigned)((n_voxels + 63) / 64)), dim3(64), 0, st, sc, (float*)p);
+            if (s->d.bvh.has_spheres == 2)
+                hipLaunchKernelGGL(k_spatial_light_tables_shapes, dim3((unsigned)((n_voxels + 63) / 64)), dim3(64), 0, st, sc, (float*)p);
+            else
+                hipLaunchKernelGGL(k_spatial_light_tables, dim3((unsigned)((n_voxels + 63) / 64)), dim3(64), 0, st, sc, (float*)p);
             HIP_TRY(ctx, hipGetLastError());
             HIP_TRY(ctx, hipStreamSynchronize(st));
             s->d_spatial = (float*)p;
@@ -1119,6 +1122,11 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
                             if (count_wide) PB_LAUNCH_WIDE(true, 0); else PB_LAUNCH_WIDE(false, 0);
                             PB_LAUNCH_SPECIAL(0);
                         }
+                    } else if (s->d.bvh.has_spheres == 2) {
+                        if (count_ref)
+                            hipLaunchKernelGGL(k_trace_shapes<true>, grid, block, 0, st, s->d.bvh, ps, trace_queue, n_trace, ctx->d_work_counter, ctx->d_counters, segments);
+                        else
+                            hipLaunchKernelGGL(k_trace_shapes<false>, grid, block, 0, st, s->d.bvh, ps, trace_queue, n_trace, ctx->d_work_counter, ctx->d_counters, segments);
                     } else if (s->d.bvh.has_spheres) {
                         if (count_ref) PB_LAUNCH_BINARY(true, 0, true); else PB_LAUNCH_BINARY(false, 0, true);
                     } else if (inst == 2) {
@@ -1144,7 +1152,14 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
                 dim3 sg((n_shade + 255) / 256), sb(256);
                 // a plastic or metal material in the scene's table selects the level-1 instantiations, a row of
                 // pbrt_hip_scene_set_material the level-2 ones, a Disney row the level-3 ones (AO reads no BSDF)
-                if (rp.integrator == PBRT_INTEGRATOR_DIRECT && s->disney)
+                const bool shapes = s->d.bvh.has_spheres == 2;  // general quadric shapes: their own builds (wf_direct.h: kDirectShapes)
+                if (shapes && rp.integrator == PBRT_INTEGRATOR_DIRECT)
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, 3 + kDirectShapes>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                else if (shapes && rp.integrator == PBRT_INTEGRATOR_WHITTED)
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, 3 + kDirectShapes>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                else if (shapes)
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_AO, kDirectShapes>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                else if (rp.integrator == PBRT_INTEGRATOR_DIRECT && s->disney)
                     hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, 3>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
                 else if (rp.integrator == PBRT_INTEGRATOR_WHITTED && s->disney)
                     hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, 3>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
@@ -1178,7 +1193,12 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
                     order = shade_sorted;
                 }
                 const dim3 sg((n_shade + 255) / 256), sb(256);
-                if (bin_shade && wavefront >= 1 && s->disney)
+                const bool shapes = s->d.bvh.has_spheres == 2;  // general quadric shapes: their own builds (wf_path.h)
+                if (shapes && bin_shade && wavefront >= 1)
+                    hipLaunchKernelGGL(k_shade_shapes<true>, sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
+                else if (shapes)
+                    hipLaunchKernelGGL(k_shade_shapes<false>, sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
+                else if (bin_shade && wavefront >= 1 && s->disney)
                     hipLaunchKernelGGL((k_shade<true, 3>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
                 else if (bin_shade && wavefront >= 1 && s->bxdfs)
                     hipLaunchKernelGGL((k_shade<true, 2>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);

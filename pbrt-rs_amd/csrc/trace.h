@@ -22,6 +22,8 @@
 
 namespace pb {
 
+struct DevShape;  // shapes_quadric.h
+
 struct DevBVH {
     const float4* __restrict__ inodes;  // 4 x float4 per interior node
     const float4* __restrict__ tris;    // 3 x float4 per leaf slot
@@ -49,7 +51,9 @@ struct DevBVH {
     // (n0.xyz, n1.x) (n1.yz, n2.xy) (n2.z, s0.xyz) (s1.xyz, s2.x) (s2.yz, uv0.xy) (uv1.xy, uv2.xy); null = none
     const float4* __restrict__ tri_shading;
     int has_normals, has_tangents, has_uvs;
-    int has_spheres;  // some leaf slots hold spheres (kPrimSphere): the SPH kernels are launched
+    int has_spheres;  // some leaf slots hold spheres (kPrimSphere): the SPH kernels are launched; 2: the slots hold general
+                      // shapes (shapes_quadric.h) and the SHP kernels are launched
+    const DevShape* __restrict__ shapes;  // has_spheres == 2: the shape table, a shape's leaf slot names its row (third float4, .x)
 };
 
 // waves per SIMD requested for the traversal kernels (occupancy sweep: DESIGN.md section 4)
@@ -81,7 +85,8 @@ struct TravHit {
 
 // tri.z.w of the third float4 carries flags in the top bits of `light`: see scene.h
 constexpr int kTriDegenerate = 1 << 30;  // Triangle::intersect returns false (triangle.rs:212-216)
-constexpr int kPrimSphere = 1 << 29;     // the slot holds a Sphere: (centre.xyz, radius) in the first float4 (shapes/sphere.rs)
+constexpr int kPrimSphere = 1 << 29;     // the slot holds a Sphere: (centre.xyz, radius) in the first float4 (shapes/sphere.rs);
+                                         // in a scene with general shapes (DevBVH::has_spheres == 2): a row of DevBVH::shapes
 constexpr int kPrimLightMask = 0x1fffffff;  // light index + 1
 
 PB_DEV bool slab_test(float bx0, float bx1, float by0, float by1, float bz0, float bz1, const TravRay& r, float idx,
@@ -261,6 +266,24 @@ PB_DEV EFloat ef_div(EFloat a, EFloat b) {
 }
 PB_DEV EFloat ef_mulf(EFloat a, float f) { return ef_mul(a, ef_make(f, 0.0f)); }
 
+// EFloat::quadratic (efloat.rs:64-87): false = no real roots, else t0 <= t1
+PB_DEV bool ef_quadratic(EFloat a, EFloat b, EFloat c, EFloat* t0_out, EFloat* t1_out) {
+    double discrim = (double)b.v * (double)b.v - 4.0 * (double)a.v * (double)c.v;
+    if (discrim < 0.0) return false;
+    double root = __builtin_sqrt(discrim);
+    EFloat froot = ef_make((float)root, kMachineEpsilon * (float)root);
+    EFloat qq = (b.v < 0.0f) ? ef_mulf(ef_sub(b, froot), -0.5f) : ef_mulf(ef_add(b, froot), -0.5f);
+    EFloat t0 = ef_div(qq, a), t1 = ef_div(c, qq);
+    if (t0.v > t1.v) {
+        EFloat tmp = t0;
+        t0 = t1;
+        t1 = tmp;
+    }
+    *t0_out = t0;
+    *t1_out = t1;
+    return true;
+}
+
 // The object-space ray of Sphere::intersect_test (geometry.rs:1077-1137 through translate(-centre)) with its
 // origin / direction error bounds.
 struct SphereRay {
@@ -304,18 +327,8 @@ PB_DEV bool sphere_test(float cx, float cy, float cz, float radius, const TravRa
     EFloat b = ef_mulf(ef_add(ef_add(ef_mul(dx, ox), ef_mul(dy, oy)), ef_mul(dz, oz)), 2.0f);
     EFloat rr = ef_make(radius, 0.0f);
     EFloat c = ef_sub(ef_add(ef_add(ef_mul(ox, ox), ef_mul(oy, oy)), ef_mul(oz, oz)), ef_mul(rr, rr));
-    // EFloat::quadratic (efloat.rs:64-87)
-    double discrim = (double)b.v * (double)b.v - 4.0 * (double)a.v * (double)c.v;
-    if (discrim < 0.0) return false;
-    double root = __builtin_sqrt(discrim);
-    EFloat froot = ef_make((float)root, kMachineEpsilon * (float)root);
-    EFloat qq = (b.v < 0.0f) ? ef_mulf(ef_sub(b, froot), -0.5f) : ef_mulf(ef_add(b, froot), -0.5f);
-    EFloat t0 = ef_div(qq, a), t1 = ef_div(c, qq);
-    if (t0.v > t1.v) {
-        EFloat tmp = t0;
-        t0 = t1;
-        t1 = tmp;
-    }
+    EFloat t0, t1;
+    if (!ef_quadratic(a, b, c, &t0, &t1)) return false;
     const float phi_max = 360.0f * (kPi / 180.0f);
     for (int k = 0; k < 2; ++k) {  // the hit-selection loop of sphere.rs:259-281
         EFloat t = k == 0 ? t0 : t1;
@@ -352,3 +365,5 @@ PB_DEV void count_flush(unsigned long long* counters, uint32_t n_node, uint32_t 
 }
 
 }  // namespace pb
+
+#include "shapes_quadric.h"

@@ -16,6 +16,8 @@
 // Traversal state lives in registers, the stack in LDS ([entry][lane]) with a global spill slab.
 //
 // SPH = true: leaf slots may hold spheres (kPrimSphere; BASELINE config 1).
+// SHP = true: leaf slots may hold general quadric shapes (kPrimSphere in a scene whose DevBVH::has_spheres is 2: a row of
+// DevBVH::shapes, shapes_quadric.h); never together with SPH.
 // COUNT = true is the instrumented variant: it also counts the box tests (bvh.rs:841-842),
 // triangle tests (triangle.rs:74) and instance entries (primitive.rs:136) that the REFERENCE's
 // loops perform for the same rays. The reference pushes the far child untested and tests it when
@@ -104,7 +106,7 @@ PB_DEV bool root_box_test(const LaneState& s, const float* mn, const float* mx) 
 // rides in the kernel arguments); 2 = the general top level (several objects, world-space triangles beside the instances).
 // A template value rather than a run-time flag: with the general code compiled in, the 96-register build of the
 // single-object kernel spilled 100 B instead of 56 B and config 5 lost 15 %.
-template <class IO, bool COUNT, int INST, bool SPH = false>
+template <class IO, bool COUNT, int INST, bool SPH = false, bool SHP = false>
 PB_DEV void trace_persistent(const DevBVH& bvh, const IO& io, unsigned int* __restrict__ work_counter,
                              uint2* lds_stack, int spill_lane, unsigned long long* counters) {
     const uint32_t n = io.n();
@@ -435,6 +437,13 @@ PB_DEV void trace_persistent(const DevBVH& bvh, const IO& io, unsigned int* __re
                         float phi;
                         hit = sphere_test(p0.x, p0.y, p0.z, p1.x, s.r, s.tmax, &t, &ph, &phi);
                         b0 = ph.x;  // a sphere's hit record carries the refined object-space hit point
+                        b1 = ph.y;
+                        b2 = ph.z;
+                    } else if (SHP && (flags & kPrimSphere)) {
+                        // Sphere / Disk / Cylinder::intersect_test under the shape's own transform (shapes_quadric.h)
+                        V3 ph;
+                        hit = shape_test(bvh.shapes[__float_as_int(p2.z)], s.r, s.tmax, &t, &ph);
+                        b0 = ph.x;
                         b1 = ph.y;
                         b2 = ph.z;
                     } else {

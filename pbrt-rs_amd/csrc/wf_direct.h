@@ -29,9 +29,15 @@ struct DirectState {
 // LEVEL as k_shade's: 1 (GLOSSY), the scene holds plastic or metal: the non-specular BSDF is the general one of
 // wf_microfacet.h (matte included); 2, a row of pbrt_hip_scene_set_material: that of wf_bxdfs.h; 3, a Disney row: that of wf_disney.h.
 // The glossy direct-lighting instantiations run one wave per SIMD: at two level 1 spills 19 registers.
-template <int MODE, int LEVEL>
-__global__ void __launch_bounds__(256, (LEVEL >= 1 && MODE == PBRT_INTEGRATOR_DIRECT) ? 1 : PB_DIRECT_WAVES) k_shade_direct(ShadeConsts sc, PathState ps, DirectState ds, Queues qin,
+// LEVEL_SHP = LEVEL, + 4 in the builds for scenes with general quadric shapes (SHP as shade_bounce's, wf_path.h): <DIRECT, 7>,
+// <WHITTED, 7> and <AO, 4>, on the level-3 BSDF set, which serves every material table. (A value of the existing parameter, not a
+// body shared through a wrapper: that moved the registers of three of the instantiations for the other scenes.)
+constexpr int kDirectShapes = 4;
+template <int MODE, int LEVEL_SHP>
+__global__ void __launch_bounds__(256, ((LEVEL_SHP & 3) >= 1 && MODE == PBRT_INTEGRATOR_DIRECT) ? 1 : PB_DIRECT_WAVES) k_shade_direct(ShadeConsts sc, PathState ps, DirectState ds, Queues qin,
                                                         Queues qout, PassParams pp, TileList tiles, uint32_t n_in) {
+    constexpr int LEVEL = LEVEL_SHP & 3;
+    constexpr bool SHP = (LEVEL_SHP & kDirectShapes) != 0;
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool active = i < n_in;
     uint32_t p = active ? qin.shade[i] : 0u;
@@ -74,7 +80,7 @@ __global__ void __launch_bounds__(256, (LEVEL >= 1 && MODE == PBRT_INTEGRATOR_DI
         if (flags & (PF_NEE_SHADOW | PF_NEE_MIS)) {
             float pick_pdf;
             V3 beta_v;
-            V3 ld = estimate_direct_resolve(sc, ps, p, flags, &pick_pdf, &beta_v);
+            V3 ld = estimate_direct_resolve<SHP>(sc, ps, p, flags, &pick_pdf, &beta_v);
             flags &= ~(PF_NEE_SHADOW | PF_NEE_MIS);
             if (sample_all) {
                 ld_acc = ld_acc + ld;
@@ -111,7 +117,7 @@ __global__ void __launch_bounds__(256, (LEVEL >= 1 && MODE == PBRT_INTEGRATOR_DI
             rd = V3{r0.w, r1.x, r1.y};
             float4 h0 = ps.hit[hbase];
             int hslot = __float_as_int(h0.x);
-            sf = surface_from_hit(sc.bvh, hslot, hit_instance(ps, hbase), h0.y, h0.z, h0.w, rd);
+            sf = surface_from_hit<SHP>(sc.bvh, hslot, hit_instance(ps, hbase), h0.y, h0.z, h0.w, rd);
             mat = sc.materials[sf.material];
             fr = make_frame(sf);
             kd = V3{mat.kd[0], mat.kd[1], mat.kd[2]};
@@ -204,7 +210,7 @@ __global__ void __launch_bounds__(256, (LEVEL >= 1 && MODE == PBRT_INTEGRATOR_DI
                 stage += 1;
                 V3 wi, li, p1, p1_err, p1_n;
                 float pdf;
-                light_sample_li(sc, sf, lt, ul0, ul1, &wi, &pdf, &li, &p1, &p1_err, &p1_n);
+                light_sample_li<SHP>(sc, sf, lt, ul0, ul1, &wi, &pdf, &li, &p1, &p1_err, &p1_n);
                 if (is_black(li) || pdf == 0.0f) continue;
                 V3 f = V3{0.0f, 0.0f, 0.0f};
                 float spdf;
@@ -255,10 +261,10 @@ __global__ void __launch_bounds__(256, (LEVEL >= 1 && MODE == PBRT_INTEGRATOR_DI
                 if (GLOSSY) {
                     typename LevelBsdf<LEVEL>::type nsb;
                     load_bsdf(sc, sf.material, sc.materials[sf.material], &nsb);
-                    nee_flags = estimate_direct_emit(sc, RecordSink{ps, p}, sf, fr, nsb.n > 0, nsb, light_num, ul0, ul1, us0, us1, pick_pdf, T);
+                    nee_flags = estimate_direct_emit<SHP>(sc, RecordSink{ps, p}, sf, fr, nsb.n > 0, nsb, light_num, ul0, ul1, us0, us1, pick_pdf, T);
                 } else {
                     bool matte = (mat.type == PBRT_MAT_MATTE) && !is_black(kd);
-                    nee_flags = estimate_direct_emit(sc, RecordSink{ps, p}, sf, fr, matte, MatteBsdf{kd}, light_num, ul0, ul1, us0, us1, pick_pdf, T);
+                    nee_flags = estimate_direct_emit<SHP>(sc, RecordSink{ps, p}, sf, fr, matte, MatteBsdf{kd}, light_num, ul0, ul1, us0, us1, pick_pdf, T);
                 }
                 stage += 1;
                 if (nee_flags) {
@@ -343,5 +349,4 @@ __global__ void __launch_bounds__(256, (LEVEL >= 1 && MODE == PBRT_INTEGRATOR_DI
     __shared__ BlockAppend sh;
     block_append(sh, qout, p, emit_cont, emit_mis, emit_shadow, emit_cont || emit_mis || emit_shadow, 0, mis_bool);
 }
-
 }  // namespace pb

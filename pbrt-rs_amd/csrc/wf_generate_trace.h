@@ -214,6 +214,17 @@ __global__ void __launch_bounds__(kTraceBlock, (COUNT || SPH) ? 4 : (INST ? PB_I
                                                   blockIdx.x * kTraceBlock + threadIdx.x, counters);
 }
 
+// scenes with general quadric shapes (shapes_quadric.h; DevBVH::has_spheres == 2)
+template <bool COUNT>
+__global__ void __launch_bounds__(kTraceBlock, 4)
+    k_trace_shapes(DevBVH bvh, PathState ps, const uint32_t* __restrict__ queue, uint32_t n, unsigned int* work_counter,
+                   unsigned long long* counters, int segments) {
+    __shared__ uint2 lds_stack[kStackLds * kTraceBlock];
+    WavefrontRayIO<false> io{ps, queue, n, segments};
+    trace_persistent<WavefrontRayIO<false>, COUNT, 0, false, true>(bvh, io, work_counter, lds_stack + threadIdx.x,
+                                                                   blockIdx.x * kTraceBlock + threadIdx.x, counters);
+}
+
 // the binary records without a stack (trace_stackless.h; PBRT_TRAVERSAL_STACKLESS)
 __global__ void __launch_bounds__(kTraceBlock, PB_STACKLESS_WAVES)
     k_trace_stackless(DevBVH bvh, PathState ps, const uint32_t* __restrict__ queue, uint32_t n, unsigned int* work_counter, int segments) {

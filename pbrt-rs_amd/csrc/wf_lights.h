@@ -79,8 +79,147 @@ PB_DEV void sphere_light_sample(float cx, float cy, float cz, float radius, cons
     *pdf_o = 1.0f / (2.0f * kPi * (1.0f - cos_theta_max));
 }
 
+// ---- a row of the shape table (shapes_quadric.h) as the shape of a DiffuseAreaLight. Full sphere: Sphere::sample / sample2 /
+// pdf2 (sphere.rs:103-192) as above with p_centre = object_to_world * (0, 0, 0); disk: Disk::sample (disk.rs:133-149); cylinder:
+// pbrt-v3's Cylinder::Sample (unimplemented in the reference, D81); disk and cylinder through the Shape trait's sample2 / pdf2
+// (shape.rs:38-69). `area` = Shape::area, an object-space quantity as in pbrt-v3 (DevLight::area, set at creation). ----
+PB_DEV V3 shape_point_to_world(const float* w, V3 p, V3 pe, V3* err) {  // Point3f::from((t, p, p_error, &mut error))
+    const float g3 = kGamma3;
+    err->x = (g3 + 1.0f) * (__builtin_fabsf(w[0] * pe.x) + __builtin_fabsf(w[1] * pe.y) + __builtin_fabsf(w[2] * pe.z)) +
+             g3 * (__builtin_fabsf(w[0] * p.x) + __builtin_fabsf(w[1] * p.y) + __builtin_fabsf(w[2] * p.z) + __builtin_fabsf(w[3]));
+    err->y = (g3 + 1.0f) * (__builtin_fabsf(w[4] * pe.x) + __builtin_fabsf(w[5] * pe.y) + __builtin_fabsf(w[6] * pe.z)) +
+             g3 * (__builtin_fabsf(w[4] * p.x) + __builtin_fabsf(w[5] * p.y) + __builtin_fabsf(w[6] * p.z) + __builtin_fabsf(w[7]));
+    err->z = (g3 + 1.0f) * (__builtin_fabsf(w[8] * pe.x) + __builtin_fabsf(w[9] * pe.y) + __builtin_fabsf(w[10] * pe.z)) +
+             g3 * (__builtin_fabsf(w[8] * p.x) + __builtin_fabsf(w[9] * p.y) + __builtin_fabsf(w[10] * p.z) + __builtin_fabsf(w[11]));
+    return V3{w[0] * p.x + w[1] * p.y + w[2] * p.z + w[3], w[4] * p.x + w[5] * p.y + w[6] * p.z + w[7],
+              w[8] * p.x + w[9] * p.y + w[10] * p.z + w[11]};
+}
+PB_DEV V3 shape_normal_to_world(const float* o, V3 v) {  // Transform * Normal3: the transpose of world_to_object's upper 3x3
+    return V3{o[0] * v.x + o[4] * v.y + o[8] * v.z, o[1] * v.x + o[5] * v.y + o[9] * v.z, o[2] * v.x + o[6] * v.y + o[10] * v.z};
+}
+PB_DEV V3 shape_centre(const DevShape& sh) {
+    const float* w = sh.o2w;
+    return V3{w[0] * 0.0f + w[1] * 0.0f + w[2] * 0.0f + w[3], w[4] * 0.0f + w[5] * 0.0f + w[6] * 0.0f + w[7],
+              w[8] * 0.0f + w[9] * 0.0f + w[10] * 0.0f + w[11]};
+}
+// Shape::sample2: point, error, normal on the shape and the solid-angle pdf from `sf`
+PB_DEV void shape_light_sample(const DevShape& sh, float area, const Surf& sf, float u0, float u1, V3* p_o, V3* err_o, V3* n_o,
+                               float* pdf_o) {
+    const int type = sh.flags & kShapeTypeMask;
+    const float radius = sh.radius;
+    float px, py, pz, nx, ny, nz, eg;  // object-space point and normal, the gamma of its error bound (scalars: see make_surface_shape)
+    if (type == kShapeSphere) {
+        V3 pc = shape_centre(sh);
+        V3 p_origin = offset_ray_origin(sf.p, sf.p_error, sf.n, pc - sf.p);
+        if (!(len2(p_origin - pc) <= radius * radius)) {
+            // outside: uniform sampling of the cone the sphere subtends (sphere.rs:140-178)
+            float dc = length(sf.p - pc);
+            float inv_dc = 1.0f / dc;
+            V3 wc = (pc - sf.p) * inv_dc, wc_x, wc_y;
+            coordinate_system(wc, &wc_x, &wc_y);
+            float sin_theta_max = radius * inv_dc;
+            float sin_theta_max2 = sin_theta_max * sin_theta_max;
+            float inv_sin_theta_max = 1.0f / sin_theta_max;
+            float cos_theta_max = __builtin_sqrtf(fmaxr(1.0f - sin_theta_max2, 0.0f));
+            float cos_theta = (cos_theta_max - 1.0f) * u0 + 1.0f;
+            float sin_theta2 = 1.0f - cos_theta * cos_theta;
+            if (sin_theta_max2 < 0.00068523f) {
+                sin_theta2 = sin_theta_max2 * u0;
+                cos_theta = __builtin_sqrtf(1.0f - sin_theta2);
+            }
+            float cos_alpha = sin_theta2 * inv_sin_theta_max +
+                              cos_theta * __builtin_sqrtf(fmaxr(1.0f - sin_theta2 * inv_sin_theta_max * inv_sin_theta_max, 0.0f));
+            float sin_alpha = __builtin_sqrtf(fmaxr(1.0f - cos_alpha * cos_alpha, 0.0f));
+            float sp, cp;
+            det_sincos(u1 * 2.0f * kPi, &sp, &cp);
+            V3 n_world = (-wc_x) * sin_alpha * cp + (-wc_y) * sin_alpha * sp + (-wc) * cos_alpha;
+            V3 p_world = pc + n_world * radius;
+            *p_o = p_world;
+            *err_o = vabs(p_world) * kGamma5;
+            *n_o = (sh.flags & kShapeReverse) ? -n_world : n_world;
+            *pdf_o = 1.0f / (2.0f * kPi * (1.0f - cos_theta_max));
+            return;
+        }
+        // inside: Sphere::sample (sphere.rs:103-121), area pdf converted to solid angle below
+        float z = 1.0f - 2.0f * u0;
+        float rr = __builtin_sqrtf(fmaxr(1.0f - z * z, 0.0f));
+        float sp, cp;
+        det_sincos(2.0f * kPi * u1, &sp, &cp);
+        nx = (rr * cp) * radius;
+        ny = (rr * sp) * radius;
+        nz = z * radius;
+        float scale = radius / length(V3{nx, ny, nz});
+        px = nx * scale;
+        py = ny * scale;
+        pz = nz * scale;
+        eg = kGamma5;
+    } else if (type == kShapeDisk) {
+        float dx, dy;
+        concentric_sample_disk(u0, u1, &dx, &dy);
+        px = dx * radius;
+        py = dy * radius;
+        pz = sh.z_min;
+        nx = 0.0f;
+        ny = 0.0f;
+        nz = 1.0f;
+        eg = 0.0f;
+    } else {
+        float sp, cp;
+        det_sincos(u1 * sh.phi_max, &sp, &cp);
+        px = radius * cp;
+        py = radius * sp;
+        pz = (1.0f - u0) * sh.z_min + u0 * sh.z_max;
+        nx = px;
+        ny = py;
+        nz = 0.0f;
+        eg = kGamma3;
+    }
+    const V3 obj = V3{px, py, pz};
+    // error bound: gamma(5) |p| (sphere), 0 (disk), gamma(3) |(x, y, 0)| (cylinder)
+    const V3 oe = V3{__builtin_fabsf(px) * eg, __builtin_fabsf(py) * eg, type == kShapeSphere ? __builtin_fabsf(pz) * eg : 0.0f};
+    V3 n = normalize(shape_normal_to_world(sh.w2o, V3{nx, ny, nz}));
+    if (sh.flags & kShapeReverse) n = -n;
+    V3 err;
+    V3 p = shape_point_to_world(sh.o2w, obj, oe, &err);
+    float pdf = 1.0f / area;
+    V3 wi = p - sf.p;
+    if (len2(wi) == 0.0f) {
+        pdf = 0.0f;
+    } else {
+        wi = normalize(wi);
+        pdf *= len2(sf.p - p) / absdot(n, -wi);
+    }
+    if (__builtin_isinf(pdf)) pdf = 0.0f;
+    *p_o = p;
+    *err_o = err;
+    *n_o = n;
+    *pdf_o = pdf;
+}
+// Shape::pdf2 of a direction wi from `sf` (shape.rs:54-69; the full sphere: Sphere::pdf2, sphere.rs:181-192)
+PB_DEV float shape_light_pdf(const DevBVH& bvh, int slot, const DevShape& sh, float area, const Surf& sf, V3 wi) {
+    if ((sh.flags & kShapeTypeMask) == kShapeSphere) {
+        V3 pc = shape_centre(sh);
+        V3 p_origin = offset_ray_origin(sf.p, sf.p_error, sf.n, pc - sf.p);
+        if (!(len2(p_origin - pc) < sh.radius * sh.radius)) {
+            float sin_theta_max2 = sh.radius * sh.radius / len2(sf.p - pc);
+            float cos_theta_max = __builtin_sqrtf(fmaxr(1.0f - sin_theta_max2, 0.0f));
+            return 1.0f / (2.0f * kPi * (1.0f - cos_theta_max));
+        }
+    }
+    V3 o2 = offset_ray_origin(sf.p, sf.p_error, sf.n, wi);
+    TravRay rr{o2.x, o2.y, o2.z, wi.x, wi.y, wi.z, kInf};
+    float th;
+    V3 ph;
+    if (!shape_test(sh, rr, kInf, &th, &ph)) return 0.0f;
+    Surf hs = make_surface_shape(bvh, slot, ph, wi);
+    float lpdf = len2(sf.p - hs.p) / (absdot(hs.n, -wi) * area);
+    return __builtin_isinf(lpdf) ? 0.0f : lpdf;
+}
+
 // Light::sample_li (light.rs:35-42): DiffuseAreaLight (diffuse.rs:60-81 with Triangle::sample / Shape::sample2)
 // or InfiniteAreaLight (infinite.rs:96-129). Outputs the visibility tester's far point (p1, error, normal).
+// SHP: the scene may hold general shapes (see surface_from_hit).
+template <bool SHP = false>
 PB_DEV void light_sample_li(const ShadeConsts& sc, const Surf& sf, const DevLight& lt, float ul0, float ul1, V3* wi_o,
                             float* pdf_o, V3* li_o, V3* p1_o, V3* p1_err_o, V3* p1_n_o) {
     V3 wi = V3{0.0f, 0.0f, 0.0f};
@@ -88,11 +227,16 @@ PB_DEV void light_sample_li(const ShadeConsts& sc, const Surf& sf, const DevLigh
     V3 li = V3{0.0f, 0.0f, 0.0f};
     V3 p1 = V3{0.0f, 0.0f, 0.0f}, p1_err = V3{0.0f, 0.0f, 0.0f}, p1_n = V3{0.0f, 0.0f, 0.0f};
     V3 Lc = V3{lt.L[0], lt.L[1], lt.L[2]};
-    if (lt.type == PBRT_LIGHT_DIFFUSE_AREA && sc.bvh.has_spheres &&
+    if (lt.type == PBRT_LIGHT_DIFFUSE_AREA && (SHP || sc.bvh.has_spheres) &&
         (__float_as_int(sc.bvh.tris[3 * (size_t)lt.slot + 2].w) & kPrimSphere)) {
-        float4 rec = sc.bvh.tris[3 * (size_t)lt.slot];
         float pdf;
-        sphere_light_sample(rec.x, rec.y, rec.z, rec.w, sf, ul0, ul1, &p1, &p1_err, &p1_n, &pdf);
+        if (SHP) {
+            shape_light_sample(sc.bvh.shapes[__float_as_int(sc.bvh.tris[3 * (size_t)lt.slot + 2].x)], lt.area, sf, ul0, ul1, &p1,
+                               &p1_err, &p1_n, &pdf);
+        } else {
+            float4 rec = sc.bvh.tris[3 * (size_t)lt.slot];
+            sphere_light_sample(rec.x, rec.y, rec.z, rec.w, sf, ul0, ul1, &p1, &p1_err, &p1_n, &pdf);
+        }
         // DiffuseAreaLight::sample_li (diffuse.rs:60-81)
         if (pdf == 0.0f || len2(p1 - sf.p) == 0.0f) {
             light_pdf = 0.0f;
@@ -223,7 +367,8 @@ PB_DEV float radical_inverse_small(int base_index, uint32_t a) {  // lowdiscrepa
     const uint32_t primes[5] = {2u, 3u, 5u, 7u, 11u};
     return halton_radical_inverse(primes[base_index], nullptr, a);
 }
-__global__ void k_spatial_light_tables(ShadeConsts sc, float* __restrict__ table) {
+template <bool SHP>
+PB_DEV void spatial_light_tables(const ShadeConsts& sc, float* __restrict__ table) {
     size_t voxel = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     size_t n_voxels = (size_t)sc.n_voxel[0] * sc.n_voxel[1] * sc.n_voxel[2];
     if (voxel >= n_voxels) return;
@@ -253,7 +398,7 @@ __global__ void k_spatial_light_tables(ShadeConsts sc, float* __restrict__ table
             DevLight lt = sc.lights[j];
             V3 wi, li, p1, p1_err, p1_n;
             float pdf;
-            light_sample_li(sc, sf, lt, u0, u1, &wi, &pdf, &li, &p1, &p1_err, &p1_n);
+            light_sample_li<SHP>(sc, sf, lt, u0, u1, &wi, &pdf, &li, &p1, &p1_err, &p1_n);
             if (pdf > 0.0f) func[j] += (0.212671f * li.x + 0.715160f * li.y + 0.072169f * li.z) / pdf;
         }
     }
@@ -273,6 +418,8 @@ __global__ void k_spatial_light_tables(ShadeConsts sc, float* __restrict__ table
     }
     func[2 * n + 1] = func_int;
 }
+__global__ void k_spatial_light_tables(ShadeConsts sc, float* __restrict__ table) { spatial_light_tables<false>(sc, table); }
+__global__ void k_spatial_light_tables_shapes(ShadeConsts sc, float* __restrict__ table) { spatial_light_tables<true>(sc, table); }
 
 // estimate_direct (integrator.rs:136-266), first part: sample the light, evaluate the BSDF, sample the
 // BSDF, evaluate the light pdf. Writes the shadow ray (slot 2), the MIS ray (slot 1) and the pending
@@ -280,7 +427,7 @@ __global__ void k_spatial_light_tables(ShadeConsts sc, float* __restrict__ table
 // staging until the index is known); returns PF_NEE_* flags for the rays that must be traced. `nonspecular` = the
 // BSDF has a non-specular lobe, `bsdf` its lobes (MatteBsdf: matte only; NsBsdf: matte, plastic or metal; GenBsdf: any row of levels 0-2; DisneyBsdf: any); otherwise f == 0
 // and nothing is emitted.
-template <class Bsdf, class Sink>
+template <bool SHP = false, class Bsdf, class Sink>
 PB_DEV int estimate_direct_emit(const ShadeConsts& sc, const Sink& out, const Surf& sf, const Frame& fr,
                                 bool nonspecular, const Bsdf& bsdf, int light_num, float ul0, float ul1, float us0, float us1,
                                 float pick_pdf, V3 beta) {
@@ -289,7 +436,7 @@ PB_DEV int estimate_direct_emit(const ShadeConsts& sc, const Sink& out, const Su
     DevLight lt = sc.lights[light_num];
     V3 wi, li, p1, p1_err, p1_n;
     float light_pdf;
-    light_sample_li(sc, sf, lt, ul0, ul1, &wi, &light_pdf, &li, &p1, &p1_err, &p1_n);
+    light_sample_li<SHP>(sc, sf, lt, ul0, ul1, &wi, &light_pdf, &li, &p1, &p1_err, &p1_n);
     int nee_flags = 0;
     V3 A = V3{0.0f, 0.0f, 0.0f};
     if (light_pdf > 0.0f && !is_black(li)) {
@@ -322,7 +469,9 @@ PB_DEV int estimate_direct_emit(const ShadeConsts& sc, const Sink& out, const Su
     if (ok) f2 = f2 * absdot(wi2, fr.ns);
     if (ok && !is_black(f2) && spdf > 0.0f) {
         float lpdf;
-        if (lt.type == PBRT_LIGHT_DIFFUSE_AREA && sc.bvh.has_spheres &&
+        if (SHP && lt.type == PBRT_LIGHT_DIFFUSE_AREA && (__float_as_int(sc.bvh.tris[3 * (size_t)lt.slot + 2].w) & kPrimSphere)) {
+            lpdf = shape_light_pdf(sc.bvh, lt.slot, sc.bvh.shapes[__float_as_int(sc.bvh.tris[3 * (size_t)lt.slot + 2].x)], lt.area, sf, wi2);
+        } else if (lt.type == PBRT_LIGHT_DIFFUSE_AREA && sc.bvh.has_spheres &&
             (__float_as_int(sc.bvh.tris[3 * (size_t)lt.slot + 2].w) & kPrimSphere)) {
             // Sphere::pdf2 (sphere.rs:181-192)
             float4 rec = sc.bvh.tris[3 * (size_t)lt.slot];
@@ -397,6 +546,7 @@ PB_DEV int estimate_direct_emit(const ShadeConsts& sc, const Sink& out, const Su
 // estimate_direct, second part: combine the traced shadow / MIS results into Ld (before the division
 // by the light-pick pdf). Also returns the pick pdf and the throughput stored with the estimate. `rec` = the record index
 // of the path's rays, hits and pending terms (k_shade: its shade-queue position; k_shade_direct: the path's number).
+template <bool SHP = false>
 PB_DEV V3 estimate_direct_resolve(const ShadeConsts& sc, const PathState& ps, uint32_t rec, int flags, float* pick_pdf,
                                   V3* beta_at_vertex) {
     float4 na = ps.nee_a[rec], nf = ps.nee_f[rec], nb = ps.nee_b[rec];
@@ -419,7 +569,7 @@ PB_DEV V3 estimate_direct_resolve(const ShadeConsts& sc, const PathState& ps, ui
                 float4 r0 = ps.ray[ray_index(ps, rec, RS_MIS)], r1 = ps.ray[ray_index(ps, rec, RS_MIS) + 1];
                 V3 wi = V3{r0.w, r1.x, r1.y};
                 float4 hb = ps.hit[hit_index(ps, rec, RS_MIS)];
-                V3 n = tri_interaction_normal(sc.bvh, hslot, hb.y, hb.z, hb.w);
+                V3 n = tri_interaction_normal<SHP>(sc.bvh, hslot, hb.y, hb.z, hb.w);
                 if (lt.two_sided || dot(n, -wi) > 0.0f) li = V3{lt.L[0], lt.L[1], lt.L[2]};
             }
         } else if (lt.type == PBRT_LIGHT_INFINITE) {

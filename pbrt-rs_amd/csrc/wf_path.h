@@ -64,9 +64,11 @@ struct ShadeBins {
 // Thread i takes the shade-queue entry at position rec = i (order: rec = order[i], the queue in material order): the path
 // p = qin.shade[rec] with its persistent state at p, and the transient records of this generation at rec. What the path
 // hands to the next launch is staged in LDS and written to the next generation at its position in qout.shade.
-template <bool BIN, int LEVEL>
-__global__ void __launch_bounds__(256, LEVEL == 3 ? 2 : PB_SHADE_WAVES) k_shade(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
-                                                 TileList tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
+// SHP: the scene may hold general quadric shapes (surface_from_hit, light_sample_li); k_shade_shapes below is that build, so the
+// kernels of every other scene compile as they did without it.
+template <bool BIN, int LEVEL, bool SHP>
+PB_DEV void shade_bounce(const ShadeConsts& sc, const PathState& ps, const Queues& qin, const Queues& qout, const PassParams& pp,
+                         const TileList& tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
     constexpr bool GLOSSY = LEVEL >= 1;
     constexpr int kShadeKeys = shade_keys(LEVEL);
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -118,7 +120,7 @@ __global__ void __launch_bounds__(256, LEVEL == 3 ? 2 : PB_SHADE_WAVES) k_shade(
         if (flags & (PF_NEE_SHADOW | PF_NEE_MIS)) {
             float pick_pdf;
             V3 beta_v;
-            V3 ld = estimate_direct_resolve(sc, ps, rec, flags, &pick_pdf, &beta_v);
+            V3 ld = estimate_direct_resolve<SHP>(sc, ps, rec, flags, &pick_pdf, &beta_v);
             ld = ld / pick_pdf;                 // integrator.rs:133
             L = L + mulv(beta_v, ld);           // path.rs:113-120
             flags &= ~(PF_NEE_SHADOW | PF_NEE_MIS);
@@ -134,7 +136,7 @@ __global__ void __launch_bounds__(256, LEVEL == 3 ? 2 : PB_SHADE_WAVES) k_shade(
             bool found = hslot >= 0;
             Surf sf;
             if (found) {
-                sf = surface_from_hit(sc.bvh, hslot, hit_instance(ps, hbase), h0.y, h0.z, h0.w, rd);
+                sf = surface_from_hit<SHP>(sc.bvh, hslot, hit_instance(ps, hbase), h0.y, h0.z, h0.w, rd);
                 if (qout.keys) cell = ray_sort_cell(sf.p.x, sf.p.y, sf.p.z, qout.key_lo, qout.key_inv);
             }
             // path.rs:80-88
@@ -189,10 +191,10 @@ __global__ void __launch_bounds__(256, LEVEL == 3 ? 2 : PB_SHADE_WAVES) k_shade(
                             float ul0, ul1, us0, us1;
                             samp_2d(pp, sm, &ul0, &ul1);
                             samp_2d(pp, sm, &us0, &us1);
-                            int nee_flags = GLOSSY ? estimate_direct_emit(sc, stage, sf, fr, true, nsb, light_num, ul0, ul1, us0,
-                                                                          us1, pick_pdf, beta)
-                                                   : estimate_direct_emit(sc, stage, sf, fr, true, MatteBsdf{kd}, light_num, ul0, ul1,
-                                                                          us0, us1, pick_pdf, beta);
+                            int nee_flags = GLOSSY ? estimate_direct_emit<SHP>(sc, stage, sf, fr, true, nsb, light_num, ul0, ul1, us0,
+                                                                               us1, pick_pdf, beta)
+                                                   : estimate_direct_emit<SHP>(sc, stage, sf, fr, true, MatteBsdf{kd}, light_num, ul0, ul1,
+                                                                               us0, us1, pick_pdf, beta);
                             flags |= nee_flags & 0xff;
                             emit_shadow = (nee_flags & PF_NEE_SHADOW) != 0;
                             emit_mis = (nee_flags & PF_NEE_MIS) != 0;
@@ -264,6 +266,18 @@ __global__ void __launch_bounds__(256, LEVEL == 3 ? 2 : PB_SHADE_WAVES) k_shade(
     const AppendSlots slots = block_reserve(sh, qout, emit_cont, emit_mis, emit_shadow, again);
     stage.flush(ps, slots.shade, emit_cont, emit_mis, emit_shadow);
     block_write(qout, slots, p, slots.shade, emit_cont, emit_mis, emit_shadow, again, cell, mis_bool);
+}
+template <bool BIN, int LEVEL>
+__global__ void __launch_bounds__(256, LEVEL == 3 ? 2 : PB_SHADE_WAVES) k_shade(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
+                                                 TileList tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
+    shade_bounce<BIN, LEVEL, false>(sc, ps, qin, qout, pp, tiles, n_in, order);
+}
+// scenes with general shapes: the level-3 BSDF set serves every material table (matte, plastic, metal and the set_material rows go
+// through it bit for bit as through the lower levels)
+template <bool BIN>
+__global__ void __launch_bounds__(256, 2) k_shade_shapes(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
+                                                        TileList tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
+    shade_bounce<BIN, 3, true>(sc, ps, qin, qout, pp, tiles, n_in, order);
 }
 
 }  // namespace pb

@@ -189,8 +189,90 @@ PB_DEV Surf make_surface_sphere(const DevBVH& bvh, int slot, V3 ph, V3 rd) {
     s.sdpdu = through(dpdu);
     return s;
 }
-// Hit record -> world-space surface. `rd` is the world-space ray direction.
+// Sphere / Disk / Cylinder::intersect past the hit test (sphere.rs:38-92, disk.rs:97-105, cylinder.rs:105-115) for a row of the
+// shape table: partial derivatives and the object-space error bound, SurfaceInteraction::new (n = normalize(dpdu x dpdv),
+// flipped when reverse_orientation ^ transform_swaps_handedness, as in pbrt-v3), then pbrt-v3's Transform(SurfaceInteraction)
+// through the shape's matrices, in the operation order of make_surface_sphere / instance_to_world. ph = the hit record's
+// object-space point (sphere and cylinder: refined onto the surface; disk: z is set to the height here).
+PB_DEV Surf make_surface_shape(const DevBVH& bvh, int slot, V3 ph, V3 rd) {
+    float4 c4 = bvh.tris[3 * (size_t)slot + 2];
+    const DevShape& sh = bvh.shapes[__float_as_int(c4.x)];
+    Surf s;
+    s.material = __float_as_int(c4.z);
+    s.light = (__float_as_int(c4.w) & kPrimLightMask) - 1;
+    const int type = sh.flags & kShapeTypeMask;
+    const float radius = sh.radius, phi_max = sh.phi_max;
+    V3 dpdu = V3{-phi_max * ph.y, phi_max * ph.x, 0.0f};
+    float vx, vy, vz, ex, ey, ez, z = ph.z;  // dpdv, the object-space error bound (scalars: the branches assign no aggregate)
+    if (type == kShapeSphere) {
+        float theta = det_acos(clampf(ph.z / radius, -1.0f, 1.0f));
+        float z_radius = __builtin_sqrtf(ph.x * ph.x + ph.y * ph.y);
+        float inv_z_radius = 1.0f / z_radius;
+        float cos_phi = ph.x * inv_z_radius, sin_phi = ph.y * inv_z_radius;
+        float dtheta = sh.theta_max - sh.theta_min;
+        vx = (ph.z * cos_phi) * dtheta;
+        vy = (ph.z * sin_phi) * dtheta;
+        vz = (-radius * det_sin(theta)) * dtheta;
+        ex = __builtin_fabsf(ph.x) * kGamma5;
+        ey = __builtin_fabsf(ph.y) * kGamma5;
+        ez = __builtin_fabsf(ph.z) * kGamma5;
+    } else if (type == kShapeCylinder) {
+        vx = 0.0f;
+        vy = 0.0f;
+        vz = sh.z_max - sh.z_min;
+        ex = __builtin_fabsf(ph.x) * kGamma3;
+        ey = __builtin_fabsf(ph.y) * kGamma3;
+        ez = __builtin_fabsf(0.0f) * kGamma3;
+    } else {
+        float r_hit = __builtin_sqrtf(ph.x * ph.x + ph.y * ph.y);
+        float k = sh.inner_radius - radius;
+        vx = (ph.x * k) / r_hit;
+        vy = (ph.y * k) / r_hit;
+        vz = (0.0f * k) / r_hit;
+        z = sh.z_min;
+        ex = ey = ez = 0.0f;
+    }
+    const V3 dpdv = V3{vx, vy, vz}, pe = V3{ex, ey, ez};
+    V3 n = normalize(cross(dpdu, dpdv));  // SurfaceInteraction::new (interaction.rs:248-300)
+    if (sh.flags & kShapeFlipNormal) n = -n;
+    const float* w = sh.o2w;
+    const float* o = sh.w2o;
+    const float g3 = kGamma3;
+    float x = ph.x, y = ph.y;
+    s.p = V3{w[0] * x + w[1] * y + w[2] * z + w[3], w[4] * x + w[5] * y + w[6] * z + w[7], w[8] * x + w[9] * y + w[10] * z + w[11]};
+    s.p_error.x = (g3 + 1.0f) * (__builtin_fabsf(w[0] * pe.x) + __builtin_fabsf(w[1] * pe.y) + __builtin_fabsf(w[2] * pe.z)) +
+                  g3 * (__builtin_fabsf(w[0] * x) + __builtin_fabsf(w[1] * y) + __builtin_fabsf(w[2] * z) + __builtin_fabsf(w[3]));
+    s.p_error.y = (g3 + 1.0f) * (__builtin_fabsf(w[4] * pe.x) + __builtin_fabsf(w[5] * pe.y) + __builtin_fabsf(w[6] * pe.z)) +
+                  g3 * (__builtin_fabsf(w[4] * x) + __builtin_fabsf(w[5] * y) + __builtin_fabsf(w[6] * z) + __builtin_fabsf(w[7]));
+    s.p_error.z = (g3 + 1.0f) * (__builtin_fabsf(w[8] * pe.x) + __builtin_fabsf(w[9] * pe.y) + __builtin_fabsf(w[10] * pe.z)) +
+                  g3 * (__builtin_fabsf(w[8] * x) + __builtin_fabsf(w[9] * y) + __builtin_fabsf(w[10] * z) + __builtin_fabsf(w[11]));
+    auto vec = [](const float* m, V3 v) {  // Transform * Vector3: the upper 3x3
+        return V3{m[0] * v.x + m[1] * v.y + m[2] * v.z, m[4] * v.x + m[5] * v.y + m[6] * v.z, m[8] * v.x + m[9] * v.y + m[10] * v.z};
+    };
+    auto nrm = [o](V3 v) {  // Transform * Normal3: the transpose of the inverse's upper 3x3
+        return V3{o[0] * v.x + o[4] * v.y + o[8] * v.z, o[1] * v.x + o[5] * v.y + o[9] * v.z, o[2] * v.x + o[6] * v.y + o[10] * v.z};
+    };
+    s.n = normalize(nrm(n));
+    V3 d_obj = vec(o, rd);  // the object-space ray direction of shape_object_ray
+    s.wo = normalize(vec(w, -d_obj));
+    s.dpdu = vec(w, dpdu);
+    V3 sn = normalize(nrm(n));  // shading.n = n before the transform (D47)
+    s.ns = dot(sn, s.n) < 0.0f ? -sn : sn;
+    s.sdpdu = vec(w, dpdu);
+    return s;
+}
+// Hit record -> world-space surface. `rd` is the world-space ray direction. SHP: the scene may hold general shapes
+// (DevBVH::has_spheres == 2); a template value so that the kernels of the other scenes compile without the dispatch.
+template <bool SHP = false>
 PB_DEV Surf surface_from_hit(const DevBVH& bvh, int slot, int inst_slot, float b0, float b1, float b2, V3 rd) {
+    if (SHP) {
+        Surf s;
+        if (__float_as_int(bvh.tris[3 * (size_t)slot + 2].w) & kPrimSphere)
+            s = make_surface_shape(bvh, slot, V3{b0, b1, b2}, rd);
+        else
+            s = make_surface(bvh, slot, b0, b1, b2, rd);
+        return s;
+    }
     if (bvh.has_spheres && (__float_as_int(bvh.tris[3 * (size_t)slot + 2].w) & kPrimSphere))
         return make_surface_sphere(bvh, slot, V3{b0, b1, b2}, rd);
     if (bvh.instanced && inst_slot >= 0) {
@@ -206,7 +288,10 @@ PB_DEV Surf surface_from_hit(const DevBVH& bvh, int slot, int inst_slot, float b
     return make_surface(bvh, slot, b0, b1, b2, rd);
 }
 // SurfaceInteraction::n of a hit at barycentrics (b0, b1, b2): the geometric normal, on the shading normal's side
+template <bool SHP = false>
 PB_DEV V3 tri_interaction_normal(const DevBVH& bvh, int slot, float b0, float b1, float b2) {
+    if (SHP && (__float_as_int(bvh.tris[3 * (size_t)slot + 2].w) & kPrimSphere))
+        return make_surface_shape(bvh, slot, V3{b0, b1, b2}, V3{0.0f, 0.0f, 1.0f}).n;  // (b0, b1, b2) = the hit point
     if (bvh.has_spheres && (__float_as_int(bvh.tris[3 * (size_t)slot + 2].w) & kPrimSphere))
         return make_surface_sphere(bvh, slot, V3{b0, b1, b2}, V3{0.0f, 0.0f, 1.0f}).n;  // (b0, b1, b2) = the hit point
     V3 p0, p1, p2;

@@ -41,6 +41,7 @@ EXPORTS = [
     "pbrt_hip_li", "pbrt_hip_li_device", "pbrt_hip_camera_rays", "pbrt_hip_scene_create_two_level", "pbrt_hip_debug_wide_export",
     "pbrt_hip_scene_set_environment_map", "pbrt_hip_envmap_tables", "pbrt_hip_scene_set_material_roughness", "pbrt_hip_bsdf_query",
     "pbrt_hip_scene_set_material", "pbrt_hip_scene_set_disney_material",
+    "pbrt_hip_shape_world_bounds", "pbrt_hip_scene_create_with_shapes",
 ]
 MAT_NONE, MAT_MATTE, MAT_MIRROR, MAT_GLASS, MAT_PLASTIC, MAT_METAL = (scenes.MAT_NONE, scenes.MAT_MATTE, scenes.MAT_MIRROR,
                                                                       scenes.MAT_GLASS, scenes.MAT_PLASTIC, scenes.MAT_METAL)
@@ -118,6 +119,9 @@ def lib():
         L.pbrt_hip_scene_set_shading_data.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp]
         L.pbrt_hip_scene_create_with_spheres.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, vp, i32, vp,
                                                          ctypes.POINTER(vp)]
+        L.pbrt_hip_shape_world_bounds.argtypes = [vp, i32, vp]
+        L.pbrt_hip_scene_create_with_shapes.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, i32, vp,
+                                                        ctypes.POINTER(vp)]
         L.pbrt_hip_free.argtypes = [vp]
         L.pbrt_hip_free.restype = None
         L.pbrt_hip_scene_create.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp,
@@ -359,6 +363,16 @@ def instance_bounds(object_min, object_max, instances):
     return lo, hi
 
 
+def shape_world_bounds(shapes):
+    """Shape::world_bound per PbrtShape record (scenes.SHAPE_DTYPE): (n, 3) mins and (n, 3) maxs. Host only."""
+    shapes = np.ascontiguousarray(shapes, dtype=scenes.SHAPE_DTYPE)
+    out = np.zeros((len(shapes), 6), dtype=np.float32)
+    rc = lib().pbrt_hip_shape_world_bounds(_p(shapes) if len(shapes) else None, len(shapes), _p(out) if len(shapes) else None)
+    if rc != 0:
+        raise PbrtHipError(f"pbrt_hip_shape_world_bounds failed ({rc})")
+    return np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3:])
+
+
 def build_general_two_level(scene, max_prims_in_node=4, split_method=SPLIT_SAH):
     """Host BVH builds for scenes.two_level_scene-style scenes: one tree per object, the top-level tree over the instances'
     world bounds followed by the world triangles' bounds. Returns (object trees [(nodes, order)], instances, tlas_nodes, tlas_order)."""
@@ -425,7 +439,12 @@ class Scene:
         materials = np.ascontiguousarray(scene["materials"], dtype=MATERIAL_DTYPE)
         tri_light = np.ascontiguousarray(scene["tri_light"], dtype=np.int32)
         lights = np.ascontiguousarray(scene["lights"], dtype=LIGHT_DTYPE)
-        spheres = scene.get("spheres")
+        spheres, shapes = scene.get("spheres"), scene.get("shapes")
+        if shapes is not None and len(shapes):
+            if spheres is not None and len(spheres):
+                raise PbrtHipError('a scene holds either "spheres" or "shapes", not both (a Sphere is a shape: scenes.sphere_shape)')
+            self._init_with_shapes(scene, tri_material, materials, tri_light, lights, max_prims_in_node, split_method, bvh)
+            return
         if spheres is not None and len(spheres):
             self._init_with_spheres(scene, tri_material, materials, tri_light, lights, max_prims_in_node, split_method, bvh)
             return
@@ -461,6 +480,24 @@ class Scene:
             _p(materials), len(materials), _p(tri_light), _p(lights) if len(lights) else None, len(lights), _p(sph4),
             _p(sph_mat), _p(sph_light), len(sph4), _p(self.nodes), len(self.nodes), _p(self.prim_order), ctypes.byref(h))
         self.ctx.check(rc, "pbrt_hip_scene_create_with_spheres")
+        self.h = h
+        self.ctx._scenes.add(self)
+
+    def _init_with_shapes(self, scene, tri_material, materials, tri_light, lights, max_prims_in_node, split_method, bvh):
+        """scene["shapes"]: scenes.SHAPE_DTYPE records (scenes.sphere_shape / disk / cylinder); shape i is primitive n_tris + i."""
+        shapes = np.ascontiguousarray(scene["shapes"], dtype=scenes.SHAPE_DTYPE).reshape(-1)
+        if bvh is None:
+            tri = self.positions[self.indices]                       # Triangle::world_bound (triangle.rs:175-180)
+            lo, hi = shape_world_bounds(shapes)                      # Shape::world_bound = object_to_world * object_bound()
+            bvh = bvh_build_boxes(np.concatenate([tri.min(axis=1), lo]), np.concatenate([tri.max(axis=1), hi]),
+                                  max_prims_in_node, split_method)
+        self.nodes, self.prim_order = bvh
+        h = ctypes.c_void_p()
+        rc = lib().pbrt_hip_scene_create_with_shapes(
+            self.ctx.h, _p(self.positions), self.positions.shape[0], _p(self.indices), self.indices.shape[0], _p(tri_material),
+            _p(materials), len(materials), _p(tri_light), _p(lights) if len(lights) else None, len(lights), _p(shapes),
+            len(shapes), _p(self.nodes), len(self.nodes), _p(self.prim_order), ctypes.byref(h))
+        self.ctx.check(rc, "pbrt_hip_scene_create_with_shapes")
         self.h = h
         self.ctx._scenes.add(self)
 

@@ -21,6 +21,11 @@ RAY_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("t_max", "<f4"), ("time
 HIT_DTYPE = np.dtype([("t", "<f4"), ("b0", "<f4"), ("b1", "<f4"), ("b2", "<f4"), ("prim_id", "<i4"),
                       ("instance_id", "<i4"), ("pad", "<i4", 2)])
 INSTANCE_DTYPE = np.dtype([("to_world", "<f4", 16), ("to_object", "<f4", 16), ("material", "<i4"), ("pad", "<i4", 3)])
+# PbrtShape (pbrt_hip_scene_create_with_shapes): scene["shapes"] is an array of these, shape i is primitive n_tris + i
+SHAPE_DTYPE = np.dtype([("type", "<i4"), ("reverse_orientation", "<i4"), ("material", "<i4"), ("light", "<i4"), ("radius", "<f4"),
+                        ("z_min", "<f4"), ("z_max", "<f4"), ("inner_radius", "<f4"), ("phi_max", "<f4"), ("pad", "<f4", 3),
+                        ("to_world", "<f4", 16), ("to_object", "<f4", 16)])
+SHAPE_SPHERE, SHAPE_DISK, SHAPE_CYLINDER = 0, 1, 2
 NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("offset", "<i4"), ("n_primitives", "<u2"),
                        ("axis", "u1"), ("pad", "u1")])
 assert MATERIAL_DTYPE.itemsize == 32 and LIGHT_DTYPE.itemsize == 96
@@ -179,6 +184,40 @@ def distant_light(w_from_surface_to_light, radiance):
     l = np.zeros((), dtype=LIGHT_DTYPE)
     l["type"], l["L"], l["prim"], l["n_samples"], l["pos"] = LIGHT_DISTANT, radiance, -1, 1, w / np.linalg.norm(w)
     return l
+
+
+def _shape(kind, radius, z_min, z_max, inner_radius, phi_max, to_world, material, light, reverse_orientation):
+    """One PbrtShape record. to_world: 4x4 affine (None = identity); the inverse is formed in float64 and rounded once."""
+    m = np.eye(4) if to_world is None else np.asarray(to_world, dtype=np.float32).astype(np.float64).reshape(4, 4)
+    rec = np.zeros(1, dtype=SHAPE_DTYPE)
+    rec["type"], rec["reverse_orientation"], rec["material"], rec["light"] = kind, int(bool(reverse_orientation)), material, light
+    rec["radius"], rec["z_min"], rec["z_max"], rec["inner_radius"], rec["phi_max"] = radius, z_min, z_max, inner_radius, phi_max
+    rec["to_world"] = m.astype(np.float32).reshape(16)
+    inv = np.linalg.inv(m)
+    inv[3] = (0.0, 0.0, 0.0, 1.0)
+    rec["to_object"] = inv.astype(np.float32).reshape(16)
+    return rec
+
+
+def sphere_shape(radius, z_min=None, z_max=None, phi_max=360.0, to_world=None, material=0, light=-1, reverse_orientation=False):
+    """Sphere::new(o2w, w2o, reverse_orientation, radius, z_min, z_max, phi_max); z_min / z_max default to the full sphere."""
+    return _shape(SHAPE_SPHERE, radius, -radius if z_min is None else z_min, radius if z_max is None else z_max, 0.0, phi_max,
+                  to_world, material, light, reverse_orientation)
+
+
+def disk(height, radius, inner_radius=0.0, phi_max=360.0, to_world=None, material=0, light=-1, reverse_orientation=False):
+    """Disk::new(o2w, w2o, reverse_orientation, height, radius, inner_radius, phi_max)"""
+    return _shape(SHAPE_DISK, radius, height, height, inner_radius, phi_max, to_world, material, light, reverse_orientation)
+
+
+def cylinder(radius, z_min, z_max, phi_max=360.0, to_world=None, material=0, light=-1, reverse_orientation=False):
+    """Cylinder::new(o2w, w2o, reverse_orientation, radius, z_min, z_max, phi_max)"""
+    return _shape(SHAPE_CYLINDER, radius, z_min, z_max, 0.0, phi_max, to_world, material, light, reverse_orientation)
+
+
+def shapes(*records):
+    """The records of sphere_shape / disk / cylinder as one scene["shapes"] array."""
+    return np.concatenate(records) if records else np.zeros(0, dtype=SHAPE_DTYPE)
 
 
 def _quad(a, b, c, d):

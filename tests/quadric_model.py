@@ -1,0 +1,227 @@
+"""float64 model of the quadric shapes (Sphere, Disk, Cylinder under an affine transform): numpy only, no project code.
+
+A shape is a dict: type ("sphere" | "disk" | "cylinder"), radius, z_min, z_max (disk: z_min = z_max = height), inner_radius,
+phi_max (radians), o2w (4x4 float64), reverse (bool). `from_record` makes one from a PbrtShape record (any mapping with the
+header's field names), applying what the constructors apply: ordered z, the sphere's z clamped to the radius, phi_max
+clamped to [0, 360] degrees.
+
+intersect() follows the textbook definitions, not the device's operation order: roots of the quadratic in float64, the
+nearer root first, each rejected by its t range, z range and sweep angle. Beside the verdict it reports `near`: some
+quantity a decision rests on lies within REL = 1e-4 (relative to that quantity's natural scale) of the boundary it is
+compared with, so float32 arithmetic may decide the other way. Only quantities that are actually consulted count: the
+farther root's only when the nearer root was rejected.
+"""
+import numpy as np
+
+REL = 1e-4
+TWO_PI = 2.0 * np.pi
+TYPES = ("sphere", "disk", "cylinder")  # PbrtShapeType 0, 1, 2
+
+
+def from_record(rec):
+    kind = TYPES[int(rec["type"])]
+    r = float(rec["radius"])
+    z0, z1 = float(min(rec["z_min"], rec["z_max"])), float(max(rec["z_min"], rec["z_max"]))
+    if kind == "sphere":
+        z0, z1 = float(np.clip(z0, -r, r)), float(np.clip(z1, -r, r))
+    if kind == "disk":
+        z0 = z1 = float(rec["z_min"])
+    return dict(type=kind, radius=r, z_min=z0, z_max=z1, inner_radius=float(rec["inner_radius"]) if kind == "disk" else 0.0,
+                phi_max=np.radians(float(np.clip(rec["phi_max"], 0.0, 360.0))),
+                o2w=np.asarray(rec["to_world"], dtype=np.float64).reshape(4, 4), reverse=bool(rec["reverse_orientation"]))
+
+
+def make(kind, radius, z_min, z_max, inner_radius=0.0, phi_max_deg=360.0, o2w=None, reverse=False):
+    return from_record(dict(type=TYPES.index(kind), radius=radius, z_min=z_min, z_max=z_max, inner_radius=inner_radius,
+                            phi_max=phi_max_deg, to_world=np.eye(4) if o2w is None else o2w, reverse_orientation=reverse))
+
+
+def swaps_handedness(shape):
+    return np.linalg.det(shape["o2w"][:3, :3]) < 0.0
+
+
+def object_bound(shape):
+    r = shape["radius"]
+    return np.array([-r, -r, shape["z_min"]]), np.array([r, r, shape["z_max"]])
+
+
+def world_bounds(shape):
+    """object_to_world * object_bound(): the union of the eight transformed corners, in float64."""
+    lo, hi = object_bound(shape)
+    corners = np.array([[(hi if c & 1 else lo)[0], (hi if c & 2 else lo)[1], (hi if c & 4 else lo)[2], 1.0] for c in range(8)])
+    w = corners @ shape["o2w"].T
+    return w[:, :3].min(axis=0), w[:, :3].max(axis=0)
+
+
+def area(shape):
+    r = shape["radius"]
+    if shape["type"] == "sphere":
+        return shape["phi_max"] * r * (shape["z_max"] - shape["z_min"])
+    if shape["type"] == "disk":
+        return shape["phi_max"] * 0.5 * (r * r - shape["inner_radius"] ** 2)
+    return (shape["z_max"] - shape["z_min"]) * r * shape["phi_max"]
+
+
+def surface_points(shape, u, v):
+    """Object-space points of the parametrisation at u, v in [0, 1] (arrays): what `area` integrates over."""
+    r, phi = shape["radius"], u * shape["phi_max"]
+    if shape["type"] == "sphere":
+        z = shape["z_min"] + v * (shape["z_max"] - shape["z_min"])
+        rho = np.sqrt(np.maximum(r * r - z * z, 0.0))
+        return np.stack([rho * np.cos(phi), rho * np.sin(phi), z], axis=-1)
+    if shape["type"] == "disk":
+        rho = shape["inner_radius"] + v * (r - shape["inner_radius"])
+        return np.stack([rho * np.cos(phi), rho * np.sin(phi), np.full_like(rho, shape["z_min"])], axis=-1)
+    z = shape["z_min"] + v * (shape["z_max"] - shape["z_min"])
+    return np.stack([r * np.cos(phi), r * np.sin(phi), z], axis=-1)
+
+
+def implicit_residual(shape, p):
+    """0 on the (unbounded) surface the shape is cut from, relative to the radius."""
+    r = shape["radius"]
+    if shape["type"] == "sphere":
+        return (np.sqrt((p ** 2).sum(axis=-1)) - r) / r
+    if shape["type"] == "disk":
+        return (p[..., 2] - shape["z_min"]) / r
+    return (np.sqrt(p[..., 0] ** 2 + p[..., 1] ** 2) - r) / r
+
+
+def _phi(p):
+    phi = np.arctan2(p[..., 1], p[..., 0])
+    return np.where(phi < 0.0, phi + TWO_PI, phi)
+
+
+def _near_phi(shape, phi):
+    near = (phi <= REL * TWO_PI) | (phi >= TWO_PI * (1.0 - REL))
+    return near | (np.abs(phi - shape["phi_max"]) <= REL * TWO_PI)
+
+
+def intersect(shape, o, d, t_max=np.inf):
+    """o, d: (n, 3) world-space rays (d need not be normalised); t_max: scalar or (n,). Returns a dict of arrays:
+    hit (bool), t, p (object-space hit point), phi, n (world-space unit normal as the shading code orients it), near."""
+    o, d = np.asarray(o, dtype=np.float64), np.asarray(d, dtype=np.float64)
+    n_rays = o.shape[0]
+    t_max = np.broadcast_to(np.asarray(t_max, dtype=np.float64), (n_rays,))
+    w2o = np.linalg.inv(shape["o2w"])
+    oo = o @ w2o[:3, :3].T + w2o[:3, 3]
+    dd = d @ w2o[:3, :3].T
+    r, kind = shape["radius"], shape["type"]
+    t_scale = np.maximum(np.sqrt((oo ** 2).sum(axis=1)) / np.sqrt((dd ** 2).sum(axis=1)), 1e-30)  # time to travel |origin|
+
+    def near_t(t):
+        tm = np.where(np.isfinite(t_max), t_max, 0.0)
+        return (np.abs(t) <= REL * np.maximum(t_scale, np.abs(t))) | \
+               (np.isfinite(t_max) & (np.abs(t - tm) <= REL * np.maximum(np.abs(t), np.abs(tm))))
+
+    hit = np.zeros(n_rays, dtype=bool)
+    near = np.zeros(n_rays, dtype=bool)
+    t_hit = np.full(n_rays, np.inf)
+    p_hit = np.zeros((n_rays, 3))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if kind == "disk":
+            dz = dd[:, 2]
+            near |= np.abs(dz) <= REL * np.sqrt((dd ** 2).sum(axis=1))
+            t = (shape["z_min"] - oo[:, 2]) / dz
+            ok = (dz != 0.0) & (t > 0.0) & (t < t_max)
+            near |= (dz != 0.0) & near_t(t)
+            p = oo + dd * np.where(ok, t, 0.0)[:, None]
+            rho = np.sqrt(p[:, 0] ** 2 + p[:, 1] ** 2)
+            inside = (rho <= r) & (rho >= shape["inner_radius"])
+            near |= ok & ((np.abs(rho - r) <= REL * r) |
+                          ((shape["inner_radius"] > 0.0) & (np.abs(rho - shape["inner_radius"]) <= REL * shape["inner_radius"])))
+            phi = _phi(p)
+            near |= ok & inside & _near_phi(shape, phi)
+            hit = ok & inside & (phi <= shape["phi_max"])
+            t_hit = np.where(hit, t, np.inf)
+            p_hit = p
+            p_hit[:, 2] = shape["z_min"]
+        else:
+            k = 3 if kind == "sphere" else 2
+            a = (dd[:, :k] ** 2).sum(axis=1)
+            b = 2.0 * (dd[:, :k] * oo[:, :k]).sum(axis=1)
+            c = (oo[:, :k] ** 2).sum(axis=1) - r * r
+            disc = b * b - 4.0 * a * c
+            near |= np.abs(disc) <= REL * (b * b + np.abs(4.0 * a * c))
+            real = (disc >= 0.0) & (a > 0.0)
+            root = np.sqrt(np.maximum(disc, 0.0))
+            q = np.where(b < 0.0, -0.5 * (b - root), -0.5 * (b + root))
+            ta, tb = q / a, c / q
+            t0, t1 = np.minimum(ta, tb), np.maximum(ta, tb)
+            pending = real.copy()
+            for t in (t0, t1):
+                in_range = pending & (t > 0.0) & (t <= t_max)
+                near |= pending & near_t(t)
+                p = oo + dd * np.where(in_range, t, 0.0)[:, None]
+                if kind == "sphere":
+                    p = p * (r / np.sqrt((p ** 2).sum(axis=1)))[:, None]
+                    z_ok = ((shape["z_min"] <= -r) | (p[:, 2] >= shape["z_min"])) & ((shape["z_max"] >= r) | (p[:, 2] <= shape["z_max"]))
+                    near_z = ((shape["z_min"] > -r) & (np.abs(p[:, 2] - shape["z_min"]) <= REL * r)) | \
+                             ((shape["z_max"] < r) & (np.abs(p[:, 2] - shape["z_max"]) <= REL * r))
+                else:
+                    p[:, :2] *= (r / np.sqrt(p[:, 0] ** 2 + p[:, 1] ** 2))[:, None]
+                    z_ok = (p[:, 2] >= shape["z_min"]) & (p[:, 2] <= shape["z_max"])
+                    near_z = (np.abs(p[:, 2] - shape["z_min"]) <= REL * r) | (np.abs(p[:, 2] - shape["z_max"]) <= REL * r)
+                phi = _phi(p)
+                near |= in_range & (near_z | _near_phi(shape, phi))
+                accept = in_range & z_ok & (phi <= shape["phi_max"])
+                t_hit = np.where(accept, t, t_hit)
+                p_hit = np.where(accept[:, None], p, p_hit)
+                hit |= accept
+                pending &= ~accept
+    # the normal: normalize(dpdu x dpdv) points outward for the sphere and the cylinder, along +z for the disk; flipped by
+    # reverse_orientation ^ transform_swaps_handedness; to world space by the inverse transpose
+    if kind == "sphere":
+        n_obj = p_hit / r
+    elif kind == "cylinder":
+        n_obj = np.stack([p_hit[:, 0], p_hit[:, 1], np.zeros(n_rays)], axis=1) / r
+    else:
+        n_obj = np.tile(np.array([0.0, 0.0, 1.0]), (n_rays, 1))
+    if shape["reverse"] != bool(swaps_handedness(shape)):
+        n_obj = -n_obj
+    n_w = n_obj @ w2o[:3, :3]  # (M^-1)^T n
+    with np.errstate(divide="ignore", invalid="ignore"):
+        n_w = n_w / np.sqrt((n_w ** 2).sum(axis=1))[:, None]
+    return dict(hit=hit, t=t_hit, p=p_hit, phi=_phi(p_hit), n=np.where(hit[:, None], n_w, 0.0), near=near)
+
+
+def intersect_scene(shapes, o, d, t_max=np.inf):
+    """Closest hit over a list of shapes: (prim index in the list or -1, t, near). `near` also flags rays whose two nearest
+    candidate hits lie within REL of each other (the closer one could be either)."""
+    n = len(o)
+    best_t, best = np.full(n, np.inf), np.full(n, -1)
+    second = np.full(n, np.inf)
+    near = np.zeros(n, dtype=bool)
+    for i, s in enumerate(shapes):
+        r = intersect(s, o, d, t_max)
+        near |= r["near"]
+        closer = r["hit"] & (r["t"] < best_t)
+        second = np.where(closer, best_t, np.where(r["hit"], np.minimum(second, r["t"]), second))
+        best = np.where(closer, i, best)
+        best_t = np.where(closer, r["t"], best_t)
+    near |= np.isfinite(second) & (second - best_t <= REL * second)
+    return best, best_t, near
+
+
+def rays_at_unit_cube(n, seed):
+    """The ray generator of the GPU tests: origins uniform on the sphere of radius 3, aimed at uniform points of [-1, 1]^3."""
+    rng = np.random.default_rng(seed)
+    v = rng.normal(size=(n, 3))
+    o = 3.0 * v / np.sqrt((v ** 2).sum(axis=1))[:, None]
+    target = rng.uniform(-1.0, 1.0, size=(n, 3))
+    d = target - o
+    d /= np.sqrt((d ** 2).sum(axis=1))[:, None]
+    return o.astype(np.float32), d.astype(np.float32)
+
+
+# ---- closed forms of the area-light tests ----
+def disk_light_floor_radiance(rho, L, R, h):
+    """Radiance leaving a Lambertian floor point (albedo rho) under the centre of a disk light of radius R at height h that
+    faces it: E = pi L R^2 / (h^2 + R^2), Lo = rho / pi * E."""
+    return rho * L * R * R / (h * h + R * R)
+
+
+def cylinder_light_centre_radiance(rho, L, R, H):
+    """The same for a Lambertian patch at the centre of a cylinder of radius R, z in [-H, H], emitting inward, the patch's
+    normal along the axis: the cylinder fills the hemisphere below polar angle atan(R / H) ... pi / 2, i.e.
+    E = pi L (1 - sin^2(theta_0)) with tan(theta_0) = R / H, Lo = rho L H^2 / (H^2 + R^2)."""
+    return rho * L * H * H / (H * H + R * R)

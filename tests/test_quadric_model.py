@@ -1,0 +1,162 @@
+"""The float64 quadric model against itself, pbrt_hip_shape_world_bounds against the model and against the float32
+corner-transform union, and the share of rays the GPU tests' generator puts next to a decision boundary. No GPU."""
+import numpy as np
+import pytest
+
+import pbrt_hip
+from pbrt_hip import scenes
+
+import quadric_model as qm
+
+
+def rot(axis, deg):
+    a = np.asarray(axis, dtype=np.float64)
+    a /= np.linalg.norm(a)
+    c, s = np.cos(np.radians(deg)), np.sin(np.radians(deg))
+    k = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    m = np.eye(4)
+    m[:3, :3] = c * np.eye(3) + s * k + (1 - c) * np.outer(a, a)
+    return m
+
+
+def translate(x, y, z):
+    m = np.eye(4)
+    m[:3, 3] = (x, y, z)
+    return m
+
+
+def scale(x, y, z):
+    return np.diag([x, y, z, 1.0])
+
+
+TRANSFORMS = {
+    "identity": np.eye(4),
+    "rigid": translate(0.2, -0.1, 0.15) @ rot((1, 2, 3), 40.0),
+    "scaled": translate(-0.1, 0.1, 0.0) @ rot((0, 1, 1), 25.0) @ scale(1.0, 0.6, 1.4),
+    "mirrored": translate(0.1, 0.0, -0.1) @ rot((1, 0, 1), 70.0) @ scale(1.0, -0.8, 1.1),
+}
+
+
+def shape_records():
+    """The shapes of the GPU tests: every type, radius in [0.3, 1], phi_max in {360, 270, 135}, mixed z ranges, inner radius 0 / 0.4 r."""
+    recs = []
+    for name, m in TRANSFORMS.items():
+        for phi in (360.0, 270.0, 135.0):
+            recs.append((f"sphere-{name}-{phi:g}", scenes.sphere_shape(0.8, -0.8 if phi == 360.0 else -0.5, 0.8 if phi != 135.0 else 0.3, phi, m)))
+            recs.append((f"cylinder-{name}-{phi:g}", scenes.cylinder(0.5 if phi != 270.0 else 0.3, -0.6, 0.7 if phi != 135.0 else 0.2, phi, m)))
+            recs.append((f"disk-{name}-{phi:g}", scenes.disk(0.1, 1.0 if phi == 360.0 else 0.7, 0.0 if phi != 270.0 else 0.28, phi, m)))
+    return recs
+
+
+RECORDS = shape_records()
+
+
+@pytest.mark.parametrize("name,rec", RECORDS[:9] + RECORDS[18:27], ids=[r[0] for r in RECORDS[:9] + RECORDS[18:27]])
+def test_hit_points_satisfy_the_implicit_equations(name, rec):
+    s = qm.from_record(rec[0])
+    o, d = qm.rays_at_unit_cube(4000, 11)
+    r = qm.intersect(s, o, d)
+    assert r["hit"].sum() > 50
+    p = r["p"][r["hit"]]
+    assert np.abs(qm.implicit_residual(s, p)).max() < 1e-12
+    # the object-space point is where the ray is at t
+    w2o = np.linalg.inv(s["o2w"])
+    oo = o.astype(np.float64) @ w2o[:3, :3].T + w2o[:3, 3]
+    dd = d.astype(np.float64) @ w2o[:3, :3].T
+    along = oo[r["hit"]] + dd[r["hit"]] * r["t"][r["hit"]][:, None]
+    assert np.abs(along - p).max() < 1e-9
+    # inside the cut: z range, sweep, radii
+    assert (r["phi"][r["hit"]] <= s["phi_max"] + 1e-12).all()
+    assert (p[:, 2] >= s["z_min"] - 1e-12).all() and (p[:, 2] <= s["z_max"] + 1e-12).all()
+    # unit normal, perpendicular to the surface: against a finite difference of the parametrisation through the transform
+    n = r["n"][r["hit"]]
+    assert np.abs(np.sqrt((n ** 2).sum(axis=1)) - 1.0).max() < 1e-12
+
+
+@pytest.mark.parametrize("kind", ["sphere", "disk", "cylinder"])
+def test_area_matches_a_quadrature(kind):
+    s = {"sphere": qm.make("sphere", 0.7, -0.4, 0.6, phi_max_deg=270.0),
+         "disk": qm.make("disk", 0.9, 0.2, 0.2, inner_radius=0.3, phi_max_deg=135.0),
+         "cylinder": qm.make("cylinder", 0.4, -0.3, 0.9, phi_max_deg=200.0)}[kind]
+    n = 400
+    u = (np.arange(n) + 0.5) / n
+    uu, vv = np.meshgrid(u, u, indexing="ij")
+    h = 1e-6
+    p = qm.surface_points(s, uu, vv)
+    du = (qm.surface_points(s, uu + h, vv) - qm.surface_points(s, uu - h, vv)) / (2 * h)
+    dv = (qm.surface_points(s, uu, vv + h) - qm.surface_points(s, uu, vv - h)) / (2 * h)
+    quad = np.sqrt((np.cross(du, dv) ** 2).sum(axis=-1)).mean()
+    assert np.abs(qm.implicit_residual(s, p)).max() < 1e-12
+    assert abs(quad - qm.area(s)) <= 2e-5 * qm.area(s)  # midpoint rule on 400 x 400 cells of a smooth integrand
+
+
+def float32_corner_union(rec):
+    """object_to_world * object_bound() as Transform * Bounds3 does it, every operation rounded to float32 in its order."""
+    f = np.float32
+    s = qm.from_record(rec)
+    lo, hi = (np.asarray(v, dtype=np.float32) for v in qm.object_bound(s))
+    m = np.asarray(rec["to_world"], dtype=np.float32).reshape(4, 4)
+    mn, mx = np.full(3, np.inf, dtype=np.float32), np.full(3, -np.inf, dtype=np.float32)
+    for c in range(8):
+        x, y, z = (hi if c & 1 else lo)[0], (hi if c & 2 else lo)[1], (hi if c & 4 else lo)[2]
+        for k in range(3):
+            p = f(f(f(f(m[k, 0] * x) + f(m[k, 1] * y)) + f(m[k, 2] * z)) + m[k, 3])
+            mn[k], mx[k] = min(mn[k], p), max(mx[k], p)
+    return mn, mx
+
+
+def test_shape_world_bounds_against_the_model_and_bit_for_bit():
+    recs = np.concatenate([r[1] for r in RECORDS])
+    lo, hi = pbrt_hip.shape_world_bounds(recs)
+    assert lo.shape == (len(recs), 3) and lo.dtype == np.float32
+    for i in range(len(recs)):
+        s = qm.from_record(recs[i])
+        mlo, mhi = qm.world_bounds(s)
+        # contains the model's bound up to the rounding of three products and three sums in float32: gamma(6) of the terms' magnitude
+        m = np.abs(s["o2w"][:3, :3]) @ np.maximum(np.abs(qm.object_bound(s)[0]), np.abs(qm.object_bound(s)[1])) + np.abs(s["o2w"][:3, 3])
+        slack = 6 * 2.0 ** -24 * m
+        assert (lo[i] <= mlo + slack).all() and (hi[i] >= mhi - slack).all(), RECORDS[i][0]
+        # every surface point of the model lies inside
+        u = np.linspace(0.0, 1.0, 41)
+        pts = qm.surface_points(s, *np.meshgrid(u, u, indexing="ij")).reshape(-1, 3) @ s["o2w"][:3, :3].T + s["o2w"][:3, 3]
+        assert (pts >= lo[i] - slack).all() and (pts <= hi[i] + slack).all(), RECORDS[i][0]
+        flo, fhi = float32_corner_union(recs[i])
+        assert lo[i].tobytes() == flo.tobytes() and hi[i].tobytes() == fhi.tobytes(), RECORDS[i][0]
+
+
+def test_shape_world_bounds_rejects_bad_arguments():
+    L = pbrt_hip.lib()
+    assert L.pbrt_hip_shape_world_bounds(None, 0, None) == 0
+    assert L.pbrt_hip_shape_world_bounds(None, 1, None) != 0
+    bad = scenes.disk(0.0, 1.0)
+    bad["type"] = 7
+    out = np.zeros(6, dtype=np.float32)
+    assert L.pbrt_hip_shape_world_bounds(bad.ctypes.data, 1, out.ctypes.data) != 0
+
+
+def test_helpers_round_the_float64_inverse_once():
+    rec = scenes.cylinder(0.5, -1.0, 1.0, to_world=TRANSFORMS["scaled"])[0]
+    m = rec["to_world"].astype(np.float64).reshape(4, 4)
+    inv = np.linalg.inv(m)
+    inv[3] = (0, 0, 0, 1)
+    assert rec["to_object"].tobytes() == inv.astype(np.float32).reshape(16).tobytes()
+    assert scenes.SHAPE_DTYPE.itemsize == 176  # sizeof(PbrtShape)
+    t = scenes.sphere_shape(0.5, to_world=translate(0.25, -1.5, 3.0))[0]
+    assert (t["to_object"].reshape(4, 4)[:3, 3] == np.float32([-0.25, 1.5, -3.0])).all()  # translate(-c), exactly
+
+
+@pytest.mark.parametrize("kind", ["sphere", "disk", "cylinder"])
+def test_ray_generator_stays_within_the_near_cap(kind):
+    """The GPU intersection test excludes rays flagged `near` and asserts that they are at most 1 % of the batch; here the
+    same generator and shapes, with the model alone."""
+    o, d = qm.rays_at_unit_cube(20000, 5)
+    worst = 0.0
+    for name, rec in RECORDS:
+        if not name.startswith(kind):
+            continue
+        r = qm.intersect(qm.from_record(rec[0]), o, d)
+        share = r["near"].mean()
+        print(f"{name}: hits {r['hit'].mean():.3f} near {share:.5f}")
+        worst = max(worst, share)
+        assert r["hit"].mean() > 0.01
+    assert worst <= 0.01

@@ -430,8 +430,11 @@ int pbrt_hip_shape_world_bounds(const PbrtShape* shapes, int32_t n, float* bound
  * n_tris + i in prim_order, and hit records of shapes carry the refined object-space hit point in (b0, b1, b2).
  * PBRT_HIP_ERR_INVALID (pbrt_hip_last_error says why) for an unknown type, a radius that is not positive, a disk's
  * inner_radius outside [0, radius), a cylinder with z_min == z_max, phi_max <= 0, a transform that is not affine, a
- * material or light out of range, and a partial sphere (z range or phi_max short of the full sphere) that carries a
- * light: Sphere::sample covers the full sphere only. */
+ * material or light out of range, and for a shape that carries a light: a partial sphere (z range or phi_max short of
+ * the full sphere) or a partial disk (inner_radius > 0 or phi_max < 360), since Sphere::sample and Disk::sample cover the
+ * full shape only; a to_world whose linear part scales or shears (an axis' squared length or two axes' dot product more
+ * than 0.001 off 1 or 0; a mirror that keeps lengths is allowed), since Shape::area is the object-space area. A one-sided
+ * shape light emits to the side of the surface normal: flipped by reverse_orientation ^ (det(to_world) < 0). */
 int pbrt_hip_scene_create_with_shapes(PbrtHipContext* ctx, const float* positions, int32_t n_verts, const int32_t* indices,
                                       int32_t n_tris, const int32_t* tri_material, const PbrtMaterial* materials,
                                       int32_t n_materials, const int32_t* tri_light, const PbrtLight* lights,

@@ -647,6 +647,20 @@ static const char* shape_invalid(const PbrtShape& sh, int32_t n_materials, int32
         if (z0 > -sh.radius || z1 < sh.radius || sh.phi_max < 360.0f)
             return "a partial sphere cannot carry an area light (Sphere::sample covers the full sphere)";
     }
+    if (sh.type == PBRT_SHAPE_DISK && sh.light >= 0 && (sh.inner_radius > 0.0f || sh.phi_max < 360.0f))
+        return "a partial disk cannot carry an area light (Disk::sample covers the full disk)";
+    if (sh.light >= 0) {
+        // Transform::has_scale (pbrt-v3): each transformed axis keeps its length; the same bound on the axes' mutual dot products
+        // (no shear). Shape::area and the sphere's cone are object-space quantities used in world space.
+        const float* m = sh.to_world;
+        for (int a = 0; a < 3; ++a)
+            for (int b = a; b < 3; ++b) {
+                const float d = m[a] * m[b] + m[4 + a] * m[4 + b] + m[8 + a] * m[8 + b];
+                const float want = a == b ? 1.0f : 0.0f;
+                if (!(d > want - 0.001f && d < want + 0.001f))
+                    return "a shape under a transform that scales or shears cannot carry an area light (Shape::area is the object-space area)";
+            }
+    }
     return nullptr;
 }
 // Shape::area in object space: Sphere (sphere.rs:99-101), Disk (disk.rs:129-131), Cylinder after pbrt-v3 (D80)
@@ -673,7 +687,7 @@ static pb::DevShape shape_row(const PbrtShape& sh) {
     const float* m = sh.to_world;
     const float det = m[0] * (m[5] * m[10] - m[6] * m[9]) - m[1] * (m[4] * m[10] - m[6] * m[8]) + m[2] * (m[4] * m[9] - m[5] * m[8]);
     const bool reverse = sh.reverse_orientation != 0;
-    d.flags = sh.type | ((reverse != (det < 0.0f)) ? pb::kShapeFlipNormal : 0) | (reverse ? pb::kShapeReverse : 0);
+    d.flags = sh.type | ((reverse != (det < 0.0f)) ? pb::kShapeFlipNormal : 0);
     return d;
 }
 namespace pb {

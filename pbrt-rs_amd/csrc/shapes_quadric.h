@@ -12,8 +12,8 @@ namespace pb {
 
 constexpr int kShapeSphere = 0, kShapeDisk = 1, kShapeCylinder = 2;  // PbrtShapeType
 constexpr int kShapeTypeMask = 3;
-constexpr int kShapeFlipNormal = 4;  // reverse_orientation ^ transform_swaps_handedness: SurfaceInteraction::new flips n
-constexpr int kShapeReverse = 8;     // reverse_orientation alone: Shape::sample flips the sampled normal
+constexpr int kShapeFlipNormal = 4;  // reverse_orientation ^ transform_swaps_handedness: SurfaceInteraction::new flips n, and so
+                                     // does the shape's sampling as an area light (D85)
 
 // One row per shape (DevBVH::shapes). theta_min / theta_max are filled on the device (k_shape_angles: the kernels' own acos).
 struct DevShape {
@@ -23,7 +23,7 @@ struct DevShape {
     float theta_min, theta_max;  // sphere (Sphere::new, sphere.rs:222-223)
     float phi_max;               // radians
     float inner_radius;          // disk
-    int flags;                   // type | kShapeFlipNormal | kShapeReverse
+    int flags;                   // type | kShapeFlipNormal
     // the z range the hit test rejects against: the cylinder's [z_min, z_max]; a sphere tests a side only where it is short of
     // the pole (sphere.rs:273-274), so a side that reaches the pole is -inf / +inf here
     float z_clip_min, z_clip_max;

@@ -82,7 +82,10 @@ PB_DEV void sphere_light_sample(float cx, float cy, float cz, float radius, cons
 // ---- a row of the shape table (shapes_quadric.h) as the shape of a DiffuseAreaLight. Full sphere: Sphere::sample / sample2 /
 // pdf2 (sphere.rs:103-192) as above with p_centre = object_to_world * (0, 0, 0); disk: Disk::sample (disk.rs:133-149); cylinder:
 // pbrt-v3's Cylinder::Sample (unimplemented in the reference, D81); disk and cylinder through the Shape trait's sample2 / pdf2
-// (shape.rs:38-69). `area` = Shape::area, an object-space quantity as in pbrt-v3 (DevLight::area, set at creation). ----
+// (shape.rs:38-69). `area` = Shape::area, an object-space quantity as in pbrt-v3 (DevLight::area, set at creation): creation
+// refuses a shape light whose transform changes lengths (D86), so it is the world-space area too. The sampled normal is
+// flipped as SurfaceInteraction::new flips the hit's (kShapeFlipNormal, D85): a one-sided light emits to one side, whichever
+// estimator reaches it. ----
 PB_DEV V3 shape_point_to_world(const float* w, V3 p, V3 pe, V3* err) {  // Point3f::from((t, p, p_error, &mut error))
     const float g3 = kGamma3;
     err->x = (g3 + 1.0f) * (__builtin_fabsf(w[0] * pe.x) + __builtin_fabsf(w[1] * pe.y) + __builtin_fabsf(w[2] * pe.z)) +
@@ -136,7 +139,7 @@ PB_DEV void shape_light_sample(const DevShape& sh, float area, const Surf& sf, f
             V3 p_world = pc + n_world * radius;
             *p_o = p_world;
             *err_o = vabs(p_world) * kGamma5;
-            *n_o = (sh.flags & kShapeReverse) ? -n_world : n_world;
+            *n_o = (sh.flags & kShapeFlipNormal) ? -n_world : n_world;  // D85
             *pdf_o = 1.0f / (2.0f * kPi * (1.0f - cos_theta_max));
             return;
         }
@@ -178,7 +181,7 @@ PB_DEV void shape_light_sample(const DevShape& sh, float area, const Surf& sf, f
     // error bound: gamma(5) |p| (sphere), 0 (disk), gamma(3) |(x, y, 0)| (cylinder)
     const V3 oe = V3{__builtin_fabsf(px) * eg, __builtin_fabsf(py) * eg, type == kShapeSphere ? __builtin_fabsf(pz) * eg : 0.0f};
     V3 n = normalize(shape_normal_to_world(sh.w2o, V3{nx, ny, nz}));
-    if (sh.flags & kShapeReverse) n = -n;
+    if (sh.flags & kShapeFlipNormal) n = -n;  // the side make_surface_shape puts n on (D85)
     V3 err;
     V3 p = shape_point_to_world(sh.o2w, obj, oe, &err);
     float pdf = 1.0f / area;

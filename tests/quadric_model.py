@@ -213,6 +213,81 @@ def rays_at_unit_cube(n, seed):
     return o.astype(np.float32), d.astype(np.float32)
 
 
+# ---- the Lambert probe: a matte shape under three pairs of opposite distant lights ----
+PROBE_OFFSETS = (1e-3, 1e-4)  # how far a shadow ray's origin is pushed off the surface, both tried
+
+
+def occluded_from_surface(shape, p_obj, w):
+    """Does the shape block the world-space direction w (n, 3) seen from its own surface points p_obj (n, 3, object space)? The
+    ray starts ON the surface: a sphere's or cylinder's quadratic has the root 0 there (the point itself, not counted) and the
+    other root -b / a; a disk cannot block its own points. Returns (blocked, near), `near` as in intersect(): the other root
+    within REL of 0 (a tangent ray), or its point within REL of an edge of the cut."""
+    n_rays = len(p_obj)
+    blocked, near = np.zeros(n_rays, dtype=bool), np.zeros(n_rays, dtype=bool)
+    if shape["type"] == "disk":
+        return blocked, near
+    w2o = np.linalg.inv(shape["o2w"])
+    dd = np.asarray(w, dtype=np.float64) @ w2o[:3, :3].T
+    r = shape["radius"]
+    k = 3 if shape["type"] == "sphere" else 2
+    a = (dd[:, :k] ** 2).sum(axis=1)
+    b = 2.0 * (dd[:, :k] * p_obj[:, :k]).sum(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        t = np.where(a > 0.0, -b / a, -np.inf)
+        near |= (a <= 0.0) | (np.abs(t) <= REL * r / np.sqrt((dd ** 2).sum(axis=1)))
+        ahead = t > 0.0
+        p = p_obj + dd * np.where(ahead, t, 0.0)[:, None]
+        if shape["type"] == "sphere":
+            z_ok = ((shape["z_min"] <= -r) | (p[:, 2] >= shape["z_min"])) & ((shape["z_max"] >= r) | (p[:, 2] <= shape["z_max"]))
+            near_z = ((shape["z_min"] > -r) & (np.abs(p[:, 2] - shape["z_min"]) <= REL * r)) | \
+                     ((shape["z_max"] < r) & (np.abs(p[:, 2] - shape["z_max"]) <= REL * r))
+        else:
+            z_ok = (p[:, 2] >= shape["z_min"]) & (p[:, 2] <= shape["z_max"])
+            near_z = (np.abs(p[:, 2] - shape["z_min"]) <= REL * r) | (np.abs(p[:, 2] - shape["z_max"]) <= REL * r)
+        phi = _phi(p)
+        near |= ahead & (near_z | _near_phi(shape, phi))
+        blocked = ahead & z_ok & (phi <= shape["phi_max"])
+    return blocked, near
+
+
+def lambert_probe(shape, o, d, axes):
+    """A matte shape under six distant lights along +-axes[:, k] (axes: 3x3, orthonormal columns), the pair of column k
+    emitting in colour channel k alone. For the world-space rays o, d: what one surface interaction of direct lighting returns
+    in channel k is rho / pi * L * expect[:, k].
+
+    expect[:, k] = |n . a_k| when the light of pair k on the viewer's side of the surface is not shadowed by the shape itself,
+    else 0 (the light on the far side never contributes to a matte surface). Shadowing: a float64 ray from the world-space hit
+    point pushed along the viewer-side normal by each of PROBE_OFFSETS, and the ray from the surface point itself
+    (occluded_from_surface: the device pushes its ray by a few ulps only, and between offset 0 and the smaller offset the far
+    end of a slanting ray still moves by about that offset). A ray is `clear` when all three give one verdict and none is
+    flagged near. Returns a dict of arrays over the rays: hit, near (of the primary hit), n (the model's world-space normal),
+    expect (n, 3), shadowed (n, 3; the common verdict), keep (a hit that is not near and whose three shadow rays are clear).
+    Which light of a pair is "on the viewer's side" flips where n . a_k = 0; the value is continuous through 0 there, so that
+    decision excludes nothing."""
+    o64, d64 = np.asarray(o, dtype=np.float64), np.asarray(d, dtype=np.float64)
+    m = intersect(shape, o, d)
+    hit = m["hit"]
+    idx = np.flatnonzero(hit)
+    n = m["n"][idx]
+    side = np.where((n * d64[idx]).sum(axis=1) < 0.0, 1.0, -1.0)
+    nv = n * side[:, None]  # the normal on the viewer's side
+    p_w = m["p"][idx] @ shape["o2w"][:3, :3].T + shape["o2w"][:3, 3]
+    cos = n @ axes
+    toward = np.where(nv @ axes >= 0.0, 1.0, -1.0)  # which light of each pair is on the viewer's side
+    expect = np.zeros((len(o64), 3))
+    shadowed = np.zeros((len(o64), 3), dtype=bool)
+    clear = np.ones((len(o64), 3), dtype=bool)
+    for k in range(3):
+        w = toward[:, k, None] * axes[:, k]
+        verdicts = [intersect(shape, p_w + eps * nv, w) for eps in PROBE_OFFSETS]
+        blocked, blocked_near = occluded_from_surface(shape, m["p"][idx], w)
+        ok = ~blocked_near & ~verdicts[0]["near"] & ~verdicts[1]["near"] & (verdicts[0]["hit"] == blocked) & (verdicts[1]["hit"] == blocked)
+        shadowed[idx, k] = blocked
+        clear[idx, k] = ok
+        expect[idx, k] = np.where(blocked, 0.0, np.abs(cos[:, k]))
+    return dict(hit=hit, n=m["n"], expect=expect, shadowed=shadowed, keep=hit & ~m["near"] & clear.all(axis=1), near=m["near"])
+
+
 # ---- closed forms of the area-light tests ----
 def disk_light_floor_radiance(rho, L, R, h):
     """Radiance leaving a Lambertian floor point (albedo rho) under the centre of a disk light of radius R at height h that
@@ -225,3 +300,40 @@ def cylinder_light_centre_radiance(rho, L, R, H):
     normal along the axis: the cylinder fills the hemisphere below polar angle atan(R / H) ... pi / 2, i.e.
     E = pi L (1 - sin^2(theta_0)) with tan(theta_0) = R / H, Lo = rho L H^2 / (H^2 + R^2)."""
     return rho * L * H * H / (H * H + R * R)
+
+
+def partial_cylinder_light_centre_radiance(rho, L, R, H, phi_max):
+    """The same under a cylinder cut to the sweep phi_max (radians): the patch's cosine does not depend on the azimuth, so every
+    sector of the cylinder gives the irradiance its angle's share."""
+    return cylinder_light_centre_radiance(rho, L, R, H) * phi_max / TWO_PI
+
+
+def sphere_light_floor_radiance(rho, L, R, d):
+    """A sphere of radius R whose centre is d > R above the floor point along the floor's normal: it fills the cone of
+    sin(theta_max) = R / d about the normal, E = pi L sin^2(theta_max), Lo = rho L (R / d)^2."""
+    return rho * L * (R / d) ** 2
+
+
+def annulus_light_floor_radiance(rho, L, R, Ri, h):
+    """disk_light_floor_radiance of the disk of radius R less that of the hole of radius Ri."""
+    return disk_light_floor_radiance(rho, L, R, h) - disk_light_floor_radiance(rho, L, Ri, h)
+
+
+def patch_radiance_by_quadrature(shape, p, n_p, rho, L, cells=400):
+    """Radiance leaving a Lambertian patch (albedo rho) at the world-space point p with normal n_p under the shape as a
+    two-sided diffuse emitter of radiance L that nothing shadows: rho / pi * L * integral of max(0, cos_p) |cos_s| / r^2 dA by
+    the midpoint rule over cells x cells cells of the shape's parametrisation (surface_points), through its transform."""
+    u = (np.arange(cells) + 0.5) / cells
+    uu, vv = np.meshgrid(u, u, indexing="ij")
+    m, h = shape["o2w"], 1e-6
+
+    def world(a, b):
+        return surface_points(shape, a, b) @ m[:3, :3].T + m[:3, 3]
+
+    q = world(uu, vv)
+    normal_da = np.cross((world(uu + h, vv) - world(uu - h, vv)) / (2 * h), (world(uu, vv + h) - world(uu, vv - h)) / (2 * h))
+    w = q - np.asarray(p, dtype=np.float64)
+    r2 = (w ** 2).sum(axis=-1)
+    cos_p = np.maximum((w * np.asarray(n_p, dtype=np.float64)).sum(axis=-1), 0.0) / np.sqrt(r2)
+    cos_s_da = np.abs((w * normal_da).sum(axis=-1)) / np.sqrt(r2)
+    return rho / np.pi * L * (cos_p * cos_s_da / r2).mean()

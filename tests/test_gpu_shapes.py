@@ -1,6 +1,8 @@
 """Disk, Cylinder and the general Sphere on the device (pbrt_hip_scene_create_with_shapes): the translated-sphere path pinned bit
-for bit, intersection against the float64 model of quadric_model.py, any-hit against closest-hit, the convex-body furnace, the
-closed forms of a disk light and a cylinder light, and the creation errors."""
+for bit, intersection against the float64 model of quadric_model.py, any-hit against closest-hit, the surface normal and the
+shadow rays' start through Lambert's law under six distant lights, the side a one-sided shape light emits to, the convex-body
+furnace (also far from the origin, tiny and huge), the closed forms of disk, cylinder and sphere lights (partial cylinder, rotated
+sphere, mirrored one-sided disk) with the estimators' mutual agreement, and the creation errors."""
 import numpy as np
 import pytest
 
@@ -8,7 +10,7 @@ import pbrt_hip
 from pbrt_hip import scenes
 
 import quadric_model as qm
-from test_quadric_model import TRANSFORMS, RECORDS, translate, rot, scale
+from test_quadric_model import TRANSFORMS, RECORDS, ORTHONORMAL_MIRROR, PROBE_AXES, PROBE_RAYS, probe_exclusion, translate, rot, scale
 
 pytestmark = pytest.mark.gpu
 
@@ -176,12 +178,132 @@ def test_closest_of_several_shapes_and_triangles(hip_ctx):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# 3a. the normal, through Lambert's law
+# ---------------------------------------------------------------------------------------------------------------------
+# The shape, matte, under six distant lights along +-PROBE_AXES[:, k], pair k emitting in channel k alone: one surface interaction
+# of direct lighting returns rho / pi * L * |n . a_k| in channel k (qm.lambert_probe), or exactly 0 where the shape shadows the
+# light on the viewer's side. Delta lights under UniformSampleAll: no random number reaches the result. A wrong normal matrix
+# (transposed, not inverted: invisible to a furnace), a wrong dpdv or a swapped cross product changes |n . a_k|; a shadow ray
+# started on the wrong side of an open shape, or any-hit disagreeing with the model, changes which channels are 0.
+#
+# Tolerance of |rgb_k pi / (rho L) - expected_k| (a quantity in [0, 1]), measured and not chosen, as T_TOL above: the same probe on
+# the translated-sphere path (scene["spheres"]; radii 0.3, 0.65 and 1.0 at the offsets below, the same 20 000 rays each) deviated
+# from the model by at most NORMAL_PROBE_SPHERE_PATH_WORST. A shape is allowed N_FACTOR times that times the condition number
+# of its transform's linear part: the inverse transpose and the renormalisation amplify an object-space error of the normal
+# by at most cond_2, and the factor covers the extra products of a general matrix as T_FACTOR does.
+NORMAL_PROBE_SPHERE_PATH_WORST = 4.9379e-05  # gfx950 (MI355X): 4.937854e-05 (r 0.3; 2.684e-05 at r 0.65, 1.007e-05 at r 1.0), rounded up
+N_FACTOR = 4.0
+PROBE_RHO, PROBE_L = 0.5, 3.0
+PROBE_SPHERES = ((0.3, (0.3, -0.2, 0.4)), (0.65, (-0.2, 0.1, 0.15)), (1.0, (0.0, 0.0, 0.0)))  # radius, centre
+
+
+def probe_lights():
+    rows = []
+    for k in range(3):
+        colour = np.zeros(3)
+        colour[k] = PROBE_L
+        rows += [scenes.distant_light(sign * PROBE_AXES[:, k], colour) for sign in (1.0, -1.0)]
+    return rows
+
+
+def normal_probe(hip_ctx, name, sc, model_shape):
+    """Runs the probe on the scene; returns (worst deviation over the channels, worst | |n| - 1 |, the model's probe, the
+    recovered |n . a_k|) after asserting what does not depend on a tolerance: the exclusion caps, misses, and the exact zeros."""
+    o, d = qm.rays_at_unit_cube(*PROBE_RAYS)
+    g = pbrt_hip.Scene(hip_ctx, sc)
+    rgb, _ = g.li(as_rays(o, d), np.arange(len(o), dtype=np.uint64) + 1, integrator=pbrt_hip.INTEGRATOR_DIRECT, max_depth=1, light_strategy=0)
+    g.close()
+    got = rgb.astype(np.float64) * (np.pi / (PROBE_RHO * PROBE_L))
+    m = qm.lambert_probe(model_shape, o, d, PROBE_AXES)
+    keep = m["keep"]
+    near, shadow_excluded = probe_exclusion(m)
+    lit = keep & ~m["shadowed"].any(axis=1)
+    worst = np.abs(got[keep] - m["expect"][keep]).max()
+    worst_len = np.abs(np.sqrt((got[lit] ** 2).sum(axis=1)) - 1.0).max()
+    on_shadowed = got[keep][m["shadowed"][keep]]
+    print(f"{name}: kept {keep.sum()} of {m['hit'].sum()} hits (near {near:.5f} of the batch, shadow rule {shadow_excluded:.5f} of the rest), "
+          f"shadowed channels {len(on_shadowed)}, worst deviation {worst:.3e}, worst | |n| - 1 | {worst_len:.3e}, "
+          f"nonzero on shadowed {np.count_nonzero(on_shadowed)}")
+    assert near <= 0.01 and shadow_excluded <= 0.01 and keep.sum() >= 1000, name
+    assert (rgb[~m["hit"] & ~m["near"]] == 0.0).all(), name  # nothing else in the scene reflects
+    assert (on_shadowed == 0.0).all(), (name, np.flatnonzero(on_shadowed)[:5])
+    return worst, worst_len, m, got
+
+
+def test_normal_probe_on_the_sphere_path_is_the_recorded_baseline(hip_ctx):
+    worst = 0.0
+    for radius, centre in PROBE_SPHERES:
+        sc = shape_scene([], lights=probe_lights())
+        del sc["shapes"]
+        sc["spheres"] = np.array([[*centre, radius, 0, -1, 0, 0]], dtype=np.float32)
+        dev, dev_len, m, _ = normal_probe(hip_ctx, f"sphere path r {radius}", sc, qm.make("sphere", radius, -radius, radius, o2w=translate(*centre)))
+        assert not m["shadowed"][m["keep"]].any()
+        worst = max(worst, dev, dev_len)
+    print(f"sphere path: worst deviation of the normal probe {worst:.6e} (recorded {NORMAL_PROBE_SPHERE_PATH_WORST:.6e})")
+    assert worst <= NORMAL_PROBE_SPHERE_PATH_WORST
+
+
+@pytest.mark.parametrize("name,rec", RECORDS, ids=[r[0] for r in RECORDS])
+def test_normals_through_lamberts_law(hip_ctx, name, rec):
+    model_shape = qm.from_record(rec[0])
+    cond = np.linalg.cond(model_shape["o2w"][:3, :3], 2)
+    tol = N_FACTOR * NORMAL_PROBE_SPHERE_PATH_WORST * cond
+    worst, worst_len, m, _ = normal_probe(hip_ctx, name, shape_scene([rec], lights=probe_lights()), model_shape)
+    print(f"{name}: cond {cond:.3f}, allowed {tol:.3e}")
+    if not name.startswith("disk") and not name.endswith("-360"):
+        assert m["shadowed"][m["keep"]].any(axis=1).sum() > 300, name  # the open shapes do put hits in their own shadow
+    assert worst <= tol, (name, worst, tol)
+    assert worst_len <= tol, (name, worst_len, tol)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 3b. the side a one-sided shape light emits to
+# ---------------------------------------------------------------------------------------------------------------------
+EMITTERS = {
+    "sphere": lambda **kw: scenes.sphere_shape(0.7, **kw),
+    "cylinder": lambda **kw: scenes.cylinder(0.5, -0.6, 0.7, **kw),
+    "disk": lambda **kw: scenes.disk(0.1, 0.9, **kw),
+}
+EMITTER_PLACES = {"rigid": TRANSFORMS["rigid"], "mirror": ORTHONORMAL_MIRROR}
+BLACK_MATTE = [(scenes.MAT_MATTE, (0.0, 0.0, 0.0), (0, 0, 0), 1.0)]
+
+
+@pytest.mark.parametrize("reverse", [False, True], ids=["as-made", "reversed"])
+@pytest.mark.parametrize("place", list(EMITTER_PLACES))
+@pytest.mark.parametrize("kind", list(EMITTERS))
+def test_one_sided_light_emits_to_the_normals_side(hip_ctx, kind, place, reverse):
+    """Emitted radiance alone (path integrator, no bounce) seen by a primary ray: LE where the model's normal (pbrt-v3's:
+    flipped by reverse_orientation ^ swaps_handedness) faces the ray's origin, 0 on the other side, both exactly."""
+    to_world = EMITTER_PLACES[place]
+    rec = EMITTERS[kind](to_world=to_world, light=0, reverse_orientation=reverse)
+    le = np.float32([LE, 0.5 * LE, 0.25 * LE])
+    sc = shape_scene([rec], materials=scenes._materials(BLACK_MATTE), lights=[(scenes.LIGHT_DIFFUSE_AREA, tuple(le), 1, 0, 1)])
+    o, d = qm.rays_at_unit_cube(20_000, 29)
+    # a closed sphere shows rays from outside one side only: a tenth of the rays start inside the shape's hollow instead
+    o_obj = np.random.default_rng(3).uniform(-0.2, 0.2, size=(2000, 3))
+    o[:2000] = (o_obj @ to_world[:3, :3].T + to_world[:3, 3]).astype(np.float32)
+    g = pbrt_hip.Scene(hip_ctx, sc)
+    rgb, _ = g.li(as_rays(o, d), np.arange(len(o), dtype=np.uint64) + 5, integrator=pbrt_hip.INTEGRATOR_PATH, max_depth=0)
+    g.close()
+    m = qm.intersect(qm.from_record(rec[0]), o, d)
+    cos = -(m["n"] * d.astype(np.float64)).sum(axis=1)
+    sure = m["hit"] & ~m["near"] & (np.abs(cos) >= 1e-3)
+    front, back = sure & (cos > 0.0), sure & (cos < 0.0)
+    print(f"{kind} {place} reverse {reverse}: {front.sum()} rays on the emitting side, {back.sum()} on the other, "
+          f"wrong on the emitting side {(rgb[front] != le).any(axis=1).sum()}, wrong on the other {(rgb[back] != 0.0).any(axis=1).sum()}")
+    assert front.sum() >= 300 and back.sum() >= 300
+    assert (rgb[front] == le).all()
+    assert (rgb[back] == 0.0).all()
+    assert (rgb[~m["hit"] & ~m["near"]] == 0.0).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # 4. convex-body furnace
 # ---------------------------------------------------------------------------------------------------------------------
-def furnace(hip_ctx, rec, view_dir, up, half=1.0, spp=64, res=32):
-    """res x res parallel rays through the pixel centres of a [-half, half]^2 window looking along view_dir, spp
-    Integrator::li samples each (direct lighting, constant environment Le = 1, matte 0.5). Returns per-pixel mean, standard
-    error, and the mask of pixels the model puts at least one pixel inside the silhouette."""
+def furnace(hip_ctx, rec, view_dir, up, half=1.0, spp=64, res=32, centre=(0.0, 0.0, 0.0)):
+    """res x res parallel rays through the pixel centres of a [-half, half]^2 window about `centre` looking along view_dir
+    from 4 * half away, spp Integrator::li samples each (direct lighting, constant environment Le = 1, matte 0.5). Returns
+    per-pixel mean, standard error, and the mask of pixels the model puts at least one pixel inside the silhouette."""
     w = np.asarray(view_dir, dtype=np.float64)
     w /= np.linalg.norm(w)
     r = np.cross(np.asarray(up, dtype=np.float64), w)
@@ -191,7 +313,7 @@ def furnace(hip_ctx, rec, view_dir, up, half=1.0, spp=64, res=32):
     px, py = np.meshgrid(c, c, indexing="xy")
 
     def origins(dx, dy):
-        return (-4.0 * w + (px.reshape(-1, 1) + dx) * r + (py.reshape(-1, 1) + dy) * u).astype(np.float32)
+        return (np.asarray(centre, dtype=np.float64) - 4.0 * half * w + (px.reshape(-1, 1) + dx) * r + (py.reshape(-1, 1) + dy) * u).astype(np.float32)
 
     d = np.tile(w.astype(np.float32), (res * res, 1))
     shape = qm.from_record(rec[0])
@@ -226,6 +348,37 @@ FURNACE = {
 def test_convex_body_furnace(hip_ctx, name):
     rec, view, up = FURNACE[name]
     mean, se, inside = furnace(hip_ctx, rec, view, up)
+    assert inside.sum() > 150, (name, inside.sum())
+    dev = np.abs(mean[inside] - 0.5)
+    print(f"{name}: {inside.sum()} pixels inside, worst |mean - 0.5| {dev.max():.4f}, worst in sigma {np.max(dev / np.maximum(se[inside], 1e-12)):.2f}, "
+          f"darkest {mean[inside].min():.4f}")
+    assert (dev <= 4.0 * se[inside] + 1e-6).all(), (name, np.flatnonzero(dev > 4.0 * se[inside] + 1e-6)[:8])
+
+
+def placed(rec, m):
+    """The record under m @ its own to_world."""
+    return scenes._shape(int(rec[0]["type"]), rec[0]["radius"], rec[0]["z_min"], rec[0]["z_max"], rec[0]["inner_radius"], rec[0]["phi_max"],
+                         m @ rec[0]["to_world"].astype(np.float64).reshape(4, 4), int(rec[0]["material"]), int(rec[0]["light"]),
+                         bool(rec[0]["reverse_orientation"]))
+
+
+# name -> (shape of FURNACE, the transform put in front of its own, the window's half size): p_error has to follow the
+# translation (|p| ~ 600: the bound is 1e4 times the one at the origin) and the scale, and offset_ray_origin has to use it in
+# world space; a shadow ray that starts inside the surface gives a dark pixel
+FAR = translate(300.0, -200.0, 500.0)
+FURNACE_PLACED = {
+    "ellipsoid-far": ("ellipsoid", FAR, 1.0),
+    "disk-far": ("disk-front", FAR, 1.0),
+    "ellipsoid-tiny": ("ellipsoid", scale(0.01, 0.01, 0.01), 0.01),
+    "ellipsoid-huge": ("ellipsoid", scale(50.0, 50.0, 50.0), 50.0),
+}
+
+
+@pytest.mark.parametrize("name", list(FURNACE_PLACED))
+def test_convex_body_furnace_at_placement_extremes(hip_ctx, name):
+    base, m, half = FURNACE_PLACED[name]
+    rec, view, up = FURNACE[base]
+    mean, se, inside = furnace(hip_ctx, placed(rec, m), view, up, half=half, centre=m[:3, 3])
     assert inside.sum() > 150, (name, inside.sum())
     dev = np.abs(mean[inside] - 0.5)
     print(f"{name}: {inside.sum()} pixels inside, worst |mean - 0.5| {dev.max():.4f}, worst in sigma {np.max(dev / np.maximum(se[inside], 1e-12)):.2f}, "
@@ -304,6 +457,116 @@ def test_cylinder_light_closed_form(hip_ctx):
     assert abs(est["path"][0] - est["direct"][0]) <= 4.0 * np.hypot(est["path"][1], est["direct"][1])
 
 
+EMITTER_MATS = [(scenes.MAT_MATTE, (RHO, RHO, RHO), (0, 0, 0), 1.0), (scenes.MAT_NONE, (0, 0, 0), (0, 0, 0), 1.0)]  # 0: floor / patch, 1: emitter
+ESTIMATORS = {
+    "direct-all": dict(integrator=pbrt_hip.INTEGRATOR_DIRECT, max_depth=2, light_strategy=0),
+    "direct-one": dict(integrator=pbrt_hip.INTEGRATOR_DIRECT, max_depth=2, light_strategy=1),
+    "path": dict(integrator=pbrt_hip.INTEGRATOR_PATH, max_depth=1, light_strategy=1),
+}
+
+
+@pytest.mark.parametrize("phi_max", [200.0, 90.0])
+def test_partial_cylinder_light_closed_form(hip_ctx, phi_max):
+    """test_cylinder_light_closed_form with the cylinder cut to a sweep: Cylinder::sample draws phi in [0, phi_max] and the
+    area counts the same part, so the sector's share of the full cylinder's irradiance arrives (the patch's cosine does not
+    depend on the azimuth)."""
+    R, H = 0.8, 1.1
+    axis_up = rot((1, 0, 0), -90.0)  # object +z -> world +y
+    move = translate(0.2, -0.1, 0.3)
+    recs = [scenes.cylinder(R, -H, H, phi_max=phi_max, to_world=move @ axis_up @ rot((0, 0, 1), 20.0), material=1, light=0),
+            scenes.disk(0.0, 0.05, to_world=move @ axis_up @ translate(0.02, 0.01, 0.0), material=0)]
+    sc = shape_scene(recs, materials=scenes._materials(EMITTER_MATS), lights=[(scenes.LIGHT_DIFFUSE_AREA, (LE, LE, LE), 1, 1, 1)])
+    expect = qm.partial_cylinder_light_centre_radiance(RHO, LE, R, H, np.radians(phi_max))
+    centre = move[:3, 3]
+    eye = centre + np.array([0.1, 0.5, 0.15])
+    est = {}
+    for name in ("path", "direct-one"):
+        est[name] = li_mean(hip_ctx, sc, eye, centre - eye, **ESTIMATORS[name])
+        print(f"cylinder light phi_max {phi_max}, {name}: {est[name][0]:.5f} +- {est[name][1]:.5f}, closed form {expect:.5f}")
+        assert abs(est[name][0] - expect) <= 4.0 * est[name][1], name
+    assert abs(est["path"][0] - est["direct-one"][0]) <= 4.0 * np.hypot(est["path"][1], est["direct-one"][1])
+
+
+@pytest.mark.parametrize("ratio", [0.5, 0.1, 0.02])
+def test_rotated_sphere_light_closed_form(hip_ctx, ratio):
+    """A full sphere light under a rotation and a translation (Sphere::sample2's cone about object_to_world * (0, 0, 0)) above
+    a floor point: Lo = rho L (R / d)^2. R / d = 0.02 takes the small-angle branch of the cone sampling (sin^2(theta_max) =
+    0.0004 < 0.00068523; at 0.1 it is 0.01, still the general branch). That branch is pbrt's approximation and float32's limit,
+    not an exact estimator: it draws sin^2(theta) uniformly (off the uniform cone by O(sin^2(theta_max))) and its pdf divides by
+    1 - cos(theta_max) = 2e-4, formed from a float32 next to 1 (cos(theta_max) carries up to 1.5 * 2^-24: the rounding of
+    1 - sin^2 halved by the root, and the root's own). Allowed there, beside 4 se: (sin^2(theta_max) + 1.5 * 2^-24 /
+    (1 - cos(theta_max))) of the value, 8.5e-4 of it; a wrong centre or radius is off by a multiple of the value."""
+    d = 1.5
+    p0 = np.array([0.3, 0.0, -0.2])
+    eye = p0 + np.array([0.8, 0.5, 0.4])
+    R = ratio * d
+    rec = scenes.sphere_shape(R, to_world=translate(p0[0], d, p0[2]) @ rot((1, 2, 3), 40.0), material=1, light=0)
+    sc = shape_scene([rec], materials=scenes._materials(EMITTER_MATS), lights=[(scenes.LIGHT_DIFFUSE_AREA, (LE, LE, LE), 2, 0, 1)],
+                     extra=floor_quad(20.0))
+    expect = qm.sphere_light_floor_radiance(RHO, LE, R, d)
+    rounding = (ratio ** 2 + 1.5 * 2.0 ** -24 / (1.0 - np.sqrt(1.0 - ratio ** 2))) * expect if ratio == 0.02 else 0.0
+    est = {}
+    for name in ESTIMATORS:
+        est[name] = li_mean(hip_ctx, sc, eye, p0 - eye, **ESTIMATORS[name])
+        print(f"sphere light R/d {ratio}, {name}: {est[name][0]:.7f} +- {est[name][1]:.7f}, closed form {expect:.7f}")
+        assert abs(est[name][0] - expect) <= 4.0 * est[name][1] + rounding, name
+    assert abs(est["path"][0] - est["direct-one"][0]) <= 4.0 * np.hypot(est["path"][1], est["direct-one"][1]) + rounding
+
+
+@pytest.mark.parametrize("reverse", [False, True], ids=["as-made", "reversed"])
+def test_mirrored_one_sided_sphere_light(hip_ctx, reverse):
+    """The sphere's cone sampling orients its normal by itself: under a mirror that keeps lengths the normal points inward
+    (the light is dark from outside, exactly) unless reverse_orientation turns it outward again (the closed form)."""
+    d, ratio = 1.5, 0.5
+    p0 = np.array([0.3, 0.0, -0.2])
+    eye = p0 + np.array([0.8, 0.5, 0.4])
+    rec = scenes.sphere_shape(ratio * d, to_world=translate(p0[0], d, p0[2]) @ rot((1, 2, 3), 40.0) @ scale(1.0, -1.0, 1.0), material=1, light=0,
+                              reverse_orientation=reverse)
+    n = qm.intersect(qm.from_record(rec[0]), p0[None, :], np.array([[0.0, 1.0, 0.0]]))["n"][0]
+    assert (n[1] < 0.0) == reverse  # outward at the sphere's lowest point is -y
+    sc = shape_scene([rec], materials=scenes._materials(EMITTER_MATS), lights=[(scenes.LIGHT_DIFFUSE_AREA, (LE, LE, LE), 2, 0, 1)],
+                     extra=floor_quad(20.0))
+    expect = qm.sphere_light_floor_radiance(RHO, LE, ratio * d, d) if reverse else 0.0
+    for name in ESTIMATORS:
+        mean, se = li_mean(hip_ctx, sc, eye, p0 - eye, **ESTIMATORS[name])
+        print(f"mirrored sphere light reverse {reverse}, {name}: {mean:.6f} +- {se:.6f}, closed form {expect:.6f}")
+        if reverse:
+            assert abs(mean - expect) <= 4.0 * se, (name, mean, se, expect)
+        else:
+            assert mean == 0.0, (name, mean)
+
+
+@pytest.mark.parametrize("reverse", [False, True], ids=["as-made", "reversed"])
+def test_mirrored_one_sided_disk_light_closed_form(hip_ctx, reverse):
+    """test_disk_light_closed_form under a mirror that keeps lengths. The emitting side is the normal's of
+    test_one_sided_light_emits_to_the_normals_side (the model's: flipped by reverse_orientation ^ swaps_handedness): turned to
+    the floor, light sampling and BSDF sampling must both see it emit (the closed form, by every estimator); turned away,
+    neither may (exactly 0)."""
+    h = R = 1.2
+    p0 = np.array([0.3, 0.0, -0.2])
+    eye = p0 + np.array([0.4, 0.9, 0.3])
+    expect = qm.disk_light_floor_radiance(RHO, LE, R, h)
+    seen = set()
+    for turn in (90.0, -90.0):  # object +z to world -y, to world +y
+        to_world = translate(p0[0], h, p0[2]) @ rot((1, 0, 0), turn) @ rot((0, 0, 1), 63.0) @ scale(1.0, -1.0, 1.0)
+        rec = scenes.disk(0.0, R, to_world=to_world, material=1, light=0, reverse_orientation=reverse)
+        n = qm.intersect(qm.from_record(rec[0]), p0[None, :], np.array([[0.0, 1.0, 0.0]]))["n"][0]
+        assert abs(abs(n[1]) - 1.0) < 1e-6
+        facing = n[1] < 0.0
+        seen.add(facing)
+        sc = shape_scene([rec], materials=scenes._materials(EMITTER_MATS), lights=[(scenes.LIGHT_DIFFUSE_AREA, (LE, LE, LE), 2, 0, 1)],
+                         extra=floor_quad(20.0))
+        for name in ESTIMATORS:
+            mean, se = li_mean(hip_ctx, sc, eye, p0 - eye, **ESTIMATORS[name])
+            print(f"mirrored disk light reverse {reverse} {'facing' if facing else 'facing away'}, {name}: {mean:.5f} +- {se:.5f}, "
+                  f"closed form {expect if facing else 0.0:.5f}")
+            if facing:
+                assert abs(mean - expect) <= 4.0 * se, (name, mean, se, expect)
+            else:
+                assert mean == 0.0, (name, mean)
+    assert seen == {True, False}
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # 7. creation errors
 # ---------------------------------------------------------------------------------------------------------------------
@@ -331,7 +594,15 @@ def test_creation_refusals_leave_the_context_usable(hip_ctx):
         "unknown type": (bad(type=3), ()),
         "sphere short in z with a light": (bad(_sphere=True, _args=dict(z_max=0.3, light=0)), area),
         "sphere short in phi with a light": (bad(_sphere=True, _args=dict(phi_max=270.0, light=0)), area),
+        # Disk::sample covers the full disk (D87); Shape::area is the object-space area (D86)
+        "annulus with a light": (bad(light=0), area),
+        "disk sector with a light": (bad(inner_radius=0.0, phi_max=270.0, light=0), area),
+        "scaled sphere with a light": (bad(_sphere=True, _args=dict(to_world=scale(2.0, 2.0, 2.0), light=0)), area),
+        "stretched sphere with a light": (bad(_sphere=True, _args=dict(to_world=rot((1, 2, 3), 40.0) @ scale(1.0, 1.0, 1.01), light=0)), area),
+        "sheared sphere with a light": (bad(_sphere=True, _args=dict(to_world=np.array([[1, 0.01, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1.0]]), light=0)), area),
     }
+    says = {"annulus with a light": "partial disk", "disk sector with a light": "partial disk", "scaled sphere with a light": "scales or shears",
+            "stretched sphere with a light": "scales or shears", "sheared sphere with a light": "scales or shears"}
     # the tree over a good record's bounds, so that every record reaches the creation call itself (the binding's own bounds call
     # refuses an unknown type before that)
     tri = FAR_TRIANGLE["positions"][FAR_TRIANGLE["indices"]]
@@ -342,9 +613,16 @@ def test_creation_refusals_leave_the_context_usable(hip_ctx):
             pbrt_hip.Scene(hip_ctx, shape_scene([rec], lights=lights), bvh=tree)
         msg = str(e.value)
         assert "pbrt_hip_scene_create_with_shapes" in msg and len(msg.split(":", 1)[-1].strip()) > 0, (name, msg)
+        assert says.get(name, "") in msg, (name, msg)
         assert not hip_ctx.is_lost(), name
     with pytest.raises(pbrt_hip.PbrtHipError):  # "spheres" and "shapes" in one scene
         pbrt_hip.Scene(hip_ctx, dict(shape_scene([scenes.disk(0.0, 0.5)]), spheres=np.array([[0, 0, 0, 1.0, 0, -1, 0, 0]], dtype=np.float32)))
+    # the same shapes without the light are good, and so is a light under a mirror that keeps lengths
+    for name in says:
+        rec = cases[name][0].copy()
+        rec["light"] = -1
+        pbrt_hip.Scene(hip_ctx, shape_scene([rec])).close()
+    pbrt_hip.Scene(hip_ctx, shape_scene([scenes.sphere_shape(0.5, to_world=ORTHONORMAL_MIRROR, light=0)], lights=area)).close()
     # the same context still creates and traces a good scene, and the other limits are reported
     g = pbrt_hip.Scene(hip_ctx, shape_scene([scenes.sphere_shape(0.5, light=0)], lights=area))
     hit = g.intersect(as_rays(np.float32([[0, 0, 3]]), np.float32([[0, 0, -1]])))

@@ -1,5 +1,6 @@
 """The float64 quadric model against itself, pbrt_hip_shape_world_bounds against the model and against the float32
-corner-transform union, and the share of rays the GPU tests' generator puts next to a decision boundary. No GPU."""
+corner-transform union, the share of rays the GPU tests' generator puts next to a decision boundary (of the hit test and of
+the Lambert probe's shadow rays), and the area lights' closed forms against a quadrature. No GPU."""
 import numpy as np
 import pytest
 
@@ -35,6 +36,12 @@ TRANSFORMS = {
     "scaled": translate(-0.1, 0.1, 0.0) @ rot((0, 1, 1), 25.0) @ scale(1.0, 0.6, 1.4),
     "mirrored": translate(0.1, 0.0, -0.1) @ rot((1, 0, 1), 70.0) @ scale(1.0, -0.8, 1.1),
 }
+
+# a mirror that neither scales nor shears (TRANSFORMS["mirrored"] also scales): swaps handedness, keeps lengths and areas
+ORTHONORMAL_MIRROR = translate(0.15, -0.1, 0.2) @ rot((2, 1, -1), 65.0) @ scale(1.0, -1.0, 1.0)
+# the Lambert probe's light axes: a generic rotation keeps every light off every object axis of every transform above
+PROBE_AXES = rot((3, -1, 2), 57.0)[:3, :3]
+PROBE_RAYS = (20_000, 23)  # qm.rays_at_unit_cube(*PROBE_RAYS)
 
 
 def shape_records():
@@ -160,3 +167,79 @@ def test_ray_generator_stays_within_the_near_cap(kind):
         worst = max(worst, share)
         assert r["hit"].mean() > 0.01
     assert worst <= 0.01
+
+
+def probe_exclusion(probe):
+    """(share of the batch the hit test flags near, share of the remaining hits whose shadow rays are not clear)."""
+    comparable = probe["hit"] & ~probe["near"]
+    return probe["near"].mean(), 1.0 - probe["keep"].sum() / comparable.sum()
+
+
+@pytest.mark.parametrize("kind", ["sphere", "disk", "cylinder"])
+def test_lambert_probe_stays_within_the_exclusion_cap(kind):
+    """The GPU normal test compares hits that are not near and whose three shadow rays are clear (two offsets and the ray from
+    the surface itself agree, none near), and asserts that the shadow rule excludes at most 1 % of the hits it could compare
+    (and the hit test's near flag at most 1 % of the batch, as above); here the same rays, shapes and lights with the model
+    alone. Measured: worst shadow-rule share 0.97 % (cylinder-mirrored-135; 0.89 % with the two offsets alone), fewest kept
+    hits 1108 (disk-scaled-135); a shape that cannot shadow itself (disk) loses up to 0.49 % to the near flag of the
+    offset ray's own start."""
+    o, d = qm.rays_at_unit_cube(*PROBE_RAYS)
+    worst_near = worst_shadow = 0.0
+    fewest = len(o)
+    for name, rec in RECORDS:
+        if not name.startswith(kind):
+            continue
+        s = qm.from_record(rec[0])
+        r = qm.lambert_probe(s, o, d, PROBE_AXES)
+        near, shadow = probe_exclusion(r)
+        k = r["keep"]
+        print(f"{name}: hits {r['hit'].sum()} near {near:.5f} shadow rule excludes {shadow:.5f} kept {k.sum()} "
+              f"with a shadowed channel {r['shadowed'][k].any(axis=1).mean():.3f}")
+        worst_near, worst_shadow, fewest = max(worst_near, near), max(worst_shadow, shadow), min(fewest, k.sum())
+        # what the model hands the GPU test: unit normals, values in [0, 1], 0 exactly where shadowed
+        assert np.abs(np.sqrt((r["n"][k] ** 2).sum(axis=1)) - 1.0).max() < 1e-12
+        assert (r["expect"][k] >= 0.0).all() and (r["expect"][k] <= 1.0).all() and (r["expect"][k][r["shadowed"][k]] == 0.0).all()
+        lit = k & ~r["shadowed"].any(axis=1)
+        assert np.abs((r["expect"][lit] ** 2).sum(axis=1) - 1.0).max() < 1e-12  # the axes are orthonormal
+        if kind == "disk" or name.endswith("-360") and kind == "sphere":
+            assert not r["shadowed"][k].any(), name  # flat or convex and seen from outside: nothing to shadow it
+        elif not name.endswith("-360"):
+            assert r["shadowed"][k].any(axis=1).sum() > 300, name  # open shapes do shadow themselves
+    assert worst_near <= 0.01 and worst_shadow <= 0.01 and fewest >= 1000
+
+
+def test_orthonormal_mirror_is_one():
+    m = ORTHONORMAL_MIRROR[:3, :3]
+    assert np.abs(m.T @ m - np.eye(3)).max() < 1e-15 and np.linalg.det(m) < 0.0
+    assert np.abs(PROBE_AXES.T @ PROBE_AXES - np.eye(3)).max() < 1e-15
+    for name, t in TRANSFORMS.items():  # no light along an object axis
+        axes = t[:3, :3] / np.sqrt((t[:3, :3] ** 2).sum(axis=0))
+        assert np.abs(axes.T @ PROBE_AXES).max() < 0.99, name
+
+
+@pytest.mark.parametrize("phi_max_deg", [360.0, 200.0, 90.0])
+def test_cylinder_light_closed_form_matches_a_quadrature(phi_max_deg):
+    R, H, rho, L = 0.8, 1.1, 0.6, 5.0
+    m = translate(0.2, -0.1, 0.3) @ rot((1, 0, 0), -90.0) @ rot((0, 0, 1), 20.0)
+    s = qm.make("cylinder", R, -H, H, phi_max_deg=phi_max_deg, o2w=m)
+    quad = qm.patch_radiance_by_quadrature(s, m[:3, 3], m[:3, :3] @ [0.0, 0.0, 1.0], rho, L)
+    closed = qm.partial_cylinder_light_centre_radiance(rho, L, R, H, np.radians(phi_max_deg))
+    assert abs(quad - closed) <= 2e-5 * closed
+    if phi_max_deg == 360.0:
+        assert closed == qm.cylinder_light_centre_radiance(rho, L, R, H)
+
+
+def test_disk_annulus_and_sphere_light_closed_forms_match_a_quadrature():
+    rho, L, h, R = 0.6, 5.0, 1.2, 1.2
+    m = translate(0.3, h, -0.2) @ rot((1, 0, 0), 90.0) @ rot((0, 0, 1), 63.0)
+    p0, up = [0.3, 0.0, -0.2], [0.0, 1.0, 0.0]
+    quad = qm.patch_radiance_by_quadrature(qm.make("disk", R, 0.0, 0.0, o2w=m), p0, up, rho, L)
+    assert abs(quad - qm.disk_light_floor_radiance(rho, L, R, h)) <= 2e-5 * quad
+    quad = qm.patch_radiance_by_quadrature(qm.make("disk", R, 0.0, 0.0, inner_radius=0.5 * R, o2w=m), p0, up, rho, L)
+    assert abs(quad - qm.annulus_light_floor_radiance(rho, L, R, 0.5 * R, h)) <= 2e-5 * quad
+    # the sphere from outside: the quadrature sees both halves (two-sided, unshadowed), the floor only the near one, and the far
+    # half subtends the same cone: twice the closed form
+    for ratio in (0.5, 0.1):
+        s = qm.make("sphere", ratio * h, -ratio * h, ratio * h, o2w=translate(0.3, h, -0.2) @ rot((1, 2, 3), 40.0))
+        quad = qm.patch_radiance_by_quadrature(s, p0, up, rho, L)
+        assert abs(0.5 * quad - qm.sphere_light_floor_radiance(rho, L, ratio * h, h)) <= 1e-4 * quad

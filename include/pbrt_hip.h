@@ -100,19 +100,22 @@ enum PbrtLightType {
     PBRT_LIGHT_INFINITE = 1,
     PBRT_LIGHT_POINT = 2,
     PBRT_LIGHT_SPOT = 3,
-    PBRT_LIGHT_DISTANT = 4
+    PBRT_LIGHT_DISTANT = 4,
+    PBRT_LIGHT_PROJECTION = 5,  /* src/lights/projection.rs with pbrt-v3's sample_li and power */
+    PBRT_LIGHT_GONIOMETRIC = 6  /* src/lights/goniometric.rs */
 };
 typedef struct PbrtLight {
     int32_t type;
-    float L[3];        /* area / infinite / distant: radiance L; point / spot: intensity I */
+    float L[3];        /* area / infinite / distant: radiance L; point / spot / projection / goniometric: intensity I */
     int32_t prim;      /* area light: triangle index (caller's order) */
     int32_t two_sided; /* src/lights/diffuse.rs:25 */
     int32_t n_samples; /* src/core/light.rs:76 (delta lights: 1) */
     int32_t pad;
-    float pos[3];      /* point / spot: p_light (world); distant: w_light (world, unit length) */
+    float pos[3];      /* point / spot / projection / goniometric: p_light (world); distant: w_light (world, unit length) */
     float cos_total_width, cos_falloff_start; /* spot */
-    float world_to_light[9];                  /* spot: rows of the upper 3x3, row-major */
-    int32_t pad2[2];
+    float world_to_light[9];                  /* spot / projection / goniometric: rows of the upper 3x3, row-major */
+    float fov;                                /* projection: the projector's field of view in degrees, in (0, 180) */
+    int32_t pad2;
 } PbrtLight;
 
 /* src/core/primitive.rs:105-123 TransformedPrimitive with a static transform: one instance of the
@@ -307,6 +310,24 @@ int pbrt_hip_scene_set_shading_data(PbrtHipScene* scene, const float* positions,
  * singular or non-affine transform, or texels pbrt_hip_envmap_tables refuses. */
 int pbrt_hip_scene_set_environment_map(PbrtHipScene* scene, int32_t light, const float* rgb, int32_t width, int32_t height,
                                        const float light_to_world[16]);
+/* ProjectionLight::new / GonioPhotometricLight::new (src/lights/projection.rs:36-88, goniometric.rs:32-63) with the texels in
+ * memory: attaches an image map to light `light` (a PBRT_LIGHT_PROJECTION or PBRT_LIGHT_GONIOMETRIC light of this scene; without
+ * a map the projector lights its whole window and the goniometric light is a point light). rgb: width x height RGB float32
+ * texels, row-major, row 0 = t 0. Projection: row 0 is the lowest screen y, column 0 the lowest screen x, and the window is
+ * [-aspect, aspect] x [-1, 1] for aspect = width / height > 1, else [-1, 1] x [-1 / aspect, 1 / aspect]. Goniometric: row 0 is
+ * theta 0 = light-space +y, column 0 is phi 0 = light-space +x, phi growing towards light-space +z. The texels are resampled to
+ * powers of two (pbrt_hip_light_map_tables) and looked up bilinearly; the light's I multiplies the looked-up value. The light's
+ * power and the power light distribution are recomputed and a spatial light distribution already built is rebuilt
+ * by the next render that uses it. Calling it again replaces the map. PBRT_HIP_ERR_INVALID (pbrt_hip_last_error says why, the
+ * scene unchanged) for a bad light index or type, a null pointer, or texels or sizes pbrt_hip_light_map_tables refuses. */
+int pbrt_hip_scene_set_light_map(PbrtHipScene* scene, int32_t light, const float* rgb, int32_t width, int32_t height);
+/* Light::sample_li (src/core/light.rs:35-42) of light `light` of the scene, in batch form, evaluated on the device by the
+ * function the shading kernels inline (any light type), from bare interactions at the world points p[3 i ..] (normal and error
+ * zero, as SpatialLightDistribution samples them). u[2 i ..]: the sample; may be NULL for delta lights (point, spot, distant,
+ * projection, goniometric). Outputs: wi[3 i ..], pdf[i], li[3 i ..]; there is no visibility test. Host buffers; any output may
+ * be NULL. n = 0 is a no-op. */
+int pbrt_hip_light_sample_li(PbrtHipScene* scene, int32_t light, int64_t n, const float* p, const float* u, float* wi, float* pdf,
+                             float* li);
 /* Roughness of a plastic or metal material after creation: TrowbridgeReitzDistribution(a_u, a_v) with a = roughness_to_alpha(r)
  * (microfacet.rs:160-169, r clamped at 1e-3) when remap != 0, else a = r (pbrt-v3's remaproughness = false). Metal may be
  * anisotropic (u along the shading frame's dpdu); plastic is isotropic (u == v). PBRT_HIP_ERR_INVALID (pbrt_hip_last_error says
@@ -658,6 +679,20 @@ int pbrt_hip_sample_bounds(int32_t width, int32_t height, float radius_x, float 
  * then says which. */
 int pbrt_hip_envmap_tables(const float* rgb, int32_t width, int32_t height, const float L[3], int32_t* res_w, int32_t* res_h,
                            float* level0_rgb, float* dist_func, float power_rgb[3], const char** reason);
+/* ProjectionLight::new's / GonioPhotometricLight::new's tables for an image map (src/lights/projection.rs:36-88, goniometric.rs:
+ * 32-63 over src/core/mipmap.rs:76-296), what pbrt_hip_scene_set_light_map uploads. Host only. type: PBRT_LIGHT_PROJECTION or
+ * PBRT_LIGHT_GONIOMETRIC; fov: the projector's, in degrees; rgb: width x height RGB texels (see there) or NULL for no map.
+ * *res_w, *res_h: the power-of-two size of level 0 (0, 0 without a map); level0_rgb (res_w * res_h * 3: the texels,
+ * Lanczos-resampled where a side is not a power of two; call once with it NULL for the size); lookup_rgb =
+ * lookup((.5, .5), .5), 1 without a map; screen_bounds = {min.x, min.y, max.x, max.y} of the projector's window (goniometric:
+ * zeros); *cos_total_width = z of the normalised light-space direction through the window's corner (goniometric: -1);
+ * power_rgb = Light::power for I = (1, 1, 1): lookup 4 pi (goniometric), lookup 2 pi (1 - cos_total_width) (projection,
+ * SURVEY.md D89). Any output but res_w / res_h may be NULL. PBRT_HIP_ERR_INVALID for another type, a fov that is not finite or
+ * not in (0, 180), width or height < 1, a table past 2^28 texels, or a non-finite or negative texel; *reason (may be NULL)
+ * then says which. */
+int pbrt_hip_light_map_tables(int32_t type, float fov, const float* rgb, int32_t width, int32_t height, int32_t* res_w,
+                              int32_t* res_h, float* level0_rgb, float lookup_rgb[3], float screen_bounds[4], float* cos_total_width,
+                              float power_rgb[3], const char** reason);
 /* Image output: Film::write_image ends in a file writer that is todo!() in the reference
  * (src/core/imageio.rs:3-5); this writes the RGB image as a little-endian PFM (top row first in memory). */
 int pbrt_hip_write_pfm(const char* path, const float* rgb, int32_t width, int32_t height);

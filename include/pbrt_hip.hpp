@@ -200,6 +200,33 @@ inline PbrtInstance TransformedPrimitive(const double to_world[16], int32_t mate
     return inst;
 }
 
+// ProjectionLight::new(light_to_world, .., I, texname, fov) and GonioPhotometricLight::new(light_to_world, .., I, texname)
+// (lights/projection.rs:36-88, goniometric.rs:32-63) without the map (Scene::set_light_map attaches the texels): the PbrtLight
+// record for TriangleMesh::lights. light_to_world row-major 4 x 4 with last row (0, 0, 0, 1); p_light and world_to_light's upper
+// 3 x 3 are formed in double and rounded once. fov: degrees, in (0, 180).
+inline PbrtLight map_light(int32_t type, const double light_to_world[16], const float intensity[3], float fov) {
+    PbrtLight l;
+    std::memset(&l, 0, sizeof(l));
+    double inv[16];
+    inverse_affine(light_to_world, inv);
+    l.type = type;
+    l.prim = -1;
+    l.n_samples = 1;
+    l.fov = fov;
+    for (int k = 0; k < 3; ++k) {
+        l.L[k] = intensity[k];
+        l.pos[k] = (float)light_to_world[4 * k + 3];
+        for (int c = 0; c < 3; ++c) l.world_to_light[3 * k + c] = (float)inv[4 * k + c];
+    }
+    return l;
+}
+inline PbrtLight projection_light(const double light_to_world[16], const float intensity[3], float fov) {
+    return map_light(PBRT_LIGHT_PROJECTION, light_to_world, intensity, fov);
+}
+inline PbrtLight goniometric_light(const double light_to_world[16], const float intensity[3]) {
+    return map_light(PBRT_LIGHT_GONIOMETRIC, light_to_world, intensity, 0.0f);
+}
+
 // BVHAccel over the mesh's triangles as GeometricPrimitives: built on the host in the reference's node order
 // (pbrt_hip_bvh_build), resident in HBM (pbrt_hip_scene_create), walked by the HIP traversal kernels.
 class BVHAccel : public Primitive {
@@ -445,6 +472,14 @@ public:
     bool intersect(Ray& ray, SurfaceInteraction* isect) const { return aggregate_->intersect(ray, isect); }
     bool intersect_p(const Ray& ray) const { return aggregate_->intersect_p(ray); }
     const BVHAccel& aggregate() const { return *aggregate_; }
+    // the image map of a projection_light() / goniometric_light() of the mesh: width x height RGB texels, row 0 = t 0
+    // (include/pbrt_hip.h: pbrt_hip_scene_set_light_map); calling it again replaces the map
+    void set_light_map(int32_t light, const std::vector<float>& rgb, int32_t width, int32_t height) {
+        if (width < 1 || height < 1 || rgb.size() != (size_t)width * (size_t)height * 3)
+            throw Error("Scene::set_light_map: rgb must hold width x height x 3 floats", PBRT_HIP_ERR_INVALID);
+        aggregate_->context()->check(pbrt_hip_scene_set_light_map(aggregate_->handle(), light, rgb.data(), width, height),
+                                     "Scene::set_light_map");
+    }
 
 private:
     std::shared_ptr<BVHAccel> aggregate_;

@@ -120,26 +120,14 @@ const char* check_texels(const float* rgb, int32_t width, int32_t height, const 
     return nullptr;
 }
 
-}  // namespace
-
-const char* envmap_resolution(int32_t width, int32_t height, int* res_w, int* res_h) {
-    if (width < 1 || height < 1) return "width and height must be >= 1";
-    int64_t rw = round_up_pow2(width), rh = round_up_pow2(height);
-    if (4 * rw * rh > kMaxTableTexels) return "the map's sampling table would pass 2^28 texels";
-    *res_w = (int)rw;
-    *res_h = (int)rh;
-    return nullptr;
-}
-
-const char* envmap_build(const float* rgb, int32_t width, int32_t height, const float L[3], EnvTables* out) {
-    int rw, rh;
-    if (const char* why = envmap_resolution(width, height, &rw, &rh)) return why;
-    if (const char* why = check_texels(rgb, width, height, L)) return why;
+// MIPMap::new (mipmap.rs:76-183) over width x height texels, each multiplied by `scale` in float (null: as they are): level 0
+// as float (what the device reads, and what the pyramid is built from) and the box pyramid over it
+void mipmap_build(const float* rgb, int32_t width, int32_t height, const float* scale, int rw, int rh, MipMap* out,
+                  std::vector<float>* level0_out) {
     const int64_t W = width, H = height;
-    // texels x L (infinite.rs:51-53), in float as the reference multiplies them
     std::vector<double> img((size_t)(W * H * 3));
-    for (size_t i = 0; i < img.size(); ++i) img[i] = (double)(rgb[i] * L[i % 3]);
-    MipMap mm;
+    for (size_t i = 0; i < img.size(); ++i) img[i] = scale ? (double)(rgb[i] * scale[i % 3]) : (double)rgb[i];
+    MipMap& mm = *out;
     Level l0{rw, rh, {}};
     if (rw == W && rh == H) {
         l0.v = std::move(img);  // D59: level 0 is the image itself
@@ -173,7 +161,7 @@ const char* envmap_build(const float* rgb, int32_t width, int32_t height, const 
     mm.pyr.push_back(std::move(l0));
     // the 2x2 box pyramid (mipmap.rs:152-170)
     int n_levels = 1;
-    for (int64_t m = std::max(rw, rh); m > 1; m >>= 1) ++n_levels;
+    for (int64_t m = std::max<int64_t>(rw, rh); m > 1; m >>= 1) ++n_levels;
     for (int i = 1; i < n_levels; ++i) {
         const Level& p = mm.pyr[i - 1];
         Level l{std::max<int64_t>(1, p.w / 2), std::max<int64_t>(1, p.h / 2), {}};
@@ -186,6 +174,28 @@ const char* envmap_build(const float* rgb, int32_t width, int32_t height, const 
             }
         mm.pyr.push_back(std::move(l));
     }
+    *level0_out = std::move(level0);
+}
+
+}  // namespace
+
+const char* envmap_resolution(int32_t width, int32_t height, int* res_w, int* res_h) {
+    if (width < 1 || height < 1) return "width and height must be >= 1";
+    int64_t rw = round_up_pow2(width), rh = round_up_pow2(height);
+    if (4 * rw * rh > kMaxTableTexels) return "the map's sampling table would pass 2^28 texels";
+    *res_w = (int)rw;
+    *res_h = (int)rh;
+    return nullptr;
+}
+
+const char* envmap_build(const float* rgb, int32_t width, int32_t height, const float L[3], EnvTables* out) {
+    int rw, rh;
+    if (const char* why = envmap_resolution(width, height, &rw, &rh)) return why;
+    if (const char* why = check_texels(rgb, width, height, L)) return why;
+    // texels x L (infinite.rs:51-53), in float as the reference multiplies them
+    MipMap mm;
+    std::vector<float> level0;
+    mipmap_build(rgb, width, height, L, rw, rh, &mm, &level0);
     // the sin-weighted luminance image and its Distribution2D (infinite.rs:59-73; D40 intended: rows sliced by v * nu)
     EnvTables e;
     e.w = rw;
@@ -219,7 +229,79 @@ const char* envmap_build(const float* rgb, int32_t width, int32_t height, const 
     return nullptr;
 }
 
+double light_map_geometry(int32_t type, float fov, int32_t width, int32_t height, float screen_bounds[4], float* inv_tan) {
+    if (type != PBRT_LIGHT_PROJECTION) {
+        screen_bounds[0] = screen_bounds[1] = screen_bounds[2] = screen_bounds[3] = 0.0f;
+        *inv_tan = 0.0f;
+        return -1.0;  // the whole sphere
+    }
+    // projection.rs:57-76
+    const double aspect = (width > 0 && height > 0) ? (double)width / (double)height : 1.0;  // in double, rounded once
+    if (aspect > 1.0) {
+        screen_bounds[0] = (float)-aspect, screen_bounds[1] = -1.0f, screen_bounds[2] = (float)aspect, screen_bounds[3] = 1.0f;
+    } else {
+        screen_bounds[0] = -1.0f, screen_bounds[1] = (float)(-1.0 / aspect), screen_bounds[2] = 1.0f, screen_bounds[3] = (float)(1.0 / aspect);
+    }
+    const double it = 1.0 / std::tan((double)fov * (kPiD / 180.0) / 2.0);
+    *inv_tan = (float)it;
+    // the light-space direction through the screen's corner (max.x, max.y): (x / inv_tan, y / inv_tan, 1), normalised
+    const double cx = (double)screen_bounds[2] / it, cy = (double)screen_bounds[3] / it;
+    return 1.0 / std::sqrt(cx * cx + cy * cy + 1.0);
+}
+
+const char* light_map_build(int32_t type, float fov, const float* rgb, int32_t width, int32_t height, LightMapTables* out) {
+    if (type != PBRT_LIGHT_PROJECTION && type != PBRT_LIGHT_GONIOMETRIC) return "light type is not PBRT_LIGHT_PROJECTION or PBRT_LIGHT_GONIOMETRIC";
+    if (type == PBRT_LIGHT_PROJECTION && !(std::isfinite(fov) && fov > 0.0f && fov < 180.0f)) return "fov must be finite and in (0, 180)";
+    LightMapTables t;
+    double look[3] = {1.0, 1.0, 1.0};
+    if (rgb) {
+        int rw, rh;
+        if (const char* why = envmap_resolution(width, height, &rw, &rh)) return why;
+        const float one[3] = {1.0f, 1.0f, 1.0f};
+        if (const char* why = check_texels(rgb, width, height, one)) return why;
+        MipMap mm;
+        mipmap_build(rgb, width, height, nullptr, rw, rh, &mm, &t.level0);  // the texels as they are: I multiplies the lookup
+        t.w = rw;
+        t.h = rh;
+        mm.lookup(0.5, 0.5, 0.5, look);
+    }
+    const double cos_total_width = light_map_geometry(type, fov, rgb ? width : 0, rgb ? height : 0, t.screen_bounds, &t.inv_tan);
+    t.cos_total_width = (float)cos_total_width;
+    // GonioPhotometricLight::power (goniometric.rs:105-113); ProjectionLight::power as pbrt-v3 has it (D89), for I = 1
+    const double cone = type == PBRT_LIGHT_PROJECTION ? 2.0 * kPiD * (1.0 - cos_total_width) : 4.0 * kPiD;
+    for (int k = 0; k < 3; ++k) {
+        t.lookup_rgb[k] = (float)look[k];
+        t.power_rgb[k] = (float)(look[k] * cone);
+        if (!std::isfinite(t.power_rgb[k])) return "the map's power overflows float";
+    }
+    *out = std::move(t);
+    return nullptr;
+}
+
 }  // namespace pb
+
+// Context-free tables of a ProjectionLight's or GonioPhotometricLight's map (include/pbrt_hip.h)
+extern "C" int pbrt_hip_light_map_tables(int32_t type, float fov, const float* rgb, int32_t width, int32_t height, int32_t* res_w,
+                                         int32_t* res_h, float* level0_rgb, float lookup_rgb[3], float screen_bounds[4],
+                                         float* cos_total_width, float power_rgb[3], const char** reason) try {
+    auto refuse = [&](const char* why) {
+        if (reason) *reason = why;
+        return PBRT_HIP_ERR_INVALID;
+    };
+    if (reason) *reason = "";
+    if (!res_w || !res_h) return refuse("null pointer");
+    pb::LightMapTables t;
+    if (const char* why = pb::light_map_build(type, fov, rgb, width, height, &t)) return refuse(why);
+    *res_w = t.w;
+    *res_h = t.h;
+    if (level0_rgb && !t.level0.empty()) std::memcpy(level0_rgb, t.level0.data(), t.level0.size() * sizeof(float));
+    if (lookup_rgb) std::memcpy(lookup_rgb, t.lookup_rgb, sizeof(t.lookup_rgb));
+    if (screen_bounds) std::memcpy(screen_bounds, t.screen_bounds, sizeof(t.screen_bounds));
+    if (cos_total_width) *cos_total_width = t.cos_total_width;
+    if (power_rgb) std::memcpy(power_rgb, t.power_rgb, sizeof(t.power_rgb));
+    return PBRT_HIP_OK;
+}
+PB_ABI_CATCH
 
 // Context-free tables of InfiniteAreaLight::new for a caller's map (include/pbrt_hip.h)
 extern "C" int pbrt_hip_envmap_tables(const float* rgb, int32_t width, int32_t height, const float L[3], int32_t* res_w,

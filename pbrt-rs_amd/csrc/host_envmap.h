@@ -24,4 +24,21 @@ const char* envmap_resolution(int32_t width, int32_t height, int* res_w, int* re
 // validates and builds everything; returns null or the reason the input was refused (`out` untouched then)
 const char* envmap_build(const float* rgb, int32_t width, int32_t height, const float L[3], EnvTables* out);
 
+// ProjectionLight's / GonioPhotometricLight's map (src/lights/projection.rs:36-88, goniometric.rs:32-63): the MIPMap over the
+// texels as they are (I multiplies the lookup), the projector's screen window and the light's power for I = 1 (D89)
+struct LightMapTables {
+    int w = 0, h = 0;                // level 0 after resampling; 0 x 0: no map
+    std::vector<float> level0;       // w * h * 3
+    float lookup_rgb[3] = {1, 1, 1};  // lookup((0.5, 0.5), 0.5); 1 without a map
+    float screen_bounds[4] = {0, 0, 0, 0};  // projection: min.x, min.y, max.x, max.y
+    float inv_tan = 0.0f;            // projection: 1 / tan(radians(fov) / 2)
+    float cos_total_width = -1.0f;   // projection: z of the normalised light-space direction through the corner (max.x, max.y)
+    float power_rgb[3] = {0, 0, 0};  // Light::power for I = (1, 1, 1)
+};
+// the projector's window and inv_tan for a width x height map (0 x 0: no map, aspect 1), in double, rounded once; returns
+// cos_total_width (-1 for a goniometric light)
+double light_map_geometry(int32_t type, float fov, int32_t width, int32_t height, float screen_bounds[4], float* inv_tan);
+// validates and builds everything (rgb null: no map); returns null or the reason the input was refused (`out` untouched then)
+const char* light_map_build(int32_t type, float fov, const float* rgb, int32_t width, int32_t height, LightMapTables* out);
+
 }  // namespace pb

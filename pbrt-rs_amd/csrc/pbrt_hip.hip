@@ -743,7 +743,16 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
         if (const char* why = material_invalid(materials[i])) return fail(why);
     }
     for (int32_t i = 0; i < n_lights; ++i) {
-        if (lights[i].type < PBRT_LIGHT_DIFFUSE_AREA || lights[i].type > PBRT_LIGHT_DISTANT) return fail("unknown light type");
+        if (lights[i].type < PBRT_LIGHT_DIFFUSE_AREA || lights[i].type > PBRT_LIGHT_GONIOMETRIC) return fail("unknown light type");
+        if (lights[i].type == PBRT_LIGHT_PROJECTION || lights[i].type == PBRT_LIGHT_GONIOMETRIC) {
+            const PbrtLight& l = lights[i];
+            for (int k = 0; k < 3; ++k)
+                if (!std::isfinite(l.pos[k]) || !std::isfinite(l.L[k])) return fail("projection / goniometric light: pos and L must be finite");
+            for (int k = 0; k < 9; ++k)
+                if (!std::isfinite(l.world_to_light[k])) return fail("projection / goniometric light: world_to_light must be finite");
+            if (l.type == PBRT_LIGHT_PROJECTION && !(std::isfinite(l.fov) && l.fov > 0.0f && l.fov < 180.0f))
+                return fail("projection light: fov must be finite and in (0, 180)");
+        }
         if (lights[i].type == PBRT_LIGHT_DIFFUSE_AREA &&
             (lights[i].prim < 0 || lights[i].prim >= (ia.n_instances > 0 ? ia.n_world_tris : n_prims)))
             return fail("area light primitive out of range");
@@ -879,7 +888,8 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
         l.cos_total_width = lights[i].cos_total_width;
         l.cos_falloff_start = lights[i].cos_falloff_start;
         std::memcpy(l.w2l, lights[i].world_to_light, 36);
-        l.delta = (l.type == PBRT_LIGHT_POINT || l.type == PBRT_LIGHT_SPOT || l.type == PBRT_LIGHT_DISTANT) ? 1 : 0;
+        const bool map_light = l.type == PBRT_LIGHT_PROJECTION || l.type == PBRT_LIGHT_GONIOMETRIC;
+        l.delta = (l.type == PBRT_LIGHT_POINT || l.type == PBRT_LIGHT_SPOT || l.type == PBRT_LIGHT_DISTANT || map_light) ? 1 : 0;
         if (l.type == PBRT_LIGHT_DIFFUSE_AREA) {
             int32_t prim = lights[i].prim + (instanced ? ia.world_tri_offset : 0);  // two-level: prim counts the world-space triangles
             l.slot = dt ? dt->light_slot[i] : prim_slot[prim];
@@ -901,6 +911,20 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
             scale = 2.0f * kPi * (1.0f - 0.5f * (l.cos_falloff_start + l.cos_total_width));  // spot.rs:90-92
         } else if (l.type == PBRT_LIGHT_DISTANT) {
             scale = kPi * world_radius * world_radius;  // distant.rs:76-78
+        } else if (map_light) {
+            // without a map (pbrt_hip_scene_set_light_map attaches one): goniometric.rs:105-113 = the point light's 4 pi I;
+            // projection: pbrt-v3's I 2 pi (1 - cos_total_width) (D89). slot names the light's DevLightMap.
+            l.slot = i;
+            s->light_maps = true;
+            if (s->h_light_maps.empty()) {
+                s->h_light_maps.assign(n_lights, DevLightMap{});
+                s->light_fov.assign(n_lights, 0.0f);
+            }
+            s->light_fov[i] = lights[i].fov;
+            DevLightMap& m = s->h_light_maps[i];
+            const double cos_total_width = light_map_geometry(l.type, lights[i].fov, 0, 0, m.screen_bounds, &m.inv_tan);
+            l.cos_total_width = (float)cos_total_width;
+            scale = l.type == PBRT_LIGHT_GONIOMETRIC ? 4.0f * kPi : (float)(2.0 * 3.14159265358979323846 * (1.0 - cos_total_width));
         } else {
             infinite_ids.push_back(i);
             scale = kPi * world_radius * world_radius;  // infinite.rs:131-133
@@ -911,7 +935,7 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
     }
     s->h_lights = dl;
     s->light_samples.resize(n_lights);
-    for (int32_t i = 0; i < n_lights; ++i) s->light_samples[i] = std::max(1, lights[i].n_samples);
+    for (int32_t i = 0; i < n_lights; ++i) s->light_samples[i] = (dl[i].type == PBRT_LIGHT_PROJECTION || dl[i].type == PBRT_LIGHT_GONIOMETRIC) ? 1 : std::max(1, lights[i].n_samples);
     std::vector<DevMaterial> dm(n_materials);
     for (int32_t i = 0; i < n_materials; ++i) {
         dm[i].type = materials[i].type;
@@ -1203,6 +1227,10 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
         d.disney = dev_upload(s, dz.data(), dz.size(), &ok);
     }
     d.lights = dev_upload(s, dl.data(), dl.size(), &ok);
+    if (s->light_maps) {
+        d.light_maps = dev_upload(s, s->h_light_maps.data(), s->h_light_maps.size(), &ok);
+        s->light_map_allocs.assign(n_lights, nullptr);
+    }
     d.n_lights = n_lights;
     d.n_materials = n_materials;
     d.n_infinite = (int)infinite_ids.size();
@@ -1298,6 +1326,8 @@ extern "C" void pbrt_hip_scene_destroy(PbrtHipScene* s) {
         for (void* p : s->allocs) (void)hipFree(p);
         for (auto& a : s->env_allocs)
             for (void* p : a) (void)hipFree(p);
+        for (void* p : s->light_map_allocs)
+            if (p) (void)hipFree(p);
     }
     delete s;
 }
@@ -1612,6 +1642,84 @@ extern "C" int pbrt_hip_scene_set_environment_map(PbrtHipScene* s, int32_t light
     for (void* q : s->env_allocs[light]) (void)hipFree(q);  // a map set before on this light
     s->env_allocs[light].swap(fresh);
     s->h_env.swap(h_env);
+    s->h_lights[light] = lt;
+    if (s->d_spatial) {
+        (void)hipFree(s->d_spatial);
+        s->allocs.erase(std::remove(s->allocs.begin(), s->allocs.end(), (void*)s->d_spatial), s->allocs.end());
+        s->d_spatial = nullptr;
+    }
+    return PBRT_HIP_OK;
+}
+PB_ABI_CATCH
+
+// ProjectionLight::new / GonioPhotometricLight::new (lights/projection.rs:36-88, goniometric.rs:32-63) with the texels in memory:
+// level 0 of the map's MIPMap goes to the device for light `light`, the projector's window follows the map's aspect, the light's
+// power (D89) and the power distribution are recomputed, and a spatial light table already built is dropped.
+extern "C" int pbrt_hip_scene_set_light_map(PbrtHipScene* s, int32_t light, const float* rgb, int32_t width, int32_t height) try {
+    if (!s) return PBRT_HIP_ERR_INVALID;
+    PbrtHipContext* ctx = s->ctx;
+    PB_ENTER(ctx);
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = "pbrt_hip_scene_set_light_map: " + why;
+        return PBRT_HIP_ERR_INVALID;
+    };
+    if (light < 0 || light >= s->d.n_lights) return invalid("light index out of range");
+    const int type = s->h_lights[light].type;
+    if (type != PBRT_LIGHT_PROJECTION && type != PBRT_LIGHT_GONIOMETRIC) return invalid("light is not PBRT_LIGHT_PROJECTION or PBRT_LIGHT_GONIOMETRIC");
+    if (!rgb) return invalid("null pointer");
+    LightMapTables t;
+    if (const char* why = light_map_build(type, s->light_fov[light], rgb, width, height, &t)) return invalid(why);
+
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<float4> texels((size_t)t.w * t.h);
+    for (size_t i = 0; i < texels.size(); ++i) texels[i] = make_float4(t.level0[3 * i], t.level0[3 * i + 1], t.level0[3 * i + 2], 0.0f);
+    void* fresh = nullptr;
+    if (!hip_ok(ctx, hipMalloc(&fresh, texels.size() * sizeof(float4)), "hipMalloc light map")) return PBRT_HIP_ERR_DEVICE;
+    if (!hip_ok(ctx, hipMemcpy(fresh, texels.data(), texels.size() * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy light map")) {
+        (void)hipFree(fresh);
+        return PBRT_HIP_ERR_DEVICE;
+    }
+    DevLightMap m{};
+    m.texels = (const float4*)fresh;
+    m.w = t.w;
+    m.h = t.h;
+    m.inv_tan = t.inv_tan;
+    std::memcpy(m.screen_bounds, t.screen_bounds, sizeof(m.screen_bounds));
+    // the light itself: its power for the power distribution
+    const int n = s->d.n_lights;
+    DevLight lt = s->h_lights[light];
+    if (type == PBRT_LIGHT_PROJECTION) lt.cos_total_width = t.cos_total_width;
+    float p[3] = {lt.L[0] * t.power_rgb[0], lt.L[1] * t.power_rgb[1], lt.L[2] * t.power_rgb[2]};
+    lt.power_y = 0.212671f * p[0] + 0.715160f * p[1] + 0.072169f * p[2];
+    std::vector<float> power_y(n), cdf, old_power_y(n), old_cdf;
+    for (int i = 0; i < n; ++i) {
+        old_power_y[i] = s->h_lights[i].power_y;
+        power_y[i] = i == light ? lt.power_y : old_power_y[i];
+    }
+    float fi, old_fi;
+    make_distribution(power_y, &cdf, &fi);
+    make_distribution(old_power_y, &old_cdf, &old_fi);
+    // the device copies of the descriptor, the light and the power distribution, from one consistent host state
+    auto write_state = [&](const DevLightMap& dm, const DevLight& l, const std::vector<float>& py, const std::vector<float>& pc) {
+        return hip_ok(ctx, hipMemcpy((void*)(s->d.light_maps + light), &dm, sizeof(DevLightMap), hipMemcpyHostToDevice), "hipMemcpy") &&
+               hip_ok(ctx, hipMemcpy((void*)(s->d.lights + light), &l, sizeof(DevLight), hipMemcpyHostToDevice), "hipMemcpy") &&
+               hip_ok(ctx, hipMemcpy((void*)s->d.light_distrib_power.func, py.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy") &&
+               hip_ok(ctx, hipMemcpy((void*)s->d.light_distrib_power.cdf, pc.data(), (size_t)(n + 1) * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy");
+    };
+    if (!write_state(m, lt, power_y, cdf)) {
+        // put the previous state back; if that fails as well the device may still point at the new texels: they then stay
+        // allocated until the scene is destroyed instead of being freed under a descriptor that names them
+        std::string why = ctx->last_error;
+        if (write_state(s->h_light_maps[light], s->h_lights[light], old_power_y, old_cdf)) (void)hipFree(fresh);
+        else s->allocs.push_back(fresh);
+        ctx->last_error = why;
+        return PBRT_HIP_ERR_DEVICE;
+    }
+    s->d.light_distrib_power.func_int = fi;
+    if (s->light_map_allocs[light]) (void)hipFree(s->light_map_allocs[light]);  // a map set before on this light
+    s->light_map_allocs[light] = fresh;
+    s->h_light_maps[light] = m;
     s->h_lights[light] = lt;
     if (s->d_spatial) {
         (void)hipFree(s->d_spatial);

@@ -326,6 +326,115 @@ extern "C" int pbrt_hip_bsdf_query(PbrtHipScene* s, int32_t material, int64_t n,
 }
 PB_ABI_CATCH
 
+// the scene's part of ShadeConsts: its tables as the shading kernels read them (the light distribution of a render, the
+// light-sample prefix and a spatial table are the caller's to add)
+static void scene_shade_consts(const PbrtHipScene* s, ShadeConsts* out) {
+    ShadeConsts& sc = *out;
+    sc.bvh = s->d.bvh;
+    sc.materials = s->d.materials;
+    sc.lights = s->d.lights;
+    sc.n_lights = s->d.n_lights;
+    sc.n_infinite = s->d.n_infinite;
+    sc.infinite_ids = s->d.infinite_ids;
+    sc.env_maps = s->d.env_maps;
+    sc.distrib = s->d.light_distrib_uniform;
+    std::memcpy(sc.env_cond_func, s->d.env_cond_func, sizeof(sc.env_cond_func));
+    std::memcpy(sc.env_cond_cdf, s->d.env_cond_cdf, sizeof(sc.env_cond_cdf));
+    std::memcpy(sc.env_cond_int, s->d.env_cond_int, sizeof(sc.env_cond_int));
+    std::memcpy(sc.env_marg_func, s->d.env_marg_func, sizeof(sc.env_marg_func));
+    std::memcpy(sc.env_marg_cdf, s->d.env_marg_cdf, sizeof(sc.env_marg_cdf));
+    sc.env_marg_int = s->d.env_marg_int;
+    sc.world_radius = s->d.world_radius;
+    sc.light_sample_prefix = nullptr;
+    sc.total_light_samples = 0;
+    sc.spatial = nullptr;
+    sc.n_voxel[0] = sc.n_voxel[1] = sc.n_voxel[2] = 1;
+    sc.mis_bool = s->ctx->count_traversal != 1 ? 1 : 0;  // wf_state.h: RS_MIS_BOOL
+    sc.disney = s->d.disney;
+    sc.light_maps = s->d.light_maps;
+}
+
+// Light::sample_li (light.rs:35-42) of one light of the scene from bare interactions at the world points p (normal and error
+// zero, as spatial_light_tables calls it), through the light_sample_li the shading kernels inline. out: 7 floats per query,
+// {wi.xyz, pdf, li.rgb}. u == null (delta lights): the sample is not read.
+template <bool SHP>
+__global__ void k_light_query(ShadeConsts sc, int light, int64_t n, const float* __restrict__ p_in, const float* __restrict__ u_in,
+                              float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Surf sf;
+    sf.n = V3{0.0f, 0.0f, 0.0f};
+    sf.p_error = V3{0.0f, 0.0f, 0.0f};
+    sf.p = V3{p_in[3 * i], p_in[3 * i + 1], p_in[3 * i + 2]};
+    const float u0 = u_in ? u_in[2 * i] : 0.0f, u1 = u_in ? u_in[2 * i + 1] : 0.0f;
+    const DevLight lt = sc.lights[light];
+    V3 wi, li, p1, p1_err, p1_n;
+    float pdf;
+    light_sample_li<SHP, true>(sc, sf, lt, u0, u1, &wi, &pdf, &li, &p1, &p1_err, &p1_n);
+    float* o = out + 7 * i;
+    o[0] = wi.x;
+    o[1] = wi.y;
+    o[2] = wi.z;
+    o[3] = pdf;
+    o[4] = li.x;
+    o[5] = li.y;
+    o[6] = li.z;
+}
+
+extern "C" int pbrt_hip_light_sample_li(PbrtHipScene* s, int32_t light, int64_t n, const float* p, const float* u, float* wi, float* pdf,
+                                        float* li) try {
+    if (!s) return PBRT_HIP_ERR_INVALID;
+    PbrtHipContext* ctx = s->ctx;
+    PB_ENTER(ctx);
+    auto invalid = [&](const char* why) {
+        ctx->last_error = std::string("pbrt_hip_light_sample_li: ") + why;
+        return PBRT_HIP_ERR_INVALID;
+    };
+    if (light < 0 || light >= s->d.n_lights) return invalid("light index out of range");
+    if (n < 0 || n > ((int64_t)1 << 31)) return invalid("n must be in [0, 2^31]");
+    if (n == 0) return PBRT_HIP_OK;
+    if (!p) return invalid("null p");
+    if (!u && !s->h_lights[light].delta) return invalid("null u for a light that is not a delta light");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t un = (size_t)n;
+    float *d_in = nullptr, *d_out = nullptr;
+    int rc = PBRT_HIP_OK;
+    if (!hip_ok(ctx, hipMalloc((void**)&d_in, un * 5 * sizeof(float)), "hipMalloc") ||
+        !hip_ok(ctx, hipMalloc((void**)&d_out, un * 7 * sizeof(float)), "hipMalloc"))
+        rc = PBRT_HIP_ERR_OOM;
+    if (rc == PBRT_HIP_OK && (!hip_ok(ctx, hipMemcpy(d_in, p, un * 3 * sizeof(float), hipMemcpyHostToDevice), "H2D") ||
+                              (u && !hip_ok(ctx, hipMemcpy(d_in + 3 * un, u, un * 2 * sizeof(float), hipMemcpyHostToDevice), "H2D"))))
+        rc = PBRT_HIP_ERR_DEVICE;
+    std::vector<float> h;
+    if (rc == PBRT_HIP_OK) {
+        ShadeConsts sc;
+        scene_shade_consts(s, &sc);
+        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+        const float* d_u = u ? d_in + 3 * un : nullptr;
+        if (s->d.bvh.has_spheres == 2)
+            hipLaunchKernelGGL(k_light_query<true>, grid, block, 0, ctx->stream, sc, light, n, d_in, d_u, d_out);
+        else
+            hipLaunchKernelGGL(k_light_query<false>, grid, block, 0, ctx->stream, sc, light, n, d_in, d_u, d_out);
+        h.resize(un * 7);
+        if (!hip_ok(ctx, hipGetLastError(), "k_light_query") || !hip_ok(ctx, hipStreamSynchronize(ctx->stream), "k_light_query") ||
+            !hip_ok(ctx, hipMemcpy(h.data(), d_out, un * 7 * sizeof(float), hipMemcpyDeviceToHost), "D2H"))
+            rc = PBRT_HIP_ERR_DEVICE;
+    }
+    (void)hipFree(d_in);
+    (void)hipFree(d_out);
+    if (rc != PBRT_HIP_OK) return rc;
+    for (size_t i = 0; i < un; ++i) {
+        const float* o = &h[7 * i];
+        for (int k = 0; k < 3; ++k) {
+            if (wi) wi[3 * i + k] = o[k];
+            if (li) li[3 * i + k] = o[4 + k];
+        }
+        if (pdf) pdf[i] = o[3];
+    }
+    return PBRT_HIP_OK;
+}
+PB_ABI_CATCH
+
 static int round_up_pow2(int v);
 extern "C" int pbrt_hip_camera_rays(PbrtHipScene* s, const PbrtCamera* camera, const PbrtRenderParams* params, int64_t capacity,
                                     PbrtRay* rays, uint64_t* stream_keys, float* p_film, int32_t* pixel_sample, int64_t* n_out) try {
@@ -941,30 +1050,13 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
     if (camera.kind < PBRT_CAMERA_PERSPECTIVE || camera.kind > PBRT_CAMERA_ENVIRONMENT) return invalid("unknown camera kind");
 
     ShadeConsts sc;
-    sc.bvh = s->d.bvh;
-    sc.materials = s->d.materials;
-    sc.lights = s->d.lights;
-    sc.n_lights = s->d.n_lights;
-    sc.n_infinite = s->d.n_infinite;
-    sc.infinite_ids = s->d.infinite_ids;
-    sc.env_maps = s->d.env_maps;
+    scene_shade_consts(s, &sc);
     // create_light_sample_distribution (lightdistrib.rs:222-232): "uniform", or one light -> uniform
     sc.distrib = (rp.light_strategy == 0 || s->d.n_lights == 1) ? s->d.light_distrib_uniform : s->d.light_distrib_power;
     if (rp.integrator == PBRT_INTEGRATOR_PATH && (rp.light_strategy < 0 || rp.light_strategy > 2))
         return invalid("path: light_strategy must be 0 (uniform), 1 (power) or 2 (spatial)");
-    std::memcpy(sc.env_cond_func, s->d.env_cond_func, sizeof(sc.env_cond_func));
-    std::memcpy(sc.env_cond_cdf, s->d.env_cond_cdf, sizeof(sc.env_cond_cdf));
-    std::memcpy(sc.env_cond_int, s->d.env_cond_int, sizeof(sc.env_cond_int));
-    std::memcpy(sc.env_marg_func, s->d.env_marg_func, sizeof(sc.env_marg_func));
-    std::memcpy(sc.env_marg_cdf, s->d.env_marg_cdf, sizeof(sc.env_marg_cdf));
-    sc.env_marg_int = s->d.env_marg_int;
-    sc.world_radius = s->d.world_radius;
     sc.light_sample_prefix = d_prefix;
     sc.total_light_samples = prefix.back();
-    sc.spatial = nullptr;
-    sc.n_voxel[0] = sc.n_voxel[1] = sc.n_voxel[2] = 1;
-    sc.mis_bool = ctx->count_traversal != 1 ? 1 : 0;  // wf_state.h: RS_MIS_BOOL
-    sc.disney = s->d.disney;
     if (rp.integrator == PBRT_INTEGRATOR_PATH && rp.light_strategy == 2 && s->d.n_lights > 1) {
         // create_light_sample_distribution("spatial") -> SpatialLightDistribution::new(scene, 64) (lightdistrib.rs:85-107, 228)
         if (!s->d_spatial) {
@@ -982,6 +1074,8 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
             for (int i = 0; i < 3; ++i) sc.n_voxel[i] = s->spatial_voxels[i];
             if (s->d.bvh.has_spheres == 2)
                 hipLaunchKernelGGL(k_spatial_light_tables_shapes, dim3((unsigned)((n_voxels + 63) / 64)), dim3(64), 0, st, sc, (float*)p);
+            else if (s->light_maps)
+                hipLaunchKernelGGL(k_spatial_light_tables_maps, dim3((unsigned)((n_voxels + 63) / 64)), dim3(64), 0, st, sc, (float*)p);
             else
                 hipLaunchKernelGGL(k_spatial_light_tables, dim3((unsigned)((n_voxels + 63) / 64)), dim3(64), 0, st, sc, (float*)p);
             HIP_TRY(ctx, hipGetLastError());
@@ -1159,6 +1253,11 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
                     hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, 3 + kDirectShapes>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
                 else if (shapes)
                     hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_AO, kDirectShapes>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                // a projection or goniometric light: the map-light builds of the most general level, whatever the material table
+                else if (rp.integrator == PBRT_INTEGRATOR_DIRECT && s->light_maps)
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, 3 + kDirectMapLights>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+                else if (rp.integrator == PBRT_INTEGRATOR_WHITTED && s->light_maps)
+                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, 3 + kDirectMapLights>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
                 else if (rp.integrator == PBRT_INTEGRATOR_DIRECT && s->disney)
                     hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, 3>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
                 else if (rp.integrator == PBRT_INTEGRATOR_WHITTED && s->disney)
@@ -1198,6 +1297,10 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
                     hipLaunchKernelGGL(k_shade_shapes<true>, sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
                 else if (shapes)
                     hipLaunchKernelGGL(k_shade_shapes<false>, sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
+                else if (s->light_maps && bin_shade && wavefront >= 1)  // a projection or goniometric light: their own builds (wf_path.h)
+                    hipLaunchKernelGGL(k_shade_maps<true>, sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
+                else if (s->light_maps)
+                    hipLaunchKernelGGL(k_shade_maps<false>, sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
                 else if (bin_shade && wavefront >= 1 && s->disney)
                     hipLaunchKernelGGL((k_shade<true, 3>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
                 else if (bin_shade && wavefront >= 1 && s->bxdfs)

@@ -85,7 +85,8 @@ constexpr int kWorkCounters = 16, kFollowUpCounter = 8, kSpecialCount = 12;
 struct DevLight {
     int type;       // PbrtLightType
     float L[3];
-    int slot;       // area light: leaf slot of its triangle; infinite light: its DevEnvMap (= its own index) or -1 (constant map)
+    int slot;       // area light: leaf slot of its triangle; infinite light: its DevEnvMap (= its own index) or -1 (constant map);
+                    // projection / goniometric light: its DevLightMap (= its own index)
     int two_sided;
     float area;     // Triangle::area (triangle.rs:323-328)
     float power_y;  // Light::power().y_value() for the power distribution
@@ -148,6 +149,17 @@ struct DevEnvMap {
     float w2l[9], l2w[9];  // upper 3x3 of world_to_light / light_to_world, row-major
 };
 
+// ProjectionLight / GonioPhotometricLight (lights/projection.rs, goniometric.rs): what the light needs beyond DevLight's pos / L /
+// w2l. One per light of a scene that holds such a light, named by DevLight::slot (= the light's own index). Level 0 of the map's
+// MIPMap (pbrt_hip_scene_set_light_map; the lookups are bilinear there), not multiplied by I; texels == null: no map, the
+// lookup is exactly 1.
+struct DevLightMap {
+    const float4* texels;    // w * h, row t = 0: projection the lowest screen y, goniometric theta = 0 (light-space +y)
+    int w, h;
+    float inv_tan;           // projection: 1 / tan(radians(fov) / 2), Transform::perspective's x / y scale
+    float screen_bounds[4];  // projection: min.x, min.y, max.x, max.y
+};
+
 struct DevSceneData {
     DevBVH bvh;
     const int* slot_prim;       // leaf slot -> caller's triangle index
@@ -165,6 +177,7 @@ struct DevSceneData {
     DevDistribution1D light_distrib_uniform, light_distrib_power;
     const DevEnvMap* env_maps;  // [n_lights] once a map was set (DevLight::slot names the entry), else null
     const DevDisney* disney;    // [n_materials]: the blocks of the kMatDisney rows
+    const DevLightMap* light_maps;  // [n_lights] when the scene holds a projection or goniometric light, else null
 };
 
 }  // namespace pb
@@ -180,6 +193,10 @@ struct PbrtHipScene {
     bool glossy = false;  // a plastic or metal material in the table: the shading kernels' glossy instantiations run
     bool bxdfs = false;   // a kMatOrenNayar / kMatRoughGlass / kMatSubstrate row in the table: their level-2 instantiations run
     bool disney = false;  // a kMatDisney row in the table: their level-3 instantiations run
+    bool light_maps = false;  // a projection or goniometric light in the table: the shading kernels' map-light builds run
+    std::vector<pb::DevLightMap> h_light_maps;  // the device table's host copy
+    std::vector<void*> light_map_allocs;         // per light: its texels on the device (pbrt_hip_scene_set_light_map) or null
+    std::vector<float> light_fov;                // per light: PbrtLight.fov (projection)
     std::vector<int> light_samples;  // max(1, n_samples) per light (light.rs:76)
     // image maps of infinite lights (pbrt_hip_scene_set_environment_map): per light its descriptor and its device arrays
     std::vector<pb::DevEnvMap> h_env;

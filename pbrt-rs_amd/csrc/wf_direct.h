@@ -32,12 +32,15 @@ struct DirectState {
 // LEVEL_SHP = LEVEL, + 4 in the builds for scenes with general quadric shapes (SHP as shade_bounce's, wf_path.h): <DIRECT, 7>,
 // <WHITTED, 7> and <AO, 4>, on the level-3 BSDF set, which serves every material table. (A value of the existing parameter, not a
 // body shared through a wrapper: that moved the registers of three of the instantiations for the other scenes.)
-constexpr int kDirectShapes = 4;
+// + 8 in the builds for scenes with a projection or goniometric light (ML as light_sample_li's): <DIRECT, 11> and <WHITTED, 11>;
+// the builds for shapes take ML too. AO samples no light.
+constexpr int kDirectShapes = 4, kDirectMapLights = 8;
 template <int MODE, int LEVEL_SHP>
 __global__ void __launch_bounds__(256, ((LEVEL_SHP & 3) >= 1 && MODE == PBRT_INTEGRATOR_DIRECT) ? 1 : PB_DIRECT_WAVES) k_shade_direct(ShadeConsts sc, PathState ps, DirectState ds, Queues qin,
                                                         Queues qout, PassParams pp, TileList tiles, uint32_t n_in) {
     constexpr int LEVEL = LEVEL_SHP & 3;
     constexpr bool SHP = (LEVEL_SHP & kDirectShapes) != 0;
+    constexpr bool ML = SHP || (LEVEL_SHP & kDirectMapLights) != 0;
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool active = i < n_in;
     uint32_t p = active ? qin.shade[i] : 0u;
@@ -210,7 +213,7 @@ __global__ void __launch_bounds__(256, ((LEVEL_SHP & 3) >= 1 && MODE == PBRT_INT
                 stage += 1;
                 V3 wi, li, p1, p1_err, p1_n;
                 float pdf;
-                light_sample_li<SHP>(sc, sf, lt, ul0, ul1, &wi, &pdf, &li, &p1, &p1_err, &p1_n);
+                light_sample_li<SHP, ML>(sc, sf, lt, ul0, ul1, &wi, &pdf, &li, &p1, &p1_err, &p1_n);
                 if (is_black(li) || pdf == 0.0f) continue;
                 V3 f = V3{0.0f, 0.0f, 0.0f};
                 float spdf;
@@ -261,10 +264,10 @@ __global__ void __launch_bounds__(256, ((LEVEL_SHP & 3) >= 1 && MODE == PBRT_INT
                 if (GLOSSY) {
                     typename LevelBsdf<LEVEL>::type nsb;
                     load_bsdf(sc, sf.material, sc.materials[sf.material], &nsb);
-                    nee_flags = estimate_direct_emit<SHP>(sc, RecordSink{ps, p}, sf, fr, nsb.n > 0, nsb, light_num, ul0, ul1, us0, us1, pick_pdf, T);
+                    nee_flags = estimate_direct_emit<SHP, ML>(sc, RecordSink{ps, p}, sf, fr, nsb.n > 0, nsb, light_num, ul0, ul1, us0, us1, pick_pdf, T);
                 } else {
                     bool matte = (mat.type == PBRT_MAT_MATTE) && !is_black(kd);
-                    nee_flags = estimate_direct_emit<SHP>(sc, RecordSink{ps, p}, sf, fr, matte, MatteBsdf{kd}, light_num, ul0, ul1, us0, us1, pick_pdf, T);
+                    nee_flags = estimate_direct_emit<SHP, ML>(sc, RecordSink{ps, p}, sf, fr, matte, MatteBsdf{kd}, light_num, ul0, ul1, us0, us1, pick_pdf, T);
                 }
                 stage += 1;
                 if (nee_flags) {

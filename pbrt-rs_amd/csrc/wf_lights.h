@@ -221,8 +221,9 @@ PB_DEV float shape_light_pdf(const DevBVH& bvh, int slot, const DevShape& sh, fl
 
 // Light::sample_li (light.rs:35-42): DiffuseAreaLight (diffuse.rs:60-81 with Triangle::sample / Shape::sample2)
 // or InfiniteAreaLight (infinite.rs:96-129). Outputs the visibility tester's far point (p1, error, normal).
-// SHP: the scene may hold general shapes (see surface_from_hit).
-template <bool SHP = false>
+// SHP: the scene may hold general shapes (see surface_from_hit). ML: it may hold a ProjectionLight or a GonioPhotometricLight
+// (projection.rs:113-132 with pbrt-v3's product, D88; goniometric.rs:84-103); off, every instantiation compiles as it did without them.
+template <bool SHP = false, bool ML = false>
 PB_DEV void light_sample_li(const ShadeConsts& sc, const Surf& sf, const DevLight& lt, float ul0, float ul1, V3* wi_o,
                             float* pdf_o, V3* li_o, V3* p1_o, V3* p1_err_o, V3* p1_n_o) {
     V3 wi = V3{0.0f, 0.0f, 0.0f};
@@ -315,6 +316,36 @@ PB_DEV void light_sample_li(const ShadeConsts& sc, const Surf& sf, const DevLigh
         light_pdf = 1.0f;
         p1 = sf.p + wi * (2.0f * sc.world_radius);
         li = Lc;
+    } else if (ML && (lt.type == PBRT_LIGHT_PROJECTION || lt.type == PBRT_LIGHT_GONIOMETRIC)) {
+        // the far point and wi as PointLight::sample_li's; I * projection(-wi) / d^2 or I * scale(-wi) / d^2
+        p1 = V3{lt.pos[0], lt.pos[1], lt.pos[2]};
+        V3 dv = p1 - sf.p;
+        wi = normalize(dv);
+        light_pdf = 1.0f;
+        float d2 = len2(dv);
+        V3 wl = mat3_mul(lt.w2l, -wi);
+        const DevLightMap& m = sc.light_maps[lt.slot];  // read only here, after the type test
+        bool lit = true;
+        float ms = 0.0f, mt = 0.0f;
+        if (lt.type == PBRT_LIGHT_PROJECTION) {
+            // ProjectionLight::projection (projection.rs:90-106): perspective(fov, 1e-3, 1e30) on the point wl, not normalised
+            lit = !(wl.z < 1e-3f);
+            if (lit) {
+                float px = m.inv_tan * wl.x / wl.z, py = m.inv_tan * wl.y / wl.z;
+                const float x0 = m.screen_bounds[0], y0 = m.screen_bounds[1], x1 = m.screen_bounds[2], y1 = m.screen_bounds[3];
+                lit = px >= x0 && px <= x1 && py >= y0 && py <= y1;  // Bounds2::inside, closed on both ends
+                ms = (px - x0) / (x1 - x0);                           // Bounds2::offset
+                mt = (py - y0) / (y1 - y0);
+            }
+        } else {
+            // GonioPhotometricLight::scale (goniometric.rs:65-76): y and z swapped, then the spherical mapping
+            wl = normalize(wl);
+            env_uv(V3{wl.x, wl.z, wl.y}, &ms, &mt, nullptr);
+        }
+        if (lit) {  // (behind hither or outside the window: 0 before any texel is touched)
+            if (m.texels) li = mulv(Lc, env_lookup(m, ms, mt)) / d2;
+            else li = Lc / d2;  // no map: exactly the point light's I / d^2
+        }
     } else if (lt.slot >= 0) {
         // InfiniteAreaLight::sample_li (infinite.rs:96-129) with an image map: light_to_world on the direction, not
         // renormalised (rigid transforms only give an unbiased estimate, as in the reference)
@@ -370,7 +401,7 @@ PB_DEV float radical_inverse_small(int base_index, uint32_t a) {  // lowdiscrepa
     const uint32_t primes[5] = {2u, 3u, 5u, 7u, 11u};
     return halton_radical_inverse(primes[base_index], nullptr, a);
 }
-template <bool SHP>
+template <bool SHP, bool ML = false>
 PB_DEV void spatial_light_tables(const ShadeConsts& sc, float* __restrict__ table) {
     size_t voxel = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     size_t n_voxels = (size_t)sc.n_voxel[0] * sc.n_voxel[1] * sc.n_voxel[2];
@@ -401,7 +432,7 @@ PB_DEV void spatial_light_tables(const ShadeConsts& sc, float* __restrict__ tabl
             DevLight lt = sc.lights[j];
             V3 wi, li, p1, p1_err, p1_n;
             float pdf;
-            light_sample_li<SHP>(sc, sf, lt, u0, u1, &wi, &pdf, &li, &p1, &p1_err, &p1_n);
+            light_sample_li<SHP, ML>(sc, sf, lt, u0, u1, &wi, &pdf, &li, &p1, &p1_err, &p1_n);
             if (pdf > 0.0f) func[j] += (0.212671f * li.x + 0.715160f * li.y + 0.072169f * li.z) / pdf;
         }
     }
@@ -422,7 +453,9 @@ PB_DEV void spatial_light_tables(const ShadeConsts& sc, float* __restrict__ tabl
     func[2 * n + 1] = func_int;
 }
 __global__ void k_spatial_light_tables(ShadeConsts sc, float* __restrict__ table) { spatial_light_tables<false>(sc, table); }
-__global__ void k_spatial_light_tables_shapes(ShadeConsts sc, float* __restrict__ table) { spatial_light_tables<true>(sc, table); }
+__global__ void k_spatial_light_tables_shapes(ShadeConsts sc, float* __restrict__ table) { spatial_light_tables<true, true>(sc, table); }
+// a scene with a projection or goniometric light
+__global__ void k_spatial_light_tables_maps(ShadeConsts sc, float* __restrict__ table) { spatial_light_tables<false, true>(sc, table); }
 
 // estimate_direct (integrator.rs:136-266), first part: sample the light, evaluate the BSDF, sample the
 // BSDF, evaluate the light pdf. Writes the shadow ray (slot 2), the MIS ray (slot 1) and the pending
@@ -430,7 +463,7 @@ __global__ void k_spatial_light_tables_shapes(ShadeConsts sc, float* __restrict_
 // staging until the index is known); returns PF_NEE_* flags for the rays that must be traced. `nonspecular` = the
 // BSDF has a non-specular lobe, `bsdf` its lobes (MatteBsdf: matte only; NsBsdf: matte, plastic or metal; GenBsdf: any row of levels 0-2; DisneyBsdf: any); otherwise f == 0
 // and nothing is emitted.
-template <bool SHP = false, class Bsdf, class Sink>
+template <bool SHP = false, bool ML = false, class Bsdf, class Sink>
 PB_DEV int estimate_direct_emit(const ShadeConsts& sc, const Sink& out, const Surf& sf, const Frame& fr,
                                 bool nonspecular, const Bsdf& bsdf, int light_num, float ul0, float ul1, float us0, float us1,
                                 float pick_pdf, V3 beta) {
@@ -439,7 +472,7 @@ PB_DEV int estimate_direct_emit(const ShadeConsts& sc, const Sink& out, const Su
     DevLight lt = sc.lights[light_num];
     V3 wi, li, p1, p1_err, p1_n;
     float light_pdf;
-    light_sample_li<SHP>(sc, sf, lt, ul0, ul1, &wi, &light_pdf, &li, &p1, &p1_err, &p1_n);
+    light_sample_li<SHP, ML>(sc, sf, lt, ul0, ul1, &wi, &light_pdf, &li, &p1, &p1_err, &p1_n);
     int nee_flags = 0;
     V3 A = V3{0.0f, 0.0f, 0.0f};
     if (light_pdf > 0.0f && !is_black(li)) {

@@ -65,8 +65,9 @@ struct ShadeBins {
 // p = qin.shade[rec] with its persistent state at p, and the transient records of this generation at rec. What the path
 // hands to the next launch is staged in LDS and written to the next generation at its position in qout.shade.
 // SHP: the scene may hold general quadric shapes (surface_from_hit, light_sample_li); k_shade_shapes below is that build, so the
-// kernels of every other scene compile as they did without it.
-template <bool BIN, int LEVEL, bool SHP>
+// kernels of every other scene compile as they did without it. ML: it may hold a projection or goniometric light (light_sample_li);
+// k_shade_maps below is that build, and k_shade_shapes takes it too.
+template <bool BIN, int LEVEL, bool SHP, bool ML = false>
 PB_DEV void shade_bounce(const ShadeConsts& sc, const PathState& ps, const Queues& qin, const Queues& qout, const PassParams& pp,
                          const TileList& tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
     constexpr bool GLOSSY = LEVEL >= 1;
@@ -191,10 +192,10 @@ PB_DEV void shade_bounce(const ShadeConsts& sc, const PathState& ps, const Queue
                             float ul0, ul1, us0, us1;
                             samp_2d(pp, sm, &ul0, &ul1);
                             samp_2d(pp, sm, &us0, &us1);
-                            int nee_flags = GLOSSY ? estimate_direct_emit<SHP>(sc, stage, sf, fr, true, nsb, light_num, ul0, ul1, us0,
-                                                                               us1, pick_pdf, beta)
-                                                   : estimate_direct_emit<SHP>(sc, stage, sf, fr, true, MatteBsdf{kd}, light_num, ul0, ul1,
-                                                                               us0, us1, pick_pdf, beta);
+                            int nee_flags = GLOSSY ? estimate_direct_emit<SHP, ML>(sc, stage, sf, fr, true, nsb, light_num, ul0, ul1, us0,
+                                                                                   us1, pick_pdf, beta)
+                                                   : estimate_direct_emit<SHP, ML>(sc, stage, sf, fr, true, MatteBsdf{kd}, light_num, ul0, ul1,
+                                                                                   us0, us1, pick_pdf, beta);
                             flags |= nee_flags & 0xff;
                             emit_shadow = (nee_flags & PF_NEE_SHADOW) != 0;
                             emit_mis = (nee_flags & PF_NEE_MIS) != 0;
@@ -277,7 +278,13 @@ __global__ void __launch_bounds__(256, LEVEL == 3 ? 2 : PB_SHADE_WAVES) k_shade(
 template <bool BIN>
 __global__ void __launch_bounds__(256, 2) k_shade_shapes(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
                                                         TileList tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
-    shade_bounce<BIN, 3, true>(sc, ps, qin, qout, pp, tiles, n_in, order);
+    shade_bounce<BIN, 3, true, true>(sc, ps, qin, qout, pp, tiles, n_in, order);
+}
+// scenes with a projection or goniometric light: the most general level only, bounded at two waves as level 3 is
+template <bool BIN>
+__global__ void __launch_bounds__(256, 2) k_shade_maps(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
+                                                      TileList tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
+    shade_bounce<BIN, 3, false, true>(sc, ps, qin, qout, pp, tiles, n_in, order);
 }
 
 }  // namespace pb

@@ -414,11 +414,14 @@ struct ShadeConsts {
     // loops are being counted (pbrt_hip_set_counting(1): the reference walks those rays to their closest hit)
     int mis_bool;
     const DevDisney* disney;  // [n_materials]: the blocks of the kMatDisney rows (wf_disney.h)
+    const DevLightMap* light_maps;  // side table of the projection / goniometric lights (DevLight::slot), null when there are none
 };
 
 // ---- InfiniteAreaLight with an image map (DevEnvMap): one lookup and one Distribution2D for le, sample_li and pdf_li ----
-// MIPMap::lookup at width 0 (mipmap.rs:211-215): MIPMap::triangle on level 0, ImageWrap::Repeat, signed floor (D60)
-PB_DEV V3 env_lookup(const DevEnvMap& e, float st_s, float st_t) {
+// MIPMap::lookup at width 0 (mipmap.rs:211-215): MIPMap::triangle on level 0, ImageWrap::Repeat, signed floor (D60).
+// Map: DevEnvMap, or the DevLightMap of a projection / goniometric light (texels, w, h)
+template <class Map>
+PB_DEV V3 env_lookup(const Map& e, float st_s, float st_t) {
     float s = st_s * (float)e.w - 0.5f, t = st_t * (float)e.h - 0.5f;
     if (!(s >= -1.0f && s <= (float)e.w)) s = -0.5f;  // a NaN direction: keep the fetches inside the level
     if (!(t >= -1.0f && t <= (float)e.h)) t = -0.5f;

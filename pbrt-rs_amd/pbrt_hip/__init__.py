@@ -42,6 +42,7 @@ EXPORTS = [
     "pbrt_hip_scene_set_environment_map", "pbrt_hip_envmap_tables", "pbrt_hip_scene_set_material_roughness", "pbrt_hip_bsdf_query",
     "pbrt_hip_scene_set_material", "pbrt_hip_scene_set_disney_material",
     "pbrt_hip_shape_world_bounds", "pbrt_hip_scene_create_with_shapes",
+    "pbrt_hip_scene_set_light_map", "pbrt_hip_light_map_tables", "pbrt_hip_light_sample_li",
 ]
 MAT_NONE, MAT_MATTE, MAT_MIRROR, MAT_GLASS, MAT_PLASTIC, MAT_METAL = (scenes.MAT_NONE, scenes.MAT_MATTE, scenes.MAT_MIRROR,
                                                                       scenes.MAT_GLASS, scenes.MAT_PLASTIC, scenes.MAT_METAL)
@@ -185,6 +186,10 @@ def lib():
         L.pbrt_hip_scene_set_material.argtypes = [vp, i32, vp]
         L.pbrt_hip_scene_set_disney_material.argtypes = [vp, i32, vp]
         L.pbrt_hip_film_to_rgb.restype = None
+        L.pbrt_hip_scene_set_light_map.argtypes = [vp, i32, vp, i32, i32]
+        L.pbrt_hip_light_map_tables.argtypes = [i32, ctypes.c_float, vp, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp, vp,
+                                                ctypes.POINTER(ctypes.c_float), vp, ctypes.POINTER(ctypes.c_char_p)]
+        L.pbrt_hip_light_sample_li.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -411,13 +416,16 @@ class Scene:
         """device_build=True: BVHAccel::new(HLBVH) built and laid out on the GPU (pbrt_hip_scene_create_hlbvh);
         self.build_ms / self.layout_ms then hold the HIP-event times and self.nodes is None.
         scene["material_descs"] = {row: descriptor} (optional): set_material(row, descriptor) after creation;
-        scene["disney_descs"] = {row: descriptor} (optional): set_disney_material(row, descriptor) after that."""
+        scene["disney_descs"] = {row: descriptor} (optional): set_disney_material(row, descriptor) after that;
+        scene["light_maps"] = {light: rgb} (optional): set_light_map(light, rgb) after that."""
         self._create(ctx, scene, max_prims_in_node, split_method, bvh, device_build)
         try:
             for row, desc in (scene.get("material_descs") or {}).items():
                 self.set_material(row, desc)
             for row, desc in (scene.get("disney_descs") or {}).items():
                 self.set_disney_material(row, desc)
+            for light, rgb in (scene.get("light_maps") or {}).items():
+                self.set_light_map(light, rgb)
         except Exception:
             self.close()  # a refused descriptor: the scene that was just created does not outlive the constructor
             raise
@@ -705,6 +713,28 @@ class Scene:
         self.ctx.check(lib().pbrt_hip_scene_set_environment_map(self.h, int(light), _p(rgb), rgb.shape[1], rgb.shape[0], _p(m)),
                        "pbrt_hip_scene_set_environment_map")
 
+    def set_light_map(self, light, rgb):
+        """The image map of light `light` (scenes.projection_light / goniometric_light): rgb (h, w, 3) float32, row 0 = t 0
+        (projection: the lowest screen y; goniometric: theta 0 = light-space +y). Calling it again replaces the map."""
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        if rgb.ndim != 3 or rgb.shape[2] != 3:
+            raise ValueError("rgb must be (h, w, 3)")
+        self.ctx.check(lib().pbrt_hip_scene_set_light_map(self.h, int(light), _p(rgb), rgb.shape[1], rgb.shape[0]),
+                       "pbrt_hip_scene_set_light_map")
+
+    def light_sample_li(self, light, p, u=None):
+        """Light::sample_li of light `light` on the device from bare interactions at the world points p (n, 3); u (n, 2) the
+        sample, None for delta lights. Returns wi (n, 3), pdf (n,), li (n, 3); no visibility test."""
+        p = np.ascontiguousarray(p, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 2)
+            assert len(u) == n
+        wi, pdf, li = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
+        self.ctx.check(lib().pbrt_hip_light_sample_li(self.h, int(light), n, _p(p), _p(u), _p(wi), _p(pdf), _p(li)),
+                       "pbrt_hip_light_sample_li")
+        return wi, pdf, li
+
     def set_material_roughness(self, m, u, v=None, remap=True):
         """TrowbridgeReitzDistribution alphas of plastic / metal material m: roughness_to_alpha(u, v) with remap, else (u, v).
         v = None: isotropic (plastic must be)."""
@@ -940,6 +970,28 @@ def envmap_tables(rgb, L=(1.0, 1.0, 1.0)):
     if rc != 0:
         raise PbrtHipError(f"pbrt_hip_envmap_tables failed ({rc}): {(why.value or b'').decode()}")
     return level0, func, power
+
+
+def light_map_tables(light_type, rgb=None, fov=0.0):
+    """pbrt_hip_light_map_tables: ProjectionLight::new's / GonioPhotometricLight::new's tables for an (h, w, 3) map (None: no map).
+    Returns dict(level0 (rh, rw, 3) or None, lookup (3,), screen_bounds (4,), cos_total_width, power (3,) for I = 1)."""
+    w = h = 0
+    if rgb is not None:
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        h, w = rgb.shape[:2]
+    rw, rh, why, cos_tw = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_char_p(), ctypes.c_float()
+
+    def call(level0, lookup, sb, power):
+        rc = lib().pbrt_hip_light_map_tables(int(light_type), float(fov), _p(rgb), w, h, ctypes.byref(rw), ctypes.byref(rh), _p(level0),
+                                             _p(lookup), _p(sb), ctypes.byref(cos_tw), _p(power), ctypes.byref(why))
+        if rc != 0:
+            raise PbrtHipError(f"pbrt_hip_light_map_tables failed ({rc}): {(why.value or b'').decode()}")
+
+    call(None, None, None, None)
+    level0 = np.zeros((rh.value, rw.value, 3), dtype=np.float32) if rgb is not None else None
+    lookup, sb, power = np.zeros(3, np.float32), np.zeros(4, np.float32), np.zeros(3, np.float32)
+    call(level0, lookup, sb, power)
+    return dict(level0=level0, lookup=lookup, screen_bounds=sb, cos_total_width=float(cos_tw.value), power=power)
 
 
 def write_exr(path, rgb):

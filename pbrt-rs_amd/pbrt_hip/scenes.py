@@ -12,7 +12,7 @@ import numpy as np
 MATERIAL_DTYPE = np.dtype([("type", "<i4"), ("kd", "<f4", 3), ("kt", "<f4", 3), ("eta", "<f4")])
 LIGHT_DTYPE = np.dtype([("type", "<i4"), ("L", "<f4", 3), ("prim", "<i4"), ("two_sided", "<i4"),
                         ("n_samples", "<i4"), ("pad", "<i4"), ("pos", "<f4", 3), ("cos_total_width", "<f4"),
-                        ("cos_falloff_start", "<f4"), ("world_to_light", "<f4", 9), ("pad2", "<i4", 2)])
+                        ("cos_falloff_start", "<f4"), ("world_to_light", "<f4", 9), ("fov", "<f4"), ("pad2", "<i4")])
 CAMERA_DTYPE = np.dtype([("camera_to_world", "<f4", 16), ("raster_to_camera", "<f4", 16),
                          ("lens_radius", "<f4"), ("focal_distance", "<f4"),
                          ("shutter_open", "<f4"), ("shutter_close", "<f4"), ("kind", "<i4"), ("pad", "<i4", 3)])
@@ -33,6 +33,7 @@ assert RAY_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 32 and NODE_DTYPE.item
 
 MAT_NONE, MAT_MATTE, MAT_MIRROR, MAT_GLASS, MAT_PLASTIC, MAT_METAL = 0, 1, 2, 3, 4, 5
 LIGHT_DIFFUSE_AREA, LIGHT_INFINITE, LIGHT_POINT, LIGHT_SPOT, LIGHT_DISTANT = 0, 1, 2, 3, 4
+LIGHT_PROJECTION, LIGHT_GONIOMETRIC = 5, 6
 
 _PCG32_MULT = np.uint64(0x5851F42D4C957F2D)
 _PCG32_DEFAULT_STATE = np.uint64(0x853C49E6748FEA9B)
@@ -184,6 +185,27 @@ def distant_light(w_from_surface_to_light, radiance):
     l = np.zeros((), dtype=LIGHT_DTYPE)
     l["type"], l["L"], l["prim"], l["n_samples"], l["pos"] = LIGHT_DISTANT, radiance, -1, 1, w / np.linalg.norm(w)
     return l
+
+
+def _map_light(kind, light_to_world, intensity, fov):
+    """light_to_world: 4x4 affine (None = identity); p_light and the inverse upper 3x3 are formed in float64 and rounded once."""
+    m = np.eye(4) if light_to_world is None else np.asarray(light_to_world, dtype=np.float32).astype(np.float64).reshape(4, 4)
+    l = np.zeros((), dtype=LIGHT_DTYPE)
+    l["type"], l["L"], l["prim"], l["n_samples"], l["pos"], l["fov"] = kind, intensity, -1, 1, m[:3, 3], fov
+    l["world_to_light"] = np.linalg.inv(m[:3, :3]).reshape(9)
+    return l
+
+
+def projection_light(light_to_world, intensity, fov):
+    """ProjectionLight::new (lights/projection.rs:36-88) without its map (Scene.set_light_map or scene["light_maps"] attach one):
+    a projector at light_to_world * (0, 0, 0) looking down light-space +z, fov in degrees across the shorter side of its window."""
+    return _map_light(LIGHT_PROJECTION, light_to_world, intensity, fov)
+
+
+def goniometric_light(light_to_world, intensity):
+    """GonioPhotometricLight::new (lights/goniometric.rs:32-63) without its map: a point light at light_to_world * (0, 0, 0) whose
+    intensity a lat-long map scales by direction (theta from light-space +y, phi from +x towards +z)."""
+    return _map_light(LIGHT_GONIOMETRIC, light_to_world, intensity, 0.0)
 
 
 def _shape(kind, radius, z_min, z_max, inner_radius, phi_max, to_world, material, light, reverse_orientation):

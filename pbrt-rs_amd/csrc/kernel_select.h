@@ -1,0 +1,127 @@
+// kernel_select.h — which kernel a launch runs, decided in one place (host only; no kernel lives here).
+//
+// Traversal: choose_trace() reads the scene and the context once and dispatch() turns the answer into compile-time constants
+// for a caller-supplied generic lambda; wavefront_render (render.hip) launches k_trace* from it, launch_batch (pbrt_hip.hip)
+// k_intersect_batch*. Shading: scene_needs() states what the scene's tables ask of the shading kernels and the three lookups
+// below return the instantiation from constexpr tables; they name the kernels of wavefront.h, so only a translation unit that
+// has included it (and says so with PB_SELECT_SHADING_KERNELS) sees them.
+#pragma once
+#include <type_traits>
+
+#include "scene.h"
+#include "trace_wide.h"
+
+namespace pb {
+
+// ---- traversal ----
+enum class TraceKind { Stackless, Wide, Shapes, Spheres, Binary };
+struct TraceChoice {
+    TraceKind kind;
+    int inst;    // trace_persistent.h: INST (0 single level, 1 instances of one aggregate, 2 general top level)
+    bool count;  // the COUNT instantiation: count_traversal == 1 for the binary families, == 2 for the wide one
+    bool ok;     // false: PBRT_TRAVERSAL_STACKLESS does not apply to this scene (last_error says why); launch nothing
+};
+
+inline TraceChoice choose_trace(const PbrtHipScene* s) {
+    const PbrtHipContext* ctx = s->ctx;
+    TraceChoice c{TraceKind::Binary, s->d.bvh.instanced ? (s->d.bvh.general_top ? 2 : 1) : 0, ctx->count_traversal == 1, true};
+    if (ctx->traversal == PBRT_TRAVERSAL_STACKLESS) {
+        c.kind = TraceKind::Stackless;  // single level, no counting: stackless_applies refuses everything else
+        c.ok = stackless_applies(s);
+    } else if (s->has_wide && ctx->count_traversal != 1 && ctx->traversal == PBRT_TRAVERSAL_AUTO) {
+        c.kind = TraceKind::Wide;
+        c.count = ctx->count_traversal == 2;
+    } else if (s->d.bvh.has_spheres) {  // single-level scenes only (checked at creation); 2: general quadric shapes
+        c.kind = s->d.bvh.has_spheres == 2 ? TraceKind::Shapes : TraceKind::Spheres;
+    }
+    return c;
+}
+
+// grid of the wide kernels' <COUNT, INST> instantiation (their launch bounds: trace_wide.h)
+template <bool COUNT, int INST>
+inline int wide_grid(const PbrtHipScene* s) {
+    return persistent_grid(s, (COUNT || INST) ? PB_WIDE_INST_WAVES : PB_WIDE_WAVES, wide_stack_lds(INST), wide_world_lds_bytes(INST));
+}
+
+template <TraceKind K>
+using TraceKindC = std::integral_constant<TraceKind, K>;
+
+// Calls f(TraceKindC<kind>, std::bool_constant<COUNT>, std::integral_constant<int, INST>) for the choice. Only the combinations
+// the kernels exist for are ever formed: shapes and spheres are single level, the stackless walk has neither COUNT nor INST.
+template <class F>
+inline void dispatch(const TraceChoice& c, F&& f) {
+    auto with_count = [&](auto kind, auto inst) {
+        if (c.count)
+            f(kind, std::true_type{}, inst);
+        else
+            f(kind, std::false_type{}, inst);
+    };
+    auto with_inst = [&](auto kind) {
+        if (c.inst == 2)
+            with_count(kind, std::integral_constant<int, 2>{});
+        else if (c.inst == 1)
+            with_count(kind, std::integral_constant<int, 1>{});
+        else
+            with_count(kind, std::integral_constant<int, 0>{});
+    };
+    switch (c.kind) {
+        case TraceKind::Stackless: f(TraceKindC<TraceKind::Stackless>{}, std::false_type{}, std::integral_constant<int, 0>{}); break;
+        case TraceKind::Wide: with_inst(TraceKindC<TraceKind::Wide>{}); break;
+        case TraceKind::Shapes: with_count(TraceKindC<TraceKind::Shapes>{}, std::integral_constant<int, 0>{}); break;
+        case TraceKind::Spheres: with_count(TraceKindC<TraceKind::Spheres>{}, std::integral_constant<int, 0>{}); break;
+        case TraceKind::Binary: with_inst(TraceKindC<TraceKind::Binary>{}); break;
+    }
+}
+
+// ---- shading ----
+// What the scene's tables ask of a shading kernel. Precedence, as the instantiations are built: general quadric shapes win over
+// everything (their builds carry the level-3 BSDF set and the map lights), a projection or goniometric light wins over the
+// material level (the map-light builds are level 3 too), and AO reads neither a BSDF nor a light.
+struct SceneNeeds {
+    bool shapes;      // bvh.has_spheres == 2
+    bool light_maps;  // a projection or goniometric light in the table
+    int level;        // 0 matte / mirror / glass, 1 plastic or metal, 2 a row of pbrt_hip_scene_set_material, 3 a Disney row
+    int column() const { return shapes ? 0 : light_maps ? 1 : 5 - level; }  // of the tables below: in that precedence, most general first
+};
+inline SceneNeeds scene_needs(const PbrtHipScene* s) {
+    return SceneNeeds{s->d.bvh.has_spheres == 2, s->light_maps, s->disney ? 3 : s->bxdfs ? 2 : s->glossy ? 1 : 0};
+}
+
+#ifdef PB_SELECT_SHADING_KERNELS
+using DirectKernel = void (*)(ShadeConsts, PathState, DirectState, Queues, Queues, PassParams, TileList, uint32_t);
+using PathKernel = void (*)(ShadeConsts, PathState, Queues, Queues, PassParams, TileList, uint32_t, const uint32_t*);
+using SpatialKernel = void (*)(ShadeConsts, float*);
+// The tables list every instantiation the library holds, once. Their initialisers are also where the compiler first meets each
+// instantiation, and the code it generates for some of the kernels depends on that order (profiles/r11_render_driver.txt): the
+// rows and columns below keep the order the kernels have always been named in.
+
+// the build of the SpatialLightDistribution tables (wf_lights.h)
+inline SpatialKernel spatial_tables_kernel(const SceneNeeds& n) {
+    static constexpr SpatialKernel table[3] = {k_spatial_light_tables_shapes, k_spatial_light_tables_maps, k_spatial_light_tables};
+    return table[n.shapes ? 0 : n.light_maps ? 1 : 2];
+}
+
+// k_shade_direct<MODE, LEVEL_SHP> (wf_direct.h) for DirectLighting, Whitted or AO
+inline DirectKernel direct_kernel(const SceneNeeds& n, int integrator) {
+    constexpr int D = PBRT_INTEGRATOR_DIRECT, W = PBRT_INTEGRATOR_WHITTED, AO = PBRT_INTEGRATOR_AO;
+    static constexpr DirectKernel lit[6][2] = {{k_shade_direct<D, 3 + kDirectShapes>, k_shade_direct<W, 3 + kDirectShapes>},
+                                               {k_shade_direct<D, 3 + kDirectMapLights>, k_shade_direct<W, 3 + kDirectMapLights>},
+                                               {k_shade_direct<D, 3>, k_shade_direct<W, 3>},
+                                               {k_shade_direct<D, 2>, k_shade_direct<W, 2>},
+                                               {k_shade_direct<D, 1>, k_shade_direct<W, 1>},
+                                               {k_shade_direct<D, 0>, k_shade_direct<W, 0>}};
+    static constexpr DirectKernel ao[2] = {k_shade_direct<AO, kDirectShapes>, k_shade_direct<AO, 0>};
+    if (integrator == D || integrator == W) return lit[n.column()][integrator == W];
+    return ao[n.shapes ? 0 : 1];
+}
+
+// k_shade_shapes<BIN> / k_shade_maps<BIN> / k_shade<BIN, LEVEL> (wf_path.h) for the path integrator
+inline PathKernel path_kernel(const SceneNeeds& n, bool bin) {
+    static constexpr PathKernel table[2][6] = {
+        {k_shade_shapes<true>, k_shade_maps<true>, k_shade<true, 3>, k_shade<true, 2>, k_shade<true, 1>, k_shade<true, 0>},
+        {k_shade_shapes<false>, k_shade_maps<false>, k_shade<false, 3>, k_shade<false, 2>, k_shade<false, 1>, k_shade<false, 0>}};
+    return table[bin ? 0 : 1][n.column()];
+}
+#endif  // PB_SELECT_SHADING_KERNELS
+
+}  // namespace pb

@@ -16,6 +16,7 @@
 
 #include "host_envmap.h"
 #include "host_wide.h"
+#include "kernel_select.h"
 #include "scene.h"
 #include "trace.h"
 #include "trace_persistent.h"
@@ -1816,9 +1817,9 @@ static int launch_batch(PbrtHipScene* s, const PbrtRay* d_rays, int64_t n, PbrtH
         ctx->last_error = "batch too large for one launch (split it below 2^32 rays)";
         return PBRT_HIP_ERR_INVALID;
     }
-    const bool wide = s->has_wide && ctx->count_traversal != 1 && ctx->traversal == PBRT_TRAVERSAL_AUTO;
-    const bool stackless = ctx->traversal == PBRT_TRAVERSAL_STACKLESS;
-    if (stackless && !stackless_applies(s)) return PBRT_HIP_ERR_INVALID;
+    const TraceChoice choice = choose_trace(s);
+    if (!choice.ok) return PBRT_HIP_ERR_INVALID;
+    const bool wide = choice.kind == TraceKind::Wide;
     if (wide && ctx->special_capacity < (size_t)n) {  // room for the queue positions of the rays the wide kernel leaves out
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (ctx->d_special_list) (void)hipFree(ctx->d_special_list);
@@ -1829,54 +1830,29 @@ static int launch_batch(PbrtHipScene* s, const PbrtRay* d_rays, int64_t n, PbrtH
     }
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_work_counter, 0, kWorkCounters * sizeof(unsigned int), ctx->stream));
     if (ctx->time_trace) HIP_TRY(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-    {
-        BatchRayIO<ANY> io{s->d.slot_prim, s->d.slot_instance, d_rays, (uint32_t)n, d_hits, d_flags};
-        dim3 grid(persistent_grid(s)), block(kTraceBlock);
-        const int inst = s->d.bvh.instanced ? (s->d.bvh.general_top ? 2 : 1) : 0;  // trace_persistent.h: INST
-        const bool count_ref = ctx->count_traversal == 1, count_wide = ctx->count_traversal == 2;
-#define PB_LAUNCH_BINARY(COUNT, INST, SPH) \
-    hipLaunchKernelGGL((k_intersect_batch<ANY, COUNT, INST, SPH>), grid, block, 0, ctx->stream, s->d.bvh, io, ctx->d_work_counter, ctx->d_counters)
-#define PB_LAUNCH_WIDE(COUNT, INST)                                                                                                  \
-    hipLaunchKernelGGL((k_intersect_batch_wide<ANY, COUNT, INST>),                                                                   \
-                       dim3(persistent_grid(s, (COUNT || INST) ? PB_WIDE_INST_WAVES : PB_WIDE_WAVES, wide_stack_lds(INST), wide_world_lds_bytes(INST))), block, 0, ctx->stream, \
-                       wt, io, ctx->d_work_counter, ctx->d_counters)
-#define PB_LAUNCH_SPECIAL(INST) \
-    hipLaunchKernelGGL((k_intersect_batch_special<ANY, INST>), grid, block, 0, ctx->stream, s->d.bvh, sio, ctx->d_work_counter + kFollowUpCounter)
-        if (stackless) {
+    const BatchRayIO<ANY> io{s->d.slot_prim, s->d.slot_instance, d_rays, (uint32_t)n, d_hits, d_flags};
+    dispatch(choice, [&](auto kind, auto count, auto inst) {
+        constexpr TraceKind K = decltype(kind)::value;
+        constexpr bool COUNT = decltype(count)::value;
+        constexpr int INST = decltype(inst)::value;
+        const dim3 grid(persistent_grid(s)), block(kTraceBlock);
+        if constexpr (K == TraceKind::Stackless) {
             hipLaunchKernelGGL((k_intersect_batch_stackless<ANY>), dim3(stackless_grid(s)), block, 0, ctx->stream, s->d.bvh, io, ctx->d_work_counter);
-        } else if (wide) {
+        } else if constexpr (K == TraceKind::Wide) {  // the wide kernel, then the follow-up over the rays it left out
             WideTrees wt = s->wide;
             wt.special_list = ctx->d_special_list;
             wt.special_count = ctx->d_work_counter + kSpecialCount;
-            SpecialListIO<BatchRayIO<ANY>> sio{io, ctx->d_special_list, ctx->d_work_counter + kSpecialCount};
-            if (inst == 2) {
-                if (count_wide) PB_LAUNCH_WIDE(true, 2); else PB_LAUNCH_WIDE(false, 2);
-                PB_LAUNCH_SPECIAL(2);
-            } else if (inst == 1) {
-                if (count_wide) PB_LAUNCH_WIDE(true, 1); else PB_LAUNCH_WIDE(false, 1);
-                PB_LAUNCH_SPECIAL(1);
-            } else {
-                if (count_wide) PB_LAUNCH_WIDE(true, 0); else PB_LAUNCH_WIDE(false, 0);
-                PB_LAUNCH_SPECIAL(0);
-            }
-        } else if (s->d.bvh.has_spheres == 2) {  // general shapes; single-level scenes only (checked at creation)
-            if (count_ref)
-                hipLaunchKernelGGL((k_intersect_batch_shapes<ANY, true>), grid, block, 0, ctx->stream, s->d.bvh, io, ctx->d_work_counter, ctx->d_counters);
-            else
-                hipLaunchKernelGGL((k_intersect_batch_shapes<ANY, false>), grid, block, 0, ctx->stream, s->d.bvh, io, ctx->d_work_counter, ctx->d_counters);
-        } else if (s->d.bvh.has_spheres) {  // single-level scenes only (checked at creation)
-            if (count_ref) PB_LAUNCH_BINARY(true, 0, true); else PB_LAUNCH_BINARY(false, 0, true);
-        } else if (inst == 2) {
-            if (count_ref) PB_LAUNCH_BINARY(true, 2, false); else PB_LAUNCH_BINARY(false, 2, false);
-        } else if (inst == 1) {
-            if (count_ref) PB_LAUNCH_BINARY(true, 1, false); else PB_LAUNCH_BINARY(false, 1, false);
+            const SpecialListIO<BatchRayIO<ANY>> sio{io, ctx->d_special_list, ctx->d_work_counter + kSpecialCount};
+            hipLaunchKernelGGL((k_intersect_batch_wide<ANY, COUNT, INST>), dim3(wide_grid<COUNT, INST>(s)), block, 0, ctx->stream, wt, io,
+                               ctx->d_work_counter, ctx->d_counters);
+            hipLaunchKernelGGL((k_intersect_batch_special<ANY, INST>), grid, block, 0, ctx->stream, s->d.bvh, sio, ctx->d_work_counter + kFollowUpCounter);
+        } else if constexpr (K == TraceKind::Shapes) {
+            hipLaunchKernelGGL((k_intersect_batch_shapes<ANY, COUNT>), grid, block, 0, ctx->stream, s->d.bvh, io, ctx->d_work_counter, ctx->d_counters);
         } else {
-            if (count_ref) PB_LAUNCH_BINARY(true, 0, false); else PB_LAUNCH_BINARY(false, 0, false);
+            hipLaunchKernelGGL((k_intersect_batch<ANY, COUNT, INST, K == TraceKind::Spheres>), grid, block, 0, ctx->stream, s->d.bvh, io,
+                               ctx->d_work_counter, ctx->d_counters);
         }
-#undef PB_LAUNCH_BINARY
-#undef PB_LAUNCH_WIDE
-#undef PB_LAUNCH_SPECIAL
-    }
+    });
     HIP_TRY(ctx, hipGetLastError());
     if (ctx->time_trace) {
         HIP_TRY(ctx, hipEventRecord(ctx->ev1, ctx->stream));

@@ -1,7 +1,8 @@
 // render.hip — Integrator::render behind the C ABI: pbrt_hip_render / pbrt_hip_render_device
 // (SamplerIntegrator::render, src/core/integrator.rs:399-480) = wavefront_render, the host driver of the kernels in
-// wavefront.h; the per-vertex shading data of the TriangleMesh (pbrt_hip_scene_set_shading_data); the host side of the
-// HaltonSampler tables.
+// wavefront.h, in stages (parameters, pass size, buffers, sampler, light distribution, PassParams, the wavefront loop, the
+// film); which traversal and shading kernel a launch runs comes from kernel_select.h; the per-vertex shading data of the
+// TriangleMesh (pbrt_hip_scene_set_shading_data); the host side of the HaltonSampler tables.
 #include <hip/hip_runtime.h>
 #include "abi_guard.h"
 
@@ -17,6 +18,8 @@
 #include "scene.h"
 #include "trace.h"
 #include "wavefront.h"
+#define PB_SELECT_SHADING_KERNELS  // kernel_select.h: the tables over the kernels of wavefront.h as well
+#include "kernel_select.h"
 
 using namespace pb;
 
@@ -435,7 +438,32 @@ extern "C" int pbrt_hip_light_sample_li(PbrtHipScene* s, int32_t light, int64_t 
 }
 PB_ABI_CATCH
 
-static int round_up_pow2(int v);
+static int round_up_pow2(int v) {  // pbrt.rs:174-182
+    v -= 1;
+    v |= v >> 1;
+    v |= v >> 2;
+    v |= v >> 4;
+    v |= v >> 8;
+    v |= v >> 16;
+    return v + 1;
+}
+
+// The samples per pixel the sampler takes (stratified.rs:30-33: nx * ny; zerotwosequence.rs:20: the next power of two), for
+// wavefront_render and for pbrt_hip_camera_rays, whose outputs are sized by THAT count and not by the caller's spp. Returns the
+// refusal, or null.
+static const char* sampler_spp(const PbrtRenderParams& rp, int32_t* spp) {
+    *spp = rp.spp;
+    if (rp.sampler == PBRT_SAMPLER_STRATIFIED) {
+        if (rp.sampler_x < 1 || rp.sampler_y < 1 || (int64_t)rp.sampler_x * rp.sampler_y > 65536)
+            return "stratified sampler: sampler_x * sampler_y must be in [1, 65536]";
+        *spp = rp.sampler_x * rp.sampler_y;
+    } else if (rp.sampler == PBRT_SAMPLER_ZEROTWO) {
+        if (rp.spp > 65536) return "(0,2)-sequence sampler: spp too large";
+        *spp = round_up_pow2(rp.spp);
+    }
+    return nullptr;
+}
+
 extern "C" int pbrt_hip_camera_rays(PbrtHipScene* s, const PbrtCamera* camera, const PbrtRenderParams* params, int64_t capacity,
                                     PbrtRay* rays, uint64_t* stream_keys, float* p_film, int32_t* pixel_sample, int64_t* n_out) try {
     if (!s || !camera || !params || !n_out) return PBRT_HIP_ERR_INVALID;
@@ -451,21 +479,10 @@ extern "C" int pbrt_hip_camera_rays(PbrtHipScene* s, const PbrtCamera* camera, c
         ctx->last_error = "camera rays: bad tile_rank / tile_world / tile_order";
         return PBRT_HIP_ERR_INVALID;
     }
-    // the samples per pixel the sampler takes, as wavefront_render will fix them (stratified.rs:30-33: nx * ny; zerotwosequence.rs:20:
-    // the next power of two): the outputs are sized by THAT count, not by the caller's spp
-    int64_t spp = params->spp;
-    if (params->sampler == PBRT_SAMPLER_STRATIFIED) {
-        if (params->sampler_x < 1 || params->sampler_y < 1 || (int64_t)params->sampler_x * params->sampler_y > 65536) {
-            ctx->last_error = "stratified sampler: sampler_x * sampler_y must be in [1, 65536]";
-            return PBRT_HIP_ERR_INVALID;
-        }
-        spp = (int64_t)params->sampler_x * params->sampler_y;
-    } else if (params->sampler == PBRT_SAMPLER_ZEROTWO) {
-        if (params->spp > 65536) {
-            ctx->last_error = "(0,2)-sequence sampler: spp too large";
-            return PBRT_HIP_ERR_INVALID;
-        }
-        spp = round_up_pow2(params->spp);
+    int32_t spp = 0;  // as wavefront_render will fix them
+    if (const char* why = sampler_spp(*params, &spp)) {
+        ctx->last_error = why;
+        return PBRT_HIP_ERR_INVALID;
     }
     const int64_t n = (int64_t)n_tiles * kTile * kTile * spp;  // whole tiles: pixels outside the bounds carry pixel = (-1, -1)
     *n_out = n;
@@ -732,27 +749,97 @@ uint64_t multiplicative_inverse(int64_t a, int64_t n) {  // halton.rs:40-49
 }
 }  // namespace
 
-static int round_up_pow2(int v) {  // pbrt.rs:174-182
-    v -= 1;
-    v |= v >> 1;
-    v |= v >> 2;
-    v |= v >> 4;
-    v |= v >> 8;
-    v |= v >> 16;
-    return v + 1;
-}
+// ---- wavefront_render in stages: one plain struct holds the render, its member functions are the stages in order ----
+namespace {
+// the four events of a render; they go with this object on every way out
+struct RenderEvents {
+    hipEvent_t begin = nullptr, end = nullptr, t0 = nullptr, t1 = nullptr;
+    bool create(PbrtHipContext* ctx) {
+        return hip_ok(ctx, hipEventCreate(&begin), "hipEventCreate") && hip_ok(ctx, hipEventCreate(&end), "hipEventCreate") &&
+               hip_ok(ctx, hipEventCreate(&t0), "hipEventCreate") && hip_ok(ctx, hipEventCreate(&t1), "hipEventCreate");
+    }
+    ~RenderEvents() {
+        for (hipEvent_t e : {begin, end, t0, t1})
+            if (e) (void)hipEventDestroy(e);
+    }
+};
 
-int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRenderParams& rp_in, float* d_film,
-                     PbrtRenderStats* stats, const LiBatch* li) {
-    const bool li_mode = li && li->d_rays, export_mode = li && li->out_rays;
-    PbrtHipContext* ctx = s->ctx;
-    auto invalid = [&](const char* m) {
+// a rocPRIM pair sort's buffers (keys in / out, the sorted values, scratch)
+struct SortBufs {
+    uint32_t *keys[2] = {nullptr, nullptr}, *vals = nullptr;
+    void* tmp = nullptr;
+    size_t tmp_bytes = 0;
+};
+
+constexpr int kSortFrom = 2;  // first sorted wavefront: the first bounce still follows the pixel order of its camera rays
+
+// One render: what it holds between its stages, and the stages in the order run() goes through them. The device blocks belong to
+// the DevBuf of run()'s own frame.
+struct RenderJob {
+    PbrtHipScene* s;
+    PbrtHipContext* ctx;
+    hipStream_t st;
+    const LiBatch* li;
+    float* d_film;
+    // stage 1, the caller's parameters checked and normalised
+    PbrtRenderParams rp;  // li substitution, the sampler's samples per pixel, AO's round_count, an export's single pass
+    bool li_mode, export_mode;
+    bool tabulated;  // not the RandomSampler
+    bool direct;     // DirectLighting, Whitted and AO share the per-vertex stage machine of k_shade_direct
+    bool box;        // the 0.5 box filter: exact in-order accumulation (k_film_accumulate)
+    float frx, fry;
+    int32_t sb[4];  // pbrt_hip_sample_bounds of the film under the filter
+    int world, rank;
+    // stages 2 - 6
+    int n_pix = 0, spp_pass = 0;
+    int64_t valid_pixels = 0;
+    size_t N = 0;  // concurrent paths of a pass
+    PathState ps;
+    Queues q[2];
+    bool sort_rays = false, sort_shade = false, bin_shade = false;
+    SortBufs ray_sort;    // Morton order of the bounce rays
+    SortBufs shade_sort;  // shade_order 2: keys, the sorted queue positions (vals)
+    uint32_t* shade_positions = nullptr;
+    TraceChoice trace;                 // kernel_select.h
+    uint32_t* special_list = nullptr;  // rays the wide kernel leaves to the binary one (wide_bvh.h)
+    std::vector<int> prefix;           // light-sample prefix sums
+    SamplerParams smp{};
+    DirectState ds{};
+    float* d_filter = nullptr;
+    float4* accum = nullptr;
+    TileList tiles{};
+    DevCamera cam;
+    ShadeConsts sc;
+    DirectKernel shade_direct = nullptr;            // the shading kernels of this scene and integrator, looked up once
+    PathKernel shade_path[2] = {nullptr, nullptr};  // [BIN]
+    PbrtRenderStats local{};
+
+    int invalid(const char* m) const {
         ctx->last_error = m;
         return PBRT_HIP_ERR_INVALID;
-    };
-    PbrtRenderParams rp = rp_in;
+    }
+    int round_count(int n) const { return rp.sampler == PBRT_SAMPLER_ZEROTWO ? round_up_pow2(n) : n; }  // Sampler::round_count
+    const char* normalise_params(const PbrtRenderParams& rp_in);
+    int size_pass();
+    int alloc_path_buffers(DevBuf& buf, bool* ok);
+    int setup_sampler(DevBuf& buf, bool* ok);
+    int setup_light_distribution(const SceneNeeds& needs);
+    PassParams pass_params(int s0) const;
+    void wait_for_counts(int& rc);
+    void trace_wavefront(const RenderEvents& ev, const Queues& qcur, uint32_t n_trace, int wavefront, int& rc);
+    void shade_wavefront(const PassParams& pp, int cur, int nxt, uint32_t n_shade, int wavefront, int& rc);
+    void run_wavefronts(const RenderEvents& ev, const PassParams& pp, uint32_t n_paths, int& rc);
+    void film_stage(const PassParams& pp, uint32_t n_paths, bool last_pass, int& rc);
+    int run(const PbrtCamera& camera, PbrtRenderStats* stats);
+};
+
+// stage 1: returns the first refusal, or null
+const char* RenderJob::normalise_params(const PbrtRenderParams& rp_in) {
+    rp = rp_in;
+    li_mode = li && li->d_rays;
+    export_mode = li && li->out_rays;
     if (li_mode) {  // the batch stands in for a 1-spp "frame" of n pixels in a row; nothing of the film plumbing is used
-        if (li->n <= 0 || li->n > (1ll << 28)) return invalid("li: batch size must be in [1, 2^28]");
+        if (li->n <= 0 || li->n > (1ll << 28)) return "li: batch size must be in [1, 2^28]";
         rp.width = (int32_t)li->n;
         rp.height = 1;
         rp.spp = 1;
@@ -765,25 +852,17 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
         rp.sampler = PBRT_SAMPLER_RANDOM;  // the caller's Sampler is a RandomSampler stream per ray (sampler.rs:452, random.rs)
         rp.filter_table = nullptr;
     }
-    if (rp.width <= 0 || rp.height <= 0 || rp.spp <= 0) return invalid("width, height and spp must be positive");
+    if (rp.width <= 0 || rp.height <= 0 || rp.spp <= 0) return "width, height and spp must be positive";
     // ---- sampler: samples per pixel and Sampler::round_count (stratified.rs:30-33, zerotwosequence.rs:20, 62-64) ----
-    if (rp.sampler < PBRT_SAMPLER_RANDOM || rp.sampler > PBRT_SAMPLER_HALTON) return invalid("unknown sampler");
-    const bool tabulated = rp.sampler != PBRT_SAMPLER_RANDOM;
-    if (tabulated && (rp.sampler_dims < 0 || rp.sampler_dims > 63)) return invalid("sampler_dims must be in [0, 63]");
-    if (rp.sampler == PBRT_SAMPLER_STRATIFIED) {
-        if (rp.sampler_x < 1 || rp.sampler_y < 1 || (int64_t)rp.sampler_x * rp.sampler_y > 65536)
-            return invalid("stratified sampler: sampler_x * sampler_y must be in [1, 65536]");
-        rp.spp = rp.sampler_x * rp.sampler_y;
-    } else if (rp.sampler == PBRT_SAMPLER_ZEROTWO) {
-        if (rp.spp > 65536) return invalid("(0,2)-sequence sampler: spp too large");
-        rp.spp = round_up_pow2(rp.spp);
-    }
-    auto round_count = [&](int n) { return rp.sampler == PBRT_SAMPLER_ZEROTWO ? round_up_pow2(n) : n; };
+    if (rp.sampler < PBRT_SAMPLER_RANDOM || rp.sampler > PBRT_SAMPLER_HALTON) return "unknown sampler";
+    tabulated = rp.sampler != PBRT_SAMPLER_RANDOM;
+    if (tabulated && (rp.sampler_dims < 0 || rp.sampler_dims > 63)) return "sampler_dims must be in [0, 63]";
+    if (const char* why = sampler_spp(rp, &rp.spp)) return why;
     if (rp.integrator == PBRT_INTEGRATOR_AO && rp.ao_samples >= 1 && rp.ao_samples <= 65535 && tabulated)
         rp.ao_samples = round_count(rp.ao_samples);  // ao.rs:36
-    float frx = rp.filter_radius[0] > 0.0f ? rp.filter_radius[0] : 0.5f;
-    float fry = rp.filter_radius[1] > 0.0f ? rp.filter_radius[1] : 0.5f;
-    bool box = true;  // the 0.5 box filter: exact in-order accumulation (k_film_accumulate)
+    frx = rp.filter_radius[0] > 0.0f ? rp.filter_radius[0] : 0.5f;
+    fry = rp.filter_radius[1] > 0.0f ? rp.filter_radius[1] : 0.5f;
+    box = true;
     if (rp.filter_table) {
         if (frx != 0.5f || fry != 0.5f) box = false;
         for (int i = 0; i < 256; ++i)
@@ -791,57 +870,29 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
     } else {
         frx = fry = 0.5f;
     }
-    if (frx > 64.0f || fry > 64.0f) return invalid("filter radius too large");
-    {
-        int32_t sb[4];
-        pbrt_hip_sample_bounds(rp.width, rp.height, frx, fry, sb);
-        if (rp.x0 < sb[0] || rp.y0 < sb[1] || rp.x1 > sb[2] || rp.y1 > sb[3] || rp.x0 > rp.x1 || rp.y0 > rp.y1)
-            return invalid("pixel bounds outside the film's sample bounds");
-    }
-    if (rp.integrator < PBRT_INTEGRATOR_PATH || rp.integrator > PBRT_INTEGRATOR_AO)
-        return invalid("integrator must be a PbrtIntegratorKind");
-    // DirectLighting, Whitted and AO share the per-vertex stage machine of k_shade_direct
-    const bool direct = rp.integrator != PBRT_INTEGRATOR_PATH;
-    if (direct && rp.max_depth > 64) return invalid("direct lighting / Whitted: max_depth > 64 (frame stack)");
+    if (frx > 64.0f || fry > 64.0f) return "filter radius too large";
+    pbrt_hip_sample_bounds(rp.width, rp.height, frx, fry, sb);
+    if (rp.x0 < sb[0] || rp.y0 < sb[1] || rp.x1 > sb[2] || rp.y1 > sb[3] || rp.x0 > rp.x1 || rp.y0 > rp.y1)
+        return "pixel bounds outside the film's sample bounds";
+    if (rp.integrator < PBRT_INTEGRATOR_PATH || rp.integrator > PBRT_INTEGRATOR_AO) return "integrator must be a PbrtIntegratorKind";
+    direct = rp.integrator != PBRT_INTEGRATOR_PATH;
+    if (direct && rp.max_depth > 64) return "direct lighting / Whitted: max_depth > 64 (frame stack)";
     if (rp.integrator == PBRT_INTEGRATOR_AO && (rp.ao_samples < 1 || rp.ao_samples > 65535))
-        return invalid("ambient occlusion: ao_samples must be in [1, 65535]");
-    if (rp.max_depth < 0 || rp.max_depth > 1 << 20) return invalid("bad max_depth");
-    int world = rp.tile_world <= 0 ? 1 : rp.tile_world;
-    int rank = rp.tile_rank;
-    if (rank < 0 || rank >= world) return invalid("tile_rank outside [0, tile_world)");
-    if (rp.tile_order != PBRT_TILE_ORDER_MORTON && rp.tile_order != PBRT_TILE_ORDER_ROW_MAJOR)
-        return invalid("tile_order must be a PbrtTileOrder");
+        return "ambient occlusion: ao_samples must be in [1, 65535]";
+    if (rp.max_depth < 0 || rp.max_depth > 1 << 20) return "bad max_depth";
+    world = rp.tile_world <= 0 ? 1 : rp.tile_world;
+    rank = rp.tile_rank;
+    if (rank < 0 || rank >= world) return "tile_rank outside [0, tile_world)";
+    if (rp.tile_order != PBRT_TILE_ORDER_MORTON && rp.tile_order != PBRT_TILE_ORDER_ROW_MAJOR) return "tile_order must be a PbrtTileOrder";
     if (rp.samples_per_wave < 0 || rp.samples_per_wave > 64 || (rp.samples_per_wave & (rp.samples_per_wave - 1)) != 0)
-        return invalid("samples_per_wave must be 0 (library default) or a power of two up to 64");
-    hipStream_t st = ctx->stream;
-
-    size_t film_bytes = (size_t)rp.width * rp.height * 4 * sizeof(float);
-    if (d_film) HIP_TRY(ctx, hipMemsetAsync(d_film, 0, film_bytes, st));
-
-    // tiles of the sample bounds (integrator.rs:402-409), dealt round-robin in rp.tile_order to the GPUs
-    std::vector<int2> origins;
-    if (li_mode) {
-        origins.assign((size_t)((li->n + kTile * kTile - 1) / (kTile * kTile)), make_int2(0, 0));  // 256 rays per "tile"
-    } else {
-        int32_t n_mine = 0;
-        if (pbrt_hip_tile_partition_order(rp.x0, rp.y0, rp.x1, rp.y1, rank, world, rp.tile_order, nullptr, 0, &n_mine) != PBRT_HIP_OK)
-            return invalid("tile partition: too many tiles");
-        origins.resize(n_mine);
-        pbrt_hip_tile_partition_order(rp.x0, rp.y0, rp.x1, rp.y1, rank, world, rp.tile_order, (int32_t*)origins.data(), n_mine, &n_mine);
-    }
-    PbrtRenderStats local{};
-    if (origins.empty()) {
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (stats) *stats = local;
-        return PBRT_HIP_OK;
-    }
-    const int n_pix = (int)origins.size() * kTile * kTile;
-    int64_t valid_pixels = 0;
-    for (const int2& o : origins)
-        valid_pixels += (int64_t)(std::min(o.x + kTile, rp.x1) - o.x) * (std::min(o.y + kTile, rp.y1) - o.y);
-    if (li_mode) valid_pixels = li->n;
+        return "samples_per_wave must be 0 (library default) or a power of two up to 64";
     if (export_mode) rp.spp_per_pass = rp.spp;  // one pass: the export is indexed by the paths of that pass
-    int spp_pass = rp.spp_per_pass > 0 ? rp.spp_per_pass : 0;
+    return nullptr;
+}
+
+// stage 2: the samples of a pixel one pass holds
+int RenderJob::size_pass() {
+    spp_pass = rp.spp_per_pass > 0 ? rp.spp_per_pass : 0;
     if (spp_pass == 0) {
         // As many samples of a pixel in flight as two thirds of the free HBM hold (the other integrators: half of it, as
         // ever). The path integrator takes 524 B per path:
@@ -861,41 +912,39 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
         spp_pass = (int)std::max<int64_t>(1, std::min<int64_t>(rp.spp, target_paths / n_pix));
     }
     spp_pass = std::min(spp_pass, rp.spp);
-    if (export_mode && spp_pass != rp.spp) return invalid("camera rays: too many samples for one pass");
-    const size_t N = (size_t)n_pix * spp_pass;
-    if (N * 4 >= (1ull << 32)) return invalid("too many concurrent paths for 32-bit queue entries; lower spp_per_pass");
+    return PBRT_HIP_OK;
+}
 
-    DevBuf buf(ctx);
-    bool ok = true;
-    PathState ps;
+// stage 3: path state, queues, sort buffers (allocation failures land in *ok; a refusal is returned)
+int RenderJob::alloc_path_buffers(DevBuf& buf, bool* ok) {
     ps.n_paths = N;
     ps.two_level = s->d.bvh.instanced ? 1 : 0;
-    ps.ray = buf.alloc<float4>(N * 6, &ok);
-    ps.hit = buf.alloc<float4>(N * 6, &ok);
-    ps.rng = buf.alloc<uint64_t>(N, &ok);
-    ps.L = buf.alloc<float4>(N, &ok);
-    ps.beta = buf.alloc<float4>(N, &ok);
-    ps.nee_a = buf.alloc<float4>(N, &ok);
-    ps.nee_f = buf.alloc<float4>(N, &ok);
-    ps.nee_b = buf.alloc<float4>(N, &ok);
-    ps.nee_light = buf.alloc<int>(N, &ok);
-    ps.pfilm = buf.alloc<float2>(N, &ok);
+    ps.ray = buf.alloc<float4>(N * 6, ok);
+    ps.hit = buf.alloc<float4>(N * 6, ok);
+    ps.rng = buf.alloc<uint64_t>(N, ok);
+    ps.L = buf.alloc<float4>(N, ok);
+    ps.beta = buf.alloc<float4>(N, ok);
+    ps.nee_a = buf.alloc<float4>(N, ok);
+    ps.nee_f = buf.alloc<float4>(N, ok);
+    ps.nee_b = buf.alloc<float4>(N, ok);
+    ps.nee_light = buf.alloc<int>(N, ok);
+    ps.pfilm = buf.alloc<float2>(N, ok);
     // the path integrator keeps two generations of the rays and the pending estimates (wf_state.h); the others one
-    ps.ray_next = direct ? ps.ray : buf.alloc<float4>(N * 6, &ok);
-    ps.nee_a_next = direct ? ps.nee_a : buf.alloc<float4>(N, &ok);
-    ps.nee_f_next = direct ? ps.nee_f : buf.alloc<float4>(N, &ok);
-    ps.nee_b_next = direct ? ps.nee_b : buf.alloc<float4>(N, &ok);
-    ps.nee_light_next = direct ? ps.nee_light : buf.alloc<int>(N, &ok);
-    Queues q[2];
+    ps.ray_next = direct ? ps.ray : buf.alloc<float4>(N * 6, ok);
+    ps.nee_a_next = direct ? ps.nee_a : buf.alloc<float4>(N, ok);
+    ps.nee_f_next = direct ? ps.nee_f : buf.alloc<float4>(N, ok);
+    ps.nee_b_next = direct ? ps.nee_b : buf.alloc<float4>(N, ok);
+    ps.nee_light_next = direct ? ps.nee_light : buf.alloc<int>(N, ok);
     for (int k = 0; k < 2; ++k) {
-        q[k].trace = buf.alloc<uint32_t>(N * 3, &ok);
-        q[k].shade = buf.alloc<uint32_t>(N, &ok);
-        q[k].counts64 = buf.alloc<unsigned long long>(2, &ok);
-        q[k].keys = nullptr;
+        Queues& qk = q[k];
+        qk.trace = buf.alloc<uint32_t>(N * 3, ok);
+        qk.shade = buf.alloc<uint32_t>(N, ok);
+        qk.counts64 = buf.alloc<unsigned long long>(2, ok);
+        qk.keys = nullptr;
         for (int a = 0; a < 3; ++a) {
             const float lo = s->d.bvh.root_min[a], hi = s->d.bvh.root_max[a];
-            q[k].key_lo[a] = lo;
-            q[k].key_inv[a] = hi > lo ? 1.0f / (hi - lo) : 0.0f;
+            qk.key_lo[a] = lo;
+            qk.key_inv[a] = hi > lo ? 1.0f / (hi - lo) : 0.0f;
         }
     }
     // ray-queue sort (spatial order for the bounce rays): keys in / out, sorted entries, rocPRIM scratch
@@ -903,52 +952,49 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
     // shooting from the camera rays' hit points, which are already in pixel order (AO: -6 % with the sort).
     // PbrtRenderParams.ray_order = 1 leaves the queues as the shading kernel filled them (results do not depend on it).
     if (rp.ray_order < 0 || rp.ray_order > 1) return invalid("ray_order must be 0 (Morton order from the second bounce on) or 1 (queue order)");
-    const bool sort_rays = rp.ray_order == 0 && rp.integrator == PBRT_INTEGRATOR_PATH;
-    constexpr int sort_from = 2;  // first sorted wavefront: the first bounce still follows the pixel order of its camera rays
-    uint32_t *sort_keys[2] = {nullptr, nullptr}, *sort_vals = nullptr;
-    void* sort_tmp = nullptr;
-    size_t sort_tmp_bytes = 0;
+    sort_rays = rp.ray_order == 0 && rp.integrator == PBRT_INTEGRATOR_PATH;
     if (sort_rays) {
-        sort_keys[0] = buf.alloc<uint32_t>(N * 3, &ok);
-        sort_keys[1] = buf.alloc<uint32_t>(N * 3, &ok);
-        sort_vals = buf.alloc<uint32_t>(N * 3, &ok);
-        if (pb::sort_pairs_u32(st, nullptr, &sort_tmp_bytes, sort_keys[0], sort_keys[1], sort_vals, sort_vals, N * 3, kSortKeyBits) != 0)
+        SortBufs& rs = ray_sort;
+        rs.keys[0] = buf.alloc<uint32_t>(N * 3, ok);
+        rs.keys[1] = buf.alloc<uint32_t>(N * 3, ok);
+        rs.vals = buf.alloc<uint32_t>(N * 3, ok);
+        if (pb::sort_pairs_u32(st, nullptr, &rs.tmp_bytes, rs.keys[0], rs.keys[1], rs.vals, rs.vals, N * 3, kSortKeyBits) != 0)
             return invalid("rocPRIM radix sort: size query failed");
-        sort_tmp = buf.alloc<char>(sort_tmp_bytes, &ok);
+        rs.tmp = buf.alloc<char>(rs.tmp_bytes, ok);
     }
+    trace = choose_trace(s);
+    if (!trace.ok) return PBRT_HIP_ERR_INVALID;
     // rays the wide kernel leaves to the binary one (wide_bvh.h): room for every entry of a trace queue
-    const bool use_wide = s->has_wide && ctx->count_traversal != 1 && ctx->traversal == PBRT_TRAVERSAL_AUTO;
-    const bool stackless = ctx->traversal == PBRT_TRAVERSAL_STACKLESS;
-    if (stackless && !stackless_applies(s)) return PBRT_HIP_ERR_INVALID;
-    uint32_t* special_list = use_wide ? buf.alloc<uint32_t>(N * 3, &ok) : nullptr;
+    special_list = trace.kind == TraceKind::Wide ? buf.alloc<uint32_t>(N * 3, ok) : nullptr;
     // sort-by-material shading (wf_path.h): PbrtRenderParams.shade_order; 2 = the whole shade queue in material order
     if (rp.shade_order < 0 || rp.shade_order > 2) return invalid("shade_order must be 0 (queue order), 1 (by material inside blocks) or 2 (sorted queue)");
-    const bool sort_shade = rp.shade_order == 2 && rp.integrator == PBRT_INTEGRATOR_PATH;
-    const bool bin_shade = rp.shade_order == 1 && rp.integrator == PBRT_INTEGRATOR_PATH;
-    uint32_t *shade_keys[2] = {nullptr, nullptr}, *shade_positions = nullptr, *shade_sorted = nullptr;
-    void* shade_tmp = nullptr;
-    size_t shade_tmp_bytes = 0;
+    sort_shade = rp.shade_order == 2 && rp.integrator == PBRT_INTEGRATOR_PATH;
+    bin_shade = rp.shade_order == 1 && rp.integrator == PBRT_INTEGRATOR_PATH;
     if (sort_shade) {
-        shade_keys[0] = buf.alloc<uint32_t>(N, &ok);
-        shade_keys[1] = buf.alloc<uint32_t>(N, &ok);
-        shade_positions = buf.alloc<uint32_t>(N, &ok);
-        shade_sorted = buf.alloc<uint32_t>(N, &ok);
-        if (pb::sort_pairs_u32(st, nullptr, &shade_tmp_bytes, shade_keys[0], shade_keys[1], shade_positions, shade_sorted, N, 3) != 0)
+        SortBufs& ss = shade_sort;
+        ss.keys[0] = buf.alloc<uint32_t>(N, ok);
+        ss.keys[1] = buf.alloc<uint32_t>(N, ok);
+        shade_positions = buf.alloc<uint32_t>(N, ok);
+        ss.vals = buf.alloc<uint32_t>(N, ok);
+        if (pb::sort_pairs_u32(st, nullptr, &ss.tmp_bytes, ss.keys[0], ss.keys[1], shade_positions, ss.vals, N, 3) != 0)
             return invalid("rocPRIM radix sort: size query failed");
-        shade_tmp = buf.alloc<char>(shade_tmp_bytes, &ok);
+        ss.tmp = buf.alloc<char>(ss.tmp_bytes, ok);
     }
-    DirectState ds{};
-    std::vector<int> prefix(s->d.n_lights + 1, 0);
+    return PBRT_HIP_OK;
+}
+
+// stage 4: SamplerParams of the render: the Halton tables and constants, the requested 2D arrays, the table sizes
+int RenderJob::setup_sampler(DevBuf& buf, bool* ok) {
+    prefix.assign(s->d.n_lights + 1, 0);
     for (int i = 0; i < s->d.n_lights; ++i)  // directlighting.rs:58-62: round_count with a tabulating sampler
         prefix[i + 1] = prefix[i] + (tabulated ? round_count(s->light_samples[i]) : s->light_samples[i]);
     // ---- PixelSampler tables: n_dims 1D + n_dims 2D dimensions and the requested 2D arrays, per pixel ----
-    SamplerParams smp{};
     smp.kind = rp.sampler;
     smp.n_dims = rp.sampler_dims;
     smp.nx = rp.sampler_x;
     smp.ny = rp.sampler_y;
     smp.jitter = rp.sampler_jitter;
-    ps.samp = buf.alloc<int>(N, &ok);
+    ps.samp = buf.alloc<int>(N, ok);
     if (rp.sampler == PBRT_SAMPLER_HALTON) {
         smp.n_dims = 0;  // nothing is tabulated per pixel: every value is a function of (sample index, dimension)
         if (!ctx->d_halton_primes) {
@@ -963,8 +1009,6 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
         smp.primes = ctx->d_halton_primes;
         smp.perms = ctx->d_halton_perms;
         // HaltonSampler::new(spp, film.get_sample_bounds(), false) (halton.rs:63-98)
-        int32_t sb[4];
-        pbrt_hip_sample_bounds(rp.width, rp.height, frx, fry, sb);
         const int res[2] = {sb[2] - sb[0], sb[3] - sb[1]};
         for (int i = 0; i < 2; ++i) {
             int base = i == 0 ? 2 : 3, scale = 1, exp = 0;
@@ -989,9 +1033,9 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
         };
         if (rp.integrator == PBRT_INTEGRATOR_DIRECT && rp.light_strategy == 0) {
             for (int i = 0; i < rp.max_depth; ++i)  // directlighting.rs:64-75
-                for (int j = 0; j < s->d.n_lights; ++j) {
-                    request_2d_array(prefix[j + 1] - prefix[j]);
-                    request_2d_array(prefix[j + 1] - prefix[j]);
+                for (int k = 0; k < s->d.n_lights; ++k) {
+                    request_2d_array(prefix[k + 1] - prefix[k]);
+                    request_2d_array(prefix[k + 1] - prefix[k]);
                 }
         } else if (rp.integrator == PBRT_INTEGRATOR_AO) {
             request_2d_array(rp.ao_samples);  // ao.rs:37
@@ -1008,13 +1052,284 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
             elems = 0;
         }
         smp.n_elems = (int)elems;
-        smp.tables = buf.alloc<float>((size_t)elems * n_pix, &ok);
-        int2* d_arrays = buf.alloc<int2>(arrays.size(), &ok);
+        smp.tables = buf.alloc<float>((size_t)elems * n_pix, ok);
+        int2* d_arrays = buf.alloc<int2>(arrays.size(), ok);
         smp.arrays = d_arrays;
-        if (ok && !arrays.empty())
+        if (*ok && !arrays.empty())
             HIP_TRY(ctx, hipMemcpyAsync(d_arrays, arrays.data(), arrays.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-        if (ok) HIP_TRY(ctx, hipStreamSynchronize(st));  // `arrays` leaves scope
+        if (*ok) HIP_TRY(ctx, hipStreamSynchronize(st));  // `arrays` leaves scope
     }
+    return PBRT_HIP_OK;
+}
+
+// stage 5: the light distribution of the render in sc (create_light_sample_distribution, lightdistrib.rs:222-232), with the
+// scene's spatial table built on first use
+int RenderJob::setup_light_distribution(const SceneNeeds& needs) {
+    // "uniform", or one light -> uniform
+    sc.distrib = (rp.light_strategy == 0 || s->d.n_lights == 1) ? s->d.light_distrib_uniform : s->d.light_distrib_power;
+    if (rp.integrator == PBRT_INTEGRATOR_PATH && (rp.light_strategy < 0 || rp.light_strategy > 2))
+        return invalid("path: light_strategy must be 0 (uniform), 1 (power) or 2 (spatial)");
+    if (rp.integrator == PBRT_INTEGRATOR_PATH && rp.light_strategy == 2 && s->d.n_lights > 1) {
+        // create_light_sample_distribution("spatial") -> SpatialLightDistribution::new(scene, 64) (lightdistrib.rs:85-107, 228)
+        if (!s->d_spatial) {
+            const float *mn = s->d.bvh.root_min, *mx = s->d.bvh.root_max;
+            float diag[3] = {mx[0] - mn[0], mx[1] - mn[1], mx[2] - mn[2]};
+            int ext = (diag[0] > diag[1] && diag[0] > diag[2]) ? 0 : (diag[1] > diag[2] ? 1 : 2);
+            for (int i = 0; i < 3; ++i) s->spatial_voxels[i] = std::max(1, (int)std::round(diag[i] / diag[ext] * 64.0f));
+            size_t n_voxels = (size_t)s->spatial_voxels[0] * s->spatial_voxels[1] * s->spatial_voxels[2];
+            size_t floats = n_voxels * (size_t)(2 * s->d.n_lights + 2);
+            if (floats > (1ull << 30)) return invalid("spatial light distribution: voxels x lights exceed 4 GB; use \"power\"");
+            void* p = nullptr;
+            HIP_TRY(ctx, hipMalloc(&p, floats * sizeof(float)));
+            s->allocs.push_back(p);
+            for (int i = 0; i < 3; ++i) sc.n_voxel[i] = s->spatial_voxels[i];
+            hipLaunchKernelGGL(spatial_tables_kernel(needs), dim3((unsigned)((n_voxels + 63) / 64)), dim3(64), 0, st, sc, (float*)p);
+            HIP_TRY(ctx, hipGetLastError());
+            HIP_TRY(ctx, hipStreamSynchronize(st));
+            s->d_spatial = (float*)p;
+        }
+        sc.spatial = s->d_spatial;
+        for (int i = 0; i < 3; ++i) sc.n_voxel[i] = s->spatial_voxels[i];
+    }
+    return PBRT_HIP_OK;
+}
+
+// stage 6: the PassParams of the pass that starts at sample s0
+PassParams RenderJob::pass_params(int s0) const {
+    PassParams pp;
+    pp.smp = smp;
+    pp.n_pix = n_pix;
+    pp.n_samples = std::min(spp_pass, rp.spp - s0);
+    // PbrtRenderParams.samples_per_wave: the largest power of two <= the request that divides the pass's samples per pixel
+    // default: a wave = the samples of ONE pixel (as many as the pass has, up to 64). The tabulating samplers keep the
+    // old layout: their tables are [element][pixel], read coalesced when a wave's lanes are 64 pixels of one sample
+    const int want = rp.samples_per_wave > 0 ? rp.samples_per_wave : ((tabulated && rp.sampler != PBRT_SAMPLER_HALTON) ? 1 : 64);
+    pp.group_shift = 0;
+    while ((2 << pp.group_shift) <= want && pp.group_shift < 6 && pp.n_samples % (2 << pp.group_shift) == 0) ++pp.group_shift;
+    if (li_mode || export_mode) pp.group_shift = 0;  // batches of rays / the exported camera rays keep the caller's order
+    pp.sample0 = s0;
+    pp.spp = rp.spp;
+    pp.width = rp.width;
+    pp.height = rp.height;
+    pp.x0 = rp.x0;
+    pp.y0 = rp.y0;
+    pp.x1 = rp.x1;
+    pp.y1 = rp.y1;
+    pp.sb_x0 = sb[0];
+    pp.sb_y0 = sb[1];
+    pp.sb_w = sb[2] - sb[0];
+    pp.seed = rp.seed;
+    pp.max_depth = rp.max_depth;
+    pp.rr_threshold = rp.rr_threshold;
+    pp.light_strategy = rp.light_strategy;
+    pp.filter_rx = frx;
+    pp.filter_ry = fry;
+    pp.filter_table = d_filter;
+    pp.max_sample_luminance = rp.max_sample_luminance > 0.0f ? rp.max_sample_luminance : INFINITY;
+    pp.stream_keys = li_mode ? li->d_keys : nullptr;
+    return pp;
+}
+
+#define RENDER_TRY(call) \
+    if (rc == PBRT_HIP_OK && !hip_ok(ctx, (call), #call)) rc = PBRT_HIP_ERR_DEVICE;
+
+// stage 7: waits for the counts copy of a wavefront (ctx->ev_sync, recorded behind it)
+void RenderJob::wait_for_counts(int& rc) {
+    // spin on the event (a blocking sync costs a scheduler wake-up per wavefront), but not for ever: a kernel
+    // that never finishes must surface as an error of this call, with the context's lock released
+    hipError_t qe;
+    const auto spin_start = std::chrono::steady_clock::now();
+    uint32_t polls = 0;
+    while ((qe = hipEventQuery(ctx->ev_sync)) == hipErrorNotReady) {
+        if ((++polls & 0xfffu) == 0) {
+            const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - spin_start).count();
+            if (waited > ctx->wavefront_deadline_s) {
+                ctx->last_error = "a wavefront did not finish within the deadline (hung kernel?)";
+                ctx->lost = true;  // the stream is not drained afterwards: nothing may follow on this context
+                rc = PBRT_HIP_ERR_DEVICE;
+                break;
+            }
+            if (waited > 0.05) std::this_thread::yield();  // long wavefronts: stop burning a core
+        }
+    }
+    if (rc == PBRT_HIP_OK) RENDER_TRY(qe);
+}
+
+// one wavefront's rays: the queue (sorted from the second bounce on when there are enough), then the traversal kernel
+void RenderJob::trace_wavefront(const RenderEvents& ev, const Queues& qcur, uint32_t n_trace, int wavefront, int& rc) {
+    RENDER_TRY(hipMemsetAsync(ctx->d_work_counter, 0, kWorkCounters * sizeof(unsigned int), st));
+    const uint32_t* trace_queue = qcur.trace;
+    if (sort_rays && wavefront >= kSortFrom && n_trace >= (1u << 20)) {
+        // from the second bounce on the rays of a wavefront start all over the scene (the first bounce still
+        // follows the pixel order of its camera rays): trace them in Morton order of their origins (the keys were
+        // written by k_shade together with the queue entries)
+        const SortBufs& rs = ray_sort;
+        size_t tb = rs.tmp_bytes;
+        if (pb::sort_pairs_u32(st, rs.tmp, &tb, rs.keys[0], rs.keys[1], qcur.trace, rs.vals, n_trace, kSortKeyBits) != 0 && rc == PBRT_HIP_OK) {
+            ctx->last_error = "rocPRIM radix sort failed";
+            rc = PBRT_HIP_ERR_DEVICE;
+        }
+        trace_queue = rs.vals;
+    }
+    RENDER_TRY(hipEventRecord(ev.t0, st));
+    const int segments = (wavefront == 0 && !trace.inst) ? kQueueSegments : 1;  // see trace.h
+    dispatch(trace, [&](auto kind, auto count, auto inst) {
+        constexpr TraceKind K = decltype(kind)::value;
+        constexpr bool COUNT = decltype(count)::value;
+        constexpr int INST = decltype(inst)::value;
+        const dim3 grid(persistent_grid(s)), block(kTraceBlock);
+        if constexpr (K == TraceKind::Stackless) {
+            hipLaunchKernelGGL(k_trace_stackless, dim3(stackless_grid(s)), block, 0, st, s->d.bvh, ps, trace_queue, n_trace, ctx->d_work_counter,
+                               segments);
+        } else if constexpr (K == TraceKind::Wide) {  // the wide kernel, then the follow-up over the rays it left out
+            WideTrees wt = s->wide;
+            wt.special_list = special_list;
+            wt.special_count = ctx->d_work_counter + kSpecialCount;
+            hipLaunchKernelGGL((k_trace_wide<COUNT, INST>), dim3(wide_grid<COUNT, INST>(s)), block, 0, st, wt, ps, trace_queue, n_trace,
+                               ctx->d_work_counter, segments, ctx->d_counters);
+            hipLaunchKernelGGL(k_trace_special<INST>, grid, block, 0, st, s->d.bvh, ps, trace_queue, n_trace, special_list,
+                               ctx->d_work_counter + kSpecialCount, ctx->d_work_counter + kFollowUpCounter);
+        } else if constexpr (K == TraceKind::Shapes) {
+            hipLaunchKernelGGL(k_trace_shapes<COUNT>, grid, block, 0, st, s->d.bvh, ps, trace_queue, n_trace, ctx->d_work_counter, ctx->d_counters,
+                               segments);
+        } else {
+            hipLaunchKernelGGL((k_trace<COUNT, INST, K == TraceKind::Spheres>), grid, block, 0, st, s->d.bvh, ps, trace_queue, n_trace,
+                               ctx->d_work_counter, ctx->d_counters, segments);
+        }
+    });
+    RENDER_TRY(hipGetLastError());
+    RENDER_TRY(hipEventRecord(ev.t1, st));
+}
+
+// one wavefront's shading: k_shade_direct, or (sorted by material first, shade_order 2) the path kernel and the generation swap
+void RenderJob::shade_wavefront(const PassParams& pp, int cur, int nxt, uint32_t n_shade, int wavefront, int& rc) {
+    const dim3 grid((n_shade + 255) / 256), block(256);
+    if (direct) {
+        hipLaunchKernelGGL(shade_direct, grid, block, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
+        return;
+    }
+    const Queues qin = q[cur];
+    const uint32_t* order = nullptr;  // shade_order 2: the queue positions in material order
+    if (sort_shade && wavefront >= 1 && n_shade >= (1u << 10)) {  // the first wavefront is all camera hits in pixel order
+        const SortBufs& ss = shade_sort;
+        hipLaunchKernelGGL(k_shade_sort_keys, dim3((n_shade + 255) / 256), dim3(256), 0, st, sc, ps, q[cur].shade, n_shade, pp.max_depth,
+                           ss.keys[0], shade_positions);
+        size_t tb = ss.tmp_bytes;
+        if (pb::sort_pairs_u32(st, ss.tmp, &tb, ss.keys[0], ss.keys[1], shade_positions, ss.vals, n_shade, (s->bxdfs || s->disney) ? 4 : 3) != 0 &&
+            rc == PBRT_HIP_OK) {
+            ctx->last_error = "rocPRIM radix sort failed";
+            rc = PBRT_HIP_ERR_DEVICE;
+        }
+        order = ss.vals;
+    }
+    hipLaunchKernelGGL(shade_path[bin_shade && wavefront >= 1], grid, block, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
+    // what this launch wrote is the generation the next trace and shade launches read
+    std::swap(ps.ray, ps.ray_next);
+    std::swap(ps.nee_a, ps.nee_a_next);
+    std::swap(ps.nee_f, ps.nee_f_next);
+    std::swap(ps.nee_b, ps.nee_b_next);
+    std::swap(ps.nee_light, ps.nee_light_next);
+}
+
+// stage 8a: the wavefront loop of one pass, from the generated camera rays until no path is left
+void RenderJob::run_wavefronts(const RenderEvents& ev, const PassParams& pp, uint32_t n_paths, int& rc) {
+    // the first wavefront is the identity: every path traces its camera ray and is shaded
+    unsigned long long counts[2] = {n_paths, n_paths};
+    local.camera_samples += (uint64_t)valid_pixels * pp.n_samples;
+    local.rays_closest += (uint64_t)valid_pixels * pp.n_samples;
+    int cur = 0, wavefront = 0;  // wavefront 0 = camera rays, 1 = first bounce + its shadow rays, ...
+    while (rc == PBRT_HIP_OK && counts[1] > 0) {
+        uint32_t n_trace = (uint32_t)counts[0], n_shade = (uint32_t)counts[1];
+        if (n_trace > 0) trace_wavefront(ev, q[cur], n_trace, wavefront, rc);
+        int nxt = cur ^ 1;
+        RENDER_TRY(hipMemsetAsync(q[nxt].counts64, 0, 2 * sizeof(unsigned long long), st));
+        // the wavefront this launch of k_shade fills is traced in Morton order: have it write the keys as well
+        q[nxt].keys = (sort_rays && wavefront + 1 >= kSortFrom) ? ray_sort.keys[0] : nullptr;
+        shade_wavefront(pp, cur, nxt, n_shade, wavefront, rc);
+        RENDER_TRY(hipGetLastError());
+        RENDER_TRY(hipMemcpyAsync(ctx->h_counts, q[nxt].counts64, sizeof(counts), hipMemcpyDeviceToHost, st));
+        RENDER_TRY(hipEventRecord(ctx->ev_sync, st));
+        if (rc == PBRT_HIP_OK) wait_for_counts(rc);
+        counts[0] = ctx->h_counts[0];
+        counts[1] = ctx->h_counts[1];
+        if (n_trace > 0 && rc == PBRT_HIP_OK) {
+            float ms = 0.0f;
+            RENDER_TRY(hipEventElapsedTime(&ms, ev.t0, ev.t1));
+            local.trace_ms += ms;
+            local.trace_launches += 1;
+            if (ctx->trace_log)
+                std::fprintf(stderr, "[pbrt_hip] k_trace: %u rays %.3f ms (%.0f Mrays/s), k_shade: %u paths\n", n_trace, ms, n_trace / ms * 1e-3,
+                             n_shade);
+            ctx->trace_ms += ms;
+            ctx->trace_launches += 1;
+        }
+        const uint64_t n_rays = counts[0] & 0xffffffffull, n_shadow = counts[0] >> 32;
+        local.rays_closest += n_rays - n_shadow;
+        local.rays_shadow += n_shadow;
+        counts[0] = n_rays;
+        wavefront += 1;
+        cur = nxt;
+    }
+}
+
+// stage 8b: what a finished pass leaves: radiance per ray (li), splats, or the ordered accumulation and, after the last pass, the merge
+void RenderJob::film_stage(const PassParams& pp, uint32_t n_paths, bool last_pass, int& rc) {
+    if (li_mode) {
+        hipLaunchKernelGGL(k_li_output, dim3((unsigned)((li->n + 255) / 256)), dim3(256), 0, st, ps, (uint32_t)li->n, li->d_rgb);
+        RENDER_TRY(hipGetLastError());
+        return;
+    }
+    if (!box) {
+        hipLaunchKernelGGL(k_film_splat, dim3((n_paths + 255) / 256), dim3(256), 0, st, ps, pp, tiles, d_film);
+        RENDER_TRY(hipGetLastError());
+        return;
+    }
+    if (pp.group_shift == 6)  // a wave of paths = one pixel's samples: sixteen lanes per pixel, coalesced reads, ordered row sums
+        hipLaunchKernelGGL(k_film_accumulate_rows, dim3((unsigned)(((size_t)n_pix * 16 + 255) / 256)), dim3(256), 0, st, ps, pp, tiles, accum,
+                           d_film);
+    else
+        hipLaunchKernelGGL(k_film_accumulate, dim3((n_pix + 255) / 256), dim3(256), 0, st, ps, pp, tiles, accum, d_film);
+    RENDER_TRY(hipGetLastError());
+    if (last_pass) {
+        hipLaunchKernelGGL(k_film_merge, dim3((n_pix + 255) / 256), dim3(256), 0, st, pp, tiles, accum, d_film);
+        RENDER_TRY(hipGetLastError());
+    }
+}
+
+// stage 8, the driver: tiles, the stages above, then per pass the camera rays, the wavefront loop and the film
+int RenderJob::run(const PbrtCamera& camera, PbrtRenderStats* stats) {
+    if (d_film) HIP_TRY(ctx, hipMemsetAsync(d_film, 0, (size_t)rp.width * rp.height * 4 * sizeof(float), st));
+
+    // tiles of the sample bounds (integrator.rs:402-409), dealt round-robin in rp.tile_order to the GPUs
+    std::vector<int2> origins;
+    if (li_mode) {
+        origins.assign((size_t)((li->n + kTile * kTile - 1) / (kTile * kTile)), make_int2(0, 0));  // 256 rays per "tile"
+    } else {
+        int32_t n_mine = 0;
+        if (pbrt_hip_tile_partition_order(rp.x0, rp.y0, rp.x1, rp.y1, rank, world, rp.tile_order, nullptr, 0, &n_mine) != PBRT_HIP_OK)
+            return invalid("tile partition: too many tiles");
+        origins.resize(n_mine);
+        pbrt_hip_tile_partition_order(rp.x0, rp.y0, rp.x1, rp.y1, rank, world, rp.tile_order, (int32_t*)origins.data(), n_mine, &n_mine);
+    }
+    if (origins.empty()) {
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (stats) *stats = local;
+        return PBRT_HIP_OK;
+    }
+    n_pix = (int)origins.size() * kTile * kTile;
+    for (const int2& o : origins)
+        valid_pixels += (int64_t)(std::min(o.x + kTile, rp.x1) - o.x) * (std::min(o.y + kTile, rp.y1) - o.y);
+    if (li_mode) valid_pixels = li->n;
+    if (int rc = size_pass()) return rc;
+    if (export_mode && spp_pass != rp.spp) return invalid("camera rays: too many samples for one pass");
+    N = (size_t)n_pix * spp_pass;
+    if (N * 4 >= (1ull << 32)) return invalid("too many concurrent paths for 32-bit queue entries; lower spp_per_pass");
+
+    // the device blocks of the call: released (or, on a lost context, kept for good) when this frame ends, after the drain below
+    DevBuf buf(ctx);
+    bool ok = true;
+    if (int rc = alloc_path_buffers(buf, &ok)) return rc;
+    if (int rc = setup_sampler(buf, &ok)) return rc;
     int* d_prefix = buf.alloc<int>(prefix.size(), &ok);
     if (direct) {
         ds.stage = buf.alloc<int>(N, &ok);
@@ -1026,20 +1341,18 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
         ds.ao_cos_sample = rp.light_strategy != 0;
         if (prefix.back() >= 0xfff0) return invalid("too many light samples per vertex");
     }
-    float* d_filter = nullptr;
     if (!box) {
         d_filter = buf.alloc<float>(256, &ok);
         if (ok) HIP_TRY(ctx, hipMemcpyAsync(d_filter, rp.filter_table, 256 * sizeof(float), hipMemcpyHostToDevice, st));
     }
-    float4* accum = buf.alloc<float4>(n_pix, &ok);
+    accum = buf.alloc<float4>(n_pix, &ok);
     int2* d_origins = buf.alloc<int2>(origins.size(), &ok);
     if (!ok) return PBRT_HIP_ERR_OOM;
     HIP_TRY(ctx, hipMemcpyAsync(d_origins, origins.data(), origins.size() * sizeof(int2), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemsetAsync(accum, 0, (size_t)n_pix * sizeof(float4), st));
     HIP_TRY(ctx, hipMemcpyAsync(d_prefix, prefix.data(), prefix.size() * sizeof(int), hipMemcpyHostToDevice, st));
-    TileList tiles{d_origins, (int)origins.size()};
+    tiles = TileList{d_origins, (int)origins.size()};
 
-    DevCamera cam;
     std::memcpy(cam.c2w, camera.camera_to_world, 64);
     std::memcpy(cam.r2c, camera.raster_to_camera, 64);
     cam.lens_radius = camera.lens_radius;
@@ -1049,108 +1362,37 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
     cam.kind = camera.kind;
     if (camera.kind < PBRT_CAMERA_PERSPECTIVE || camera.kind > PBRT_CAMERA_ENVIRONMENT) return invalid("unknown camera kind");
 
-    ShadeConsts sc;
+    // the scene's tables and, from them, this render's shading kernels (kernel_select.h)
+    const SceneNeeds needs = scene_needs(s);
     scene_shade_consts(s, &sc);
-    // create_light_sample_distribution (lightdistrib.rs:222-232): "uniform", or one light -> uniform
-    sc.distrib = (rp.light_strategy == 0 || s->d.n_lights == 1) ? s->d.light_distrib_uniform : s->d.light_distrib_power;
-    if (rp.integrator == PBRT_INTEGRATOR_PATH && (rp.light_strategy < 0 || rp.light_strategy > 2))
-        return invalid("path: light_strategy must be 0 (uniform), 1 (power) or 2 (spatial)");
     sc.light_sample_prefix = d_prefix;
     sc.total_light_samples = prefix.back();
-    if (rp.integrator == PBRT_INTEGRATOR_PATH && rp.light_strategy == 2 && s->d.n_lights > 1) {
-        // create_light_sample_distribution("spatial") -> SpatialLightDistribution::new(scene, 64) (lightdistrib.rs:85-107, 228)
-        if (!s->d_spatial) {
-            const float* mn = s->d.bvh.root_min;
-            const float* mx = s->d.bvh.root_max;
-            float diag[3] = {mx[0] - mn[0], mx[1] - mn[1], mx[2] - mn[2]};
-            int ext = (diag[0] > diag[1] && diag[0] > diag[2]) ? 0 : (diag[1] > diag[2] ? 1 : 2);
-            for (int i = 0; i < 3; ++i) s->spatial_voxels[i] = std::max(1, (int)std::round(diag[i] / diag[ext] * 64.0f));
-            size_t n_voxels = (size_t)s->spatial_voxels[0] * s->spatial_voxels[1] * s->spatial_voxels[2];
-            size_t floats = n_voxels * (size_t)(2 * s->d.n_lights + 2);
-            if (floats > (1ull << 30)) return invalid("spatial light distribution: voxels x lights exceed 4 GB; use \"power\"");
-            void* p = nullptr;
-            HIP_TRY(ctx, hipMalloc(&p, floats * sizeof(float)));
-            s->allocs.push_back(p);
-            for (int i = 0; i < 3; ++i) sc.n_voxel[i] = s->spatial_voxels[i];
-            if (s->d.bvh.has_spheres == 2)
-                hipLaunchKernelGGL(k_spatial_light_tables_shapes, dim3((unsigned)((n_voxels + 63) / 64)), dim3(64), 0, st, sc, (float*)p);
-            else if (s->light_maps)
-                hipLaunchKernelGGL(k_spatial_light_tables_maps, dim3((unsigned)((n_voxels + 63) / 64)), dim3(64), 0, st, sc, (float*)p);
-            else
-                hipLaunchKernelGGL(k_spatial_light_tables, dim3((unsigned)((n_voxels + 63) / 64)), dim3(64), 0, st, sc, (float*)p);
-            HIP_TRY(ctx, hipGetLastError());
-            HIP_TRY(ctx, hipStreamSynchronize(st));
-            s->d_spatial = (float*)p;
-        }
-        sc.spatial = s->d_spatial;
-        for (int i = 0; i < 3; ++i) sc.n_voxel[i] = s->spatial_voxels[i];
+    if (int rc = setup_light_distribution(needs)) return rc;
+    if (direct) {
+        shade_direct = direct_kernel(needs, rp.integrator);
+    } else {
+        shade_path[0] = path_kernel(needs, false);
+        shade_path[1] = path_kernel(needs, true);
     }
 
-    hipEvent_t e_begin = nullptr, e_end = nullptr, e_t0 = nullptr, e_t1 = nullptr;
-    auto cleanup_events = [&]() {
-        for (hipEvent_t e : {e_begin, e_end, e_t0, e_t1})
-            if (e) (void)hipEventDestroy(e);
-    };
-    if (!hip_ok(ctx, hipEventCreate(&e_begin), "hipEventCreate") || !hip_ok(ctx, hipEventCreate(&e_end), "hipEventCreate") ||
-        !hip_ok(ctx, hipEventCreate(&e_t0), "hipEventCreate") || !hip_ok(ctx, hipEventCreate(&e_t1), "hipEventCreate")) {
-        cleanup_events();
-        return PBRT_HIP_ERR_DEVICE;
-    }
+    RenderEvents ev;
+    if (!ev.create(ctx)) return PBRT_HIP_ERR_DEVICE;
     int rc = PBRT_HIP_OK;
-#define RENDER_TRY(call)                                  \
-    if (rc == PBRT_HIP_OK && !hip_ok(ctx, (call), #call)) rc = PBRT_HIP_ERR_DEVICE;
-
-    RENDER_TRY(hipEventRecord(e_begin, st));
+    RENDER_TRY(hipEventRecord(ev.begin, st));
     bool tables_ready = !tabulated || rp.sampler == PBRT_SAMPLER_HALTON;
     for (int s0 = 0; s0 < rp.spp && rc == PBRT_HIP_OK; s0 += spp_pass) {
-        PassParams pp;
-        pp.smp = smp;
-        pp.n_pix = n_pix;
-        pp.n_samples = std::min(spp_pass, rp.spp - s0);
-        {   // PbrtRenderParams.samples_per_wave: the largest power of two <= the request that divides the pass's samples per pixel
-            // default: a wave = the samples of ONE pixel (as many as the pass has, up to 64). The tabulating samplers keep the
-            // old layout: their tables are [element][pixel], read coalesced when a wave's lanes are 64 pixels of one sample
-            const int want = rp.samples_per_wave > 0 ? rp.samples_per_wave : ((tabulated && rp.sampler != PBRT_SAMPLER_HALTON) ? 1 : 64);
-            pp.group_shift = 0;
-            while ((2 << pp.group_shift) <= want && pp.group_shift < 6 && pp.n_samples % (2 << pp.group_shift) == 0) ++pp.group_shift;
-            if (li_mode || export_mode) pp.group_shift = 0;  // batches of rays / the exported camera rays keep the caller's order
-        }
-        pp.sample0 = s0;
-        pp.spp = rp.spp;
-        pp.width = rp.width;
-        pp.height = rp.height;
-        pp.x0 = rp.x0;
-        pp.y0 = rp.y0;
-        pp.x1 = rp.x1;
-        pp.y1 = rp.y1;
-        {
-            int32_t sb[4];
-            pbrt_hip_sample_bounds(rp.width, rp.height, frx, fry, sb);
-            pp.sb_x0 = sb[0];
-            pp.sb_y0 = sb[1];
-            pp.sb_w = sb[2] - sb[0];
-        }
-        pp.seed = rp.seed;
-        pp.max_depth = rp.max_depth;
-        pp.rr_threshold = rp.rr_threshold;
-        pp.light_strategy = rp.light_strategy;
-        pp.filter_rx = frx;
-        pp.filter_ry = fry;
-        pp.filter_table = d_filter;
-        pp.max_sample_luminance = rp.max_sample_luminance > 0.0f ? rp.max_sample_luminance : INFINITY;
-        pp.stream_keys = li_mode ? li->d_keys : nullptr;
-        uint32_t n_paths = (uint32_t)n_pix * pp.n_samples;
-        int cur = 0;
+        const PassParams pp = pass_params(s0);
+        const uint32_t n_paths = (uint32_t)n_pix * pp.n_samples;
         if (!tables_ready) {  // Sampler::start_pixel for every pixel of this GPU, once per render
             hipLaunchKernelGGL(k_sampler_tables, dim3((n_pix + 63) / 64), dim3(64), 0, st, pp, tiles);
             RENDER_TRY(hipGetLastError());
             tables_ready = true;
         }
         if (li_mode)
-            hipLaunchKernelGGL(k_li_generate, dim3((n_paths + 255) / 256), dim3(256), 0, st, ps, q[cur], li->d_rays, li->d_keys,
-                               (uint32_t)li->n, n_paths, li->skip);
+            hipLaunchKernelGGL(k_li_generate, dim3((n_paths + 255) / 256), dim3(256), 0, st, ps, q[0], li->d_rays, li->d_keys, (uint32_t)li->n,
+                               n_paths, li->skip);
         else
-            hipLaunchKernelGGL(k_generate, dim3((n_paths + 255) / 256), dim3(256), 0, st, ps, q[cur], pp, cam, tiles);
+            hipLaunchKernelGGL(k_generate, dim3((n_paths + 255) / 256), dim3(256), 0, st, ps, q[0], pp, cam, tiles);
         RENDER_TRY(hipGetLastError());
         if (export_mode) {
             hipLaunchKernelGGL(k_camera_rays_out, dim3((n_paths + 255) / 256), dim3(256), 0, st, ps, pp, tiles, li->out_rays, li->out_keys,
@@ -1162,236 +1404,10 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
             RENDER_TRY(hipMemsetAsync(ds.stage, 0, (size_t)n_paths * sizeof(int), st));
             RENDER_TRY(hipMemsetAsync(ds.ld_acc, 0, (size_t)n_paths * sizeof(float4), st));
         }
-        // the first wavefront is the identity: every path traces its camera ray and is shaded
-        unsigned long long counts[2] = {n_paths, n_paths};
-        local.camera_samples += (uint64_t)valid_pixels * pp.n_samples;
-        local.rays_closest += (uint64_t)valid_pixels * pp.n_samples;
-        bool first = true;
-        int wavefront = 0;  // 0 = camera rays, 1 = first bounce + its shadow rays, ...
-        while (rc == PBRT_HIP_OK && counts[1] > 0) {
-            uint32_t n_trace = (uint32_t)counts[0], n_shade = (uint32_t)counts[1];
-            if (n_trace > 0) {
-                RENDER_TRY(hipMemsetAsync(ctx->d_work_counter, 0, kWorkCounters * sizeof(unsigned int), st));
-                const uint32_t* trace_queue = q[cur].trace;
-                if (sort_rays && wavefront >= sort_from && n_trace >= (1u << 20)) {
-                    // from the second bounce on the rays of a wavefront start all over the scene (the first bounce still
-                    // follows the pixel order of its camera rays): trace them in Morton order of their origins (the keys were
-                    // written by k_shade together with the queue entries)
-                    size_t tb = sort_tmp_bytes;
-                    if (pb::sort_pairs_u32(st, sort_tmp, &tb, sort_keys[0], sort_keys[1], q[cur].trace, sort_vals, n_trace, kSortKeyBits) != 0 &&
-                        rc == PBRT_HIP_OK) {
-                        ctx->last_error = "rocPRIM radix sort failed";
-                        rc = PBRT_HIP_ERR_DEVICE;
-                    }
-                    trace_queue = sort_vals;
-                }
-                RENDER_TRY(hipEventRecord(e_t0, st));
-                {
-                    dim3 grid(persistent_grid(s)), block(kTraceBlock);
-                    const int inst = s->d.bvh.instanced ? (s->d.bvh.general_top ? 2 : 1) : 0;  // trace_persistent.h: INST
-                    int segments = (wavefront == 0 && !inst) ? kQueueSegments : 1;  // see trace.h
-                    const bool count_ref = ctx->count_traversal == 1, count_wide = ctx->count_traversal == 2;
-#define PB_LAUNCH_BINARY(COUNT, INST, SPH) \
-    hipLaunchKernelGGL((k_trace<COUNT, INST, SPH>), grid, block, 0, st, s->d.bvh, ps, trace_queue, n_trace, ctx->d_work_counter, ctx->d_counters, segments)
-#define PB_LAUNCH_WIDE(COUNT, INST)                                                                                                        \
-    hipLaunchKernelGGL((k_trace_wide<COUNT, INST>), dim3(persistent_grid(s, (COUNT || INST) ? PB_WIDE_INST_WAVES : PB_WIDE_WAVES, wide_stack_lds(INST), wide_world_lds_bytes(INST))), \
-                       block, 0, st, wt, ps, trace_queue, n_trace, ctx->d_work_counter, segments, ctx->d_counters)
-#define PB_LAUNCH_SPECIAL(INST)                                                                                   \
-    hipLaunchKernelGGL(k_trace_special<INST>, grid, block, 0, st, s->d.bvh, ps, trace_queue, n_trace, special_list, \
-                       ctx->d_work_counter + kSpecialCount, ctx->d_work_counter + kFollowUpCounter)
-                    if (stackless) {
-                        hipLaunchKernelGGL(k_trace_stackless, dim3(stackless_grid(s)), block, 0, st, s->d.bvh, ps, trace_queue, n_trace,
-                                           ctx->d_work_counter, segments);
-                    } else if (use_wide) {
-                        WideTrees wt = s->wide;
-                        wt.special_list = special_list;
-                        wt.special_count = ctx->d_work_counter + kSpecialCount;
-                        if (inst == 2) {
-                            if (count_wide) PB_LAUNCH_WIDE(true, 2); else PB_LAUNCH_WIDE(false, 2);
-                            PB_LAUNCH_SPECIAL(2);
-                        } else if (inst == 1) {
-                            if (count_wide) PB_LAUNCH_WIDE(true, 1); else PB_LAUNCH_WIDE(false, 1);
-                            PB_LAUNCH_SPECIAL(1);
-                        } else {
-                            if (count_wide) PB_LAUNCH_WIDE(true, 0); else PB_LAUNCH_WIDE(false, 0);
-                            PB_LAUNCH_SPECIAL(0);
-                        }
-                    } else if (s->d.bvh.has_spheres == 2) {
-                        if (count_ref)
-                            hipLaunchKernelGGL(k_trace_shapes<true>, grid, block, 0, st, s->d.bvh, ps, trace_queue, n_trace, ctx->d_work_counter, ctx->d_counters, segments);
-                        else
-                            hipLaunchKernelGGL(k_trace_shapes<false>, grid, block, 0, st, s->d.bvh, ps, trace_queue, n_trace, ctx->d_work_counter, ctx->d_counters, segments);
-                    } else if (s->d.bvh.has_spheres) {
-                        if (count_ref) PB_LAUNCH_BINARY(true, 0, true); else PB_LAUNCH_BINARY(false, 0, true);
-                    } else if (inst == 2) {
-                        if (count_ref) PB_LAUNCH_BINARY(true, 2, false); else PB_LAUNCH_BINARY(false, 2, false);
-                    } else if (inst == 1) {
-                        if (count_ref) PB_LAUNCH_BINARY(true, 1, false); else PB_LAUNCH_BINARY(false, 1, false);
-                    } else {
-                        if (count_ref) PB_LAUNCH_BINARY(true, 0, false); else PB_LAUNCH_BINARY(false, 0, false);
-                    }
-#undef PB_LAUNCH_BINARY
-#undef PB_LAUNCH_WIDE
-#undef PB_LAUNCH_SPECIAL
-                }
-                RENDER_TRY(hipGetLastError());
-                RENDER_TRY(hipEventRecord(e_t1, st));
-            }
-            int nxt = cur ^ 1;
-            RENDER_TRY(hipMemsetAsync(q[nxt].counts64, 0, 2 * sizeof(unsigned long long), st));
-            // the wavefront this launch of k_shade fills is traced in Morton order: have it write the keys as well
-            q[nxt].keys = (sort_rays && wavefront + 1 >= sort_from) ? sort_keys[0] : nullptr;
-            if (direct)
-{
-                dim3 sg((n_shade + 255) / 256), sb(256);
-                // a plastic or metal material in the scene's table selects the level-1 instantiations, a row of
-                // pbrt_hip_scene_set_material the level-2 ones, a Disney row the level-3 ones (AO reads no BSDF)
-                const bool shapes = s->d.bvh.has_spheres == 2;  // general quadric shapes: their own builds (wf_direct.h: kDirectShapes)
-                if (shapes && rp.integrator == PBRT_INTEGRATOR_DIRECT)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, 3 + kDirectShapes>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
-                else if (shapes && rp.integrator == PBRT_INTEGRATOR_WHITTED)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, 3 + kDirectShapes>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
-                else if (shapes)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_AO, kDirectShapes>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
-                // a projection or goniometric light: the map-light builds of the most general level, whatever the material table
-                else if (rp.integrator == PBRT_INTEGRATOR_DIRECT && s->light_maps)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, 3 + kDirectMapLights>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
-                else if (rp.integrator == PBRT_INTEGRATOR_WHITTED && s->light_maps)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, 3 + kDirectMapLights>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
-                else if (rp.integrator == PBRT_INTEGRATOR_DIRECT && s->disney)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, 3>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
-                else if (rp.integrator == PBRT_INTEGRATOR_WHITTED && s->disney)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, 3>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
-                else if (rp.integrator == PBRT_INTEGRATOR_DIRECT && s->bxdfs)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, 2>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
-                else if (rp.integrator == PBRT_INTEGRATOR_DIRECT && s->glossy)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, 1>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
-                else if (rp.integrator == PBRT_INTEGRATOR_DIRECT)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_DIRECT, 0>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
-                else if (rp.integrator == PBRT_INTEGRATOR_WHITTED && s->bxdfs)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, 2>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
-                else if (rp.integrator == PBRT_INTEGRATOR_WHITTED && s->glossy)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, 1>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
-                else if (rp.integrator == PBRT_INTEGRATOR_WHITTED)
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_WHITTED, 0>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
-                else
-                    hipLaunchKernelGGL((k_shade_direct<PBRT_INTEGRATOR_AO, 0>), sg, sb, 0, st, sc, ps, ds, q[cur], q[nxt], pp, tiles, n_shade);
-            }
-            else {
-                const Queues qin = q[cur];
-                const uint32_t* order = nullptr;  // shade_order 2: the queue positions in material order
-                if (sort_shade && wavefront >= 1 && n_shade >= (1u << 10)) {  // the first wavefront is all camera hits in pixel order
-                    hipLaunchKernelGGL(k_shade_sort_keys, dim3((n_shade + 255) / 256), dim3(256), 0, st, sc, ps, q[cur].shade, n_shade,
-                                       pp.max_depth, shade_keys[0], shade_positions);
-                    size_t tb = shade_tmp_bytes;
-                    if (pb::sort_pairs_u32(st, shade_tmp, &tb, shade_keys[0], shade_keys[1], shade_positions, shade_sorted, n_shade, (s->bxdfs || s->disney) ? 4 : 3) != 0 &&
-                        rc == PBRT_HIP_OK) {
-                        ctx->last_error = "rocPRIM radix sort failed";
-                        rc = PBRT_HIP_ERR_DEVICE;
-                    }
-                    order = shade_sorted;
-                }
-                const dim3 sg((n_shade + 255) / 256), sb(256);
-                const bool shapes = s->d.bvh.has_spheres == 2;  // general quadric shapes: their own builds (wf_path.h)
-                if (shapes && bin_shade && wavefront >= 1)
-                    hipLaunchKernelGGL(k_shade_shapes<true>, sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
-                else if (shapes)
-                    hipLaunchKernelGGL(k_shade_shapes<false>, sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
-                else if (s->light_maps && bin_shade && wavefront >= 1)  // a projection or goniometric light: their own builds (wf_path.h)
-                    hipLaunchKernelGGL(k_shade_maps<true>, sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
-                else if (s->light_maps)
-                    hipLaunchKernelGGL(k_shade_maps<false>, sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
-                else if (bin_shade && wavefront >= 1 && s->disney)
-                    hipLaunchKernelGGL((k_shade<true, 3>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
-                else if (bin_shade && wavefront >= 1 && s->bxdfs)
-                    hipLaunchKernelGGL((k_shade<true, 2>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
-                else if (bin_shade && wavefront >= 1 && s->glossy)
-                    hipLaunchKernelGGL((k_shade<true, 1>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
-                else if (bin_shade && wavefront >= 1)
-                    hipLaunchKernelGGL((k_shade<true, 0>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
-                else if (s->disney)
-                    hipLaunchKernelGGL((k_shade<false, 3>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
-                else if (s->bxdfs)
-                    hipLaunchKernelGGL((k_shade<false, 2>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
-                else if (s->glossy)
-                    hipLaunchKernelGGL((k_shade<false, 1>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
-                else
-                    hipLaunchKernelGGL((k_shade<false, 0>), sg, sb, 0, st, sc, ps, qin, q[nxt], pp, tiles, n_shade, order);
-                // what this launch wrote is the generation the next trace and shade launches read
-                std::swap(ps.ray, ps.ray_next);
-                std::swap(ps.nee_a, ps.nee_a_next);
-                std::swap(ps.nee_f, ps.nee_f_next);
-                std::swap(ps.nee_b, ps.nee_b_next);
-                std::swap(ps.nee_light, ps.nee_light_next);
-            }
-            RENDER_TRY(hipGetLastError());
-            RENDER_TRY(hipMemcpyAsync(ctx->h_counts, q[nxt].counts64, sizeof(counts), hipMemcpyDeviceToHost, st));
-            RENDER_TRY(hipEventRecord(ctx->ev_sync, st));
-            if (rc == PBRT_HIP_OK) {
-                // spin on the event (a blocking sync costs a scheduler wake-up per wavefront), but not for ever: a kernel
-                // that never finishes must surface as an error of this call, with the context's lock released
-                hipError_t qe;
-                const auto spin_start = std::chrono::steady_clock::now();
-                uint32_t polls = 0;
-                while ((qe = hipEventQuery(ctx->ev_sync)) == hipErrorNotReady) {
-                    if ((++polls & 0xfffu) == 0) {
-                        const double waited = std::chrono::duration<double>(std::chrono::steady_clock::now() - spin_start).count();
-                        if (waited > ctx->wavefront_deadline_s) {
-                            ctx->last_error = "a wavefront did not finish within the deadline (hung kernel?)";
-                            ctx->lost = true;  // the stream is not drained below: nothing may follow on this context
-                            rc = PBRT_HIP_ERR_DEVICE;
-                            break;
-                        }
-                        if (waited > 0.05) std::this_thread::yield();  // long wavefronts: stop burning a core
-                    }
-                }
-                if (rc == PBRT_HIP_OK) RENDER_TRY(qe);
-            }
-            counts[0] = ctx->h_counts[0];
-            counts[1] = ctx->h_counts[1];
-            if (n_trace > 0 && rc == PBRT_HIP_OK) {
-                float ms = 0.0f;
-                RENDER_TRY(hipEventElapsedTime(&ms, e_t0, e_t1));
-                local.trace_ms += ms;
-                local.trace_launches += 1;
-                if (ctx->trace_log)
-                    std::fprintf(stderr, "[pbrt_hip] k_trace: %u rays %.3f ms (%.0f Mrays/s), k_shade: %u paths\n", n_trace, ms, n_trace / ms * 1e-3,
-                                 n_shade);
-                ctx->trace_ms += ms;
-                ctx->trace_launches += 1;
-            }
-            {
-                uint64_t n_rays = counts[0] & 0xffffffffull, n_shadow = counts[0] >> 32;
-                local.rays_closest += n_rays - n_shadow;
-                local.rays_shadow += n_shadow;
-                counts[0] = n_rays;
-            }
-            (void)first;
-            first = false;
-            wavefront += 1;
-            cur = nxt;
-        }
-        if (li_mode) {
-            hipLaunchKernelGGL(k_li_output, dim3((unsigned)((li->n + 255) / 256)), dim3(256), 0, st, ps, (uint32_t)li->n, li->d_rgb);
-            RENDER_TRY(hipGetLastError());
-            continue;
-        }
-        if (!box) {
-            hipLaunchKernelGGL(k_film_splat, dim3((n_paths + 255) / 256), dim3(256), 0, st, ps, pp, tiles, d_film);
-            RENDER_TRY(hipGetLastError());
-            continue;
-        }
-        if (pp.group_shift == 6)  // a wave of paths = one pixel's samples: sixteen lanes per pixel, coalesced reads, ordered row sums
-            hipLaunchKernelGGL(k_film_accumulate_rows, dim3((unsigned)(((size_t)n_pix * 16 + 255) / 256)), dim3(256), 0, st, ps, pp, tiles, accum, d_film);
-        else
-            hipLaunchKernelGGL(k_film_accumulate, dim3((n_pix + 255) / 256), dim3(256), 0, st, ps, pp, tiles, accum, d_film);
-        RENDER_TRY(hipGetLastError());
-        if (s0 + spp_pass >= rp.spp) {
-            hipLaunchKernelGGL(k_film_merge, dim3((n_pix + 255) / 256), dim3(256), 0, st, pp, tiles, accum, d_film);
-            RENDER_TRY(hipGetLastError());
-        }
+        run_wavefronts(ev, pp, n_paths, rc);
+        film_stage(pp, n_paths, s0 + spp_pass >= rp.spp, rc);
     }
-    RENDER_TRY(hipEventRecord(e_end, st));
+    RENDER_TRY(hipEventRecord(ev.end, st));
     // Nothing of this call may still run when its buffers go back to the cache: drain the stream, also after an error
     // (an asynchronous fault of the last kernels surfaces here). After the deadline the stream is presumed hung: it is
     // not waited on, the context is lost and the buffers are never reused (DevBuf).
@@ -1401,14 +1417,21 @@ int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRender
     }
     if (rc == PBRT_HIP_OK) {
         float ms = 0.0f;
-        RENDER_TRY(hipEventElapsedTime(&ms, e_begin, e_end));
+        RENDER_TRY(hipEventElapsedTime(&ms, ev.begin, ev.end));
         local.total_ms = ms;
     }
-#undef RENDER_TRY
-    cleanup_events();
     if (stats) *stats = local;
     return rc;
 }
+}  // namespace
+
+int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRenderParams& rp_in, float* d_film,
+                     PbrtRenderStats* stats, const LiBatch* li) {
+    RenderJob job{s, s->ctx, s->ctx->stream, li, d_film};
+    if (const char* why = job.normalise_params(rp_in)) return job.invalid(why);
+    return job.run(camera, stats);
+}
+#undef RENDER_TRY
 
 #ifdef PB_LANE_STATS
 extern "C" int pbrt_hip_debug_wide_stats(unsigned long long* out24, int reset) try {

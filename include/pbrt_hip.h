@@ -400,6 +400,70 @@ typedef struct PbrtDisneyDesc {
     int32_t thin;
 } PbrtDisneyDesc;
 int pbrt_hip_scene_set_disney_material(PbrtHipScene* scene, int32_t material, const PbrtDisneyDesc* desc);
+/* pbrt-v3's UberMaterial, TranslucentMaterial and MixMaterial on the reference's general BSDF: a list of up to 8 lobes of any
+ * kind, matched by BxDFType flags (reflection.rs:207-449). pbrt_hip_scene_set_lobe_material replaces row `material` by such a
+ * list ("lobe row"); pbrt_hip_scene_set_material and pbrt_hip_scene_set_disney_material replace a lobe row in turn. Every colour
+ * is clamped to [0, 1] first (pbrt-v3's Clamp()), colour products are formed in float in pbrt-v3's order, a lobe whose colour is
+ * black is left out, and a = roughness_to_alpha(roughness) when remap_roughness != 0, else a = roughness.
+ *   PBRT_LOBEMAT_UBER         kd, ks, kr, kt, opacity, eta, u_roughness, v_roughness. t = clamp(1 - opacity), op = clamp(opacity).
+ *                             t not black: SpecularTransmission(t, 1, 1) first and the BSDF's eta is 1; else its eta is `eta`. Then
+ *                             LambertianReflection(op Kd), MicrofacetReflection(op Ks, TR(a_u, a_v), FresnelDielectric(1, eta)),
+ *                             SpecularReflection(op Kr, FresnelDielectric(1, eta)), SpecularTransmission(op Kt, 1, eta).
+ *   PBRT_LOBEMAT_TRANSLUCENT  kd, ks, reflect (r), transmit (t), u_roughness (isotropic). No lobe when r and t are both black. Kd not
+ *                             black: LambertianReflection(r Kd), LambertianTransmission(t Kd). Ks not black: MicrofacetReflection(
+ *                             r Ks, TR(a, a), FresnelDielectric(1, 1.5)), MicrofacetTransmission(t Ks, TR(a, a), 1, 1.5). eta 1.5.
+ *   PBRT_LOBEMAT_MIX          material_a, material_b (rows of the same scene), amount. s1 = clamp(amount), s2 = clamp(1 - s1): a's
+ *                             lobes under ScaledBxDF(s1), then b's under ScaledBxDF(s2) (a black scale is kept, as pbrt-v3 keeps
+ *                             it; ScaledBxDF scales f and sample_f's value, not the pdf). The BSDF's eta is a's. The operands'
+ *                             lists are COPIED AT THE TIME OF THE CALL: setting row a or b again later does not change the mix row.
+ * The path integrator estimates direct lighting when the row has a non-specular lobe, samples the next vertex over all lobes,
+ * and takes the specular-bounce flag from the sampled lobe; DirectLighting and Whitted follow every matching specular lobe in
+ * their reflect and transmit branches. PBRT_HIP_ERR_INVALID (pbrt_hip_last_error says why, the scene unchanged) for a null
+ * descriptor, a row out of range, an unknown type, a colour, roughness or amount that is not finite or negative, eta <= 0, a
+ * roughness of 0 with remap_roughness == 0 on a row that gets a microfacet lobe, a mix operand out of range, a mix operand that is
+ * a Disney row, a lobe row made by a mix, or a smooth glass row (PBRT_MAT_GLASS: its lobes depend on the integrator; an uber row
+ * with Kr, Kt gives smooth specular lobes in a mix), a mix of more than 8 lobes, and a scene with general quadric shapes or with
+ * a projection or goniometric light. */
+enum PbrtLobeMaterialType { PBRT_LOBEMAT_UBER = 1, PBRT_LOBEMAT_TRANSLUCENT = 2, PBRT_LOBEMAT_MIX = 3 };
+typedef struct PbrtLobeMaterialDesc {
+    int32_t type;                 /* PbrtLobeMaterialType */
+    float kd[3], ks[3];           /* uber, translucent */
+    float kr[3], kt[3];           /* uber */
+    float opacity[3];             /* uber */
+    float reflect[3], transmit[3]; /* translucent */
+    float amount[3];              /* mix */
+    float eta;                    /* uber (> 0) */
+    float u_roughness, v_roughness; /* uber; translucent reads u_roughness */
+    int32_t remap_roughness;
+    int32_t material_a, material_b; /* mix */
+} PbrtLobeMaterialDesc;
+int pbrt_hip_scene_set_lobe_material(PbrtHipScene* scene, int32_t material, const PbrtLobeMaterialDesc* desc);
+/* One lobe of a list. `type` holds the BxDFType bits the reference gives the kind (1 reflection, 2 transmission, 4 diffuse,
+ * 8 glossy, 16 specular). The specular kinds and MicrofacetTransmission take eta_i = 1. */
+enum PbrtLobeKind { PBRT_LOBE_LAMBERTIAN_REFLECTION = 1, PBRT_LOBE_LAMBERTIAN_TRANSMISSION = 2, PBRT_LOBE_OREN_NAYAR = 3,
+                    PBRT_LOBE_SPECULAR_REFLECTION = 4, PBRT_LOBE_SPECULAR_TRANSMISSION = 5, PBRT_LOBE_MICROFACET_REFLECTION = 6,
+                    PBRT_LOBE_MICROFACET_TRANSMISSION = 7, PBRT_LOBE_FRESNEL_BLEND = 8 };
+enum PbrtLobeFresnel { PBRT_FRESNEL_NOOP = 0, PBRT_FRESNEL_DIELECTRIC = 1, PBRT_FRESNEL_CONDUCTOR = 2 };
+typedef struct PbrtLobe {
+    int32_t kind;     /* PbrtLobeKind */
+    int32_t type;     /* BxDFType bits */
+    int32_t fresnel;  /* PbrtLobeFresnel: SpecularReflection and MicrofacetReflection */
+    float scale[3];   /* ScaledBxDF's factor, 1 outside a mix */
+    float r[3];       /* the lobe's colour: R or T; FresnelBlend Rd */
+    float s[3];       /* FresnelBlend Rs */
+    float ax, ay;     /* Trowbridge-Reitz alphas */
+    float eta_i, eta_t; /* FresnelDielectric(eta_i, eta_t); the transmission kinds: eta_a = eta_i, eta_b = eta_t */
+    float eta[3], k[3]; /* FresnelConductor(1, eta, k) */
+    float A, B;       /* OrenNayar */
+} PbrtLobe;
+/* The lobe list and BSDF eta of any row description, on the host, without a context or a GPU: exactly one of `row` (a
+ * PbrtMaterial as given at scene creation), `desc` (pbrt_hip_scene_set_material) and `lobe_desc` is not NULL. For
+ * PBRT_LOBEMAT_MIX the operands' lists are a[n_a] with eta_a and b[n_b] (material_a / material_b are not read). lobes[8], n and
+ * eta receive the list. PBRT_HIP_ERR_INVALID with *reason set (a static string; reason may be NULL) for what the setters refuse
+ * and can be seen here: bad values, more than 8 lobes, and smooth glass (PBRT_MAT_GLASS), whose lobes depend on the integrator. */
+int pbrt_hip_material_lobes(const PbrtMaterial* row, const PbrtMaterialDesc* desc, const PbrtLobeMaterialDesc* lobe_desc,
+                            const PbrtLobe* a, int32_t n_a, float eta_a, const PbrtLobe* b, int32_t n_b, PbrtLobe lobes[8],
+                            int32_t* n, float* eta, const char** reason);
 /* BSDF::f, BSDF::pdf and BSDF::sample_f (reflection.rs:264-446) of material `material` of the scene, in batch form, evaluated
  * on the device by the functions the shading kernels inline (any material type). Directions are in the shading frame
  * (ns = ng = +z, dpdu = +x): wo[3 i ..], wi[3 i ..], u[2 i ..] the sample_f sample. Outputs: f[3 i ..] = f(wo, wi),

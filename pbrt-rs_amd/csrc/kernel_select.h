@@ -81,10 +81,11 @@ struct SceneNeeds {
     bool shapes;      // bvh.has_spheres == 2
     bool light_maps;  // a projection or goniometric light in the table
     int level;        // 0 matte / mirror / glass, 1 plastic or metal, 2 a row of pbrt_hip_scene_set_material, 3 a Disney row
+    bool lobes;       // a row of pbrt_hip_scene_set_lobe_material: the lobe-list builds (never with shapes or light_maps: the setter refuses)
     int column() const { return shapes ? 0 : light_maps ? 1 : 5 - level; }  // of the tables below: in that precedence, most general first
 };
 inline SceneNeeds scene_needs(const PbrtHipScene* s) {
-    return SceneNeeds{s->d.bvh.has_spheres == 2, s->light_maps, s->disney ? 3 : s->bxdfs ? 2 : s->glossy ? 1 : 0};
+    return SceneNeeds{s->d.bvh.has_spheres == 2, s->light_maps, s->disney ? 3 : s->bxdfs ? 2 : s->glossy ? 1 : 0, s->lobes};
 }
 
 #ifdef PB_SELECT_SHADING_KERNELS
@@ -94,6 +95,10 @@ using SpatialKernel = void (*)(ShadeConsts, float*);
 // The tables list every instantiation the library holds, once. Their initialisers are also where the compiler first meets each
 // instantiation, and the code it generates for some of the kernels depends on that order (profiles/r11_render_driver.txt): the
 // rows and columns below keep the order the kernels have always been named in.
+
+// The lobe-list builds have tables of their own at the END of this file, so that every older instantiation is met first.
+inline DirectKernel lobe_direct_kernel(bool whitted);
+inline PathKernel lobe_path_kernel(bool bin);
 
 // the build of the SpatialLightDistribution tables (wf_lights.h)
 inline SpatialKernel spatial_tables_kernel(const SceneNeeds& n) {
@@ -111,6 +116,7 @@ inline DirectKernel direct_kernel(const SceneNeeds& n, int integrator) {
                                                {k_shade_direct<D, 1>, k_shade_direct<W, 1>},
                                                {k_shade_direct<D, 0>, k_shade_direct<W, 0>}};
     static constexpr DirectKernel ao[2] = {k_shade_direct<AO, kDirectShapes>, k_shade_direct<AO, 0>};
+    if (n.lobes && (integrator == D || integrator == W)) return lobe_direct_kernel(integrator == W);
     if (integrator == D || integrator == W) return lit[n.column()][integrator == W];
     return ao[n.shapes ? 0 : 1];
 }
@@ -120,7 +126,19 @@ inline PathKernel path_kernel(const SceneNeeds& n, bool bin) {
     static constexpr PathKernel table[2][6] = {
         {k_shade_shapes<true>, k_shade_maps<true>, k_shade<true, 3>, k_shade<true, 2>, k_shade<true, 1>, k_shade<true, 0>},
         {k_shade_shapes<false>, k_shade_maps<false>, k_shade<false, 3>, k_shade<false, 2>, k_shade<false, 1>, k_shade<false, 0>}};
+    if (n.lobes) return lobe_path_kernel(bin);
     return table[bin ? 0 : 1][n.column()];
+}
+
+// k_shade_direct<MODE, 3 + kDirectLobes> and k_shade_lobes<BIN>: scenes that hold a lobe row
+inline DirectKernel lobe_direct_kernel(bool whitted) {
+    static constexpr DirectKernel table[2] = {k_shade_direct<PBRT_INTEGRATOR_DIRECT, 3 + kDirectLobes>,
+                                              k_shade_direct<PBRT_INTEGRATOR_WHITTED, 3 + kDirectLobes>};
+    return table[whitted ? 1 : 0];
+}
+inline PathKernel lobe_path_kernel(bool bin) {
+    static constexpr PathKernel table[2] = {k_shade_lobes<true>, k_shade_lobes<false>};
+    return table[bin ? 0 : 1];
 }
 #endif  // PB_SELECT_SHADING_KERNELS
 

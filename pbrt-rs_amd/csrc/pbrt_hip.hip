@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "host_envmap.h"
+#include "host_lobes.h"
 #include "host_wide.h"
 #include "kernel_select.h"
 #include "scene.h"
@@ -586,30 +587,7 @@ extern "C" int pbrt_hip_scene_create_instanced(PbrtHipContext* ctx, const float*
 }
 PB_ABI_CATCH
 
-// TrowbridgeReitzDistribution::roughness_to_alpha (microfacet.rs:160-169), in double, rounded once
-static float roughness_to_alpha(float roughness) {
-    double x = std::log(std::max((double)roughness, 1e-3));
-    return (float)(1.62142 + 0.819955 * x + 0.1734 * x * x + 0.0171201 * x * x * x + 0.000640711 * x * x * x * x);
-}
-// Roughness of a plastic / metal material: finite, >= 0, and > 0 when it is taken as alpha unchanged (remap off)
-static const char* roughness_invalid(float u, float v, bool remap) {
-    if (!std::isfinite(u) || !std::isfinite(v) || u < 0.0f || v < 0.0f) return "roughness must be finite and >= 0";
-    if (!remap && (u == 0.0f || v == 0.0f)) return "roughness 0 without remapping (alpha 0)";
-    return nullptr;
-}
-// The one place materials are checked (scene creation); nullptr when the material is usable
-static const char* material_invalid(const PbrtMaterial& m) {
-    if (m.type < PBRT_MAT_NONE || m.type > PBRT_MAT_METAL) return "unknown material type";
-    if (m.type == PBRT_MAT_GLASS && !(m.eta > 0.0f)) return "glass needs eta > 0";
-    if (m.type == PBRT_MAT_PLASTIC || m.type == PBRT_MAT_METAL)
-        if (const char* why = roughness_invalid(m.eta, m.eta, true)) return why;
-    if (m.type == PBRT_MAT_METAL)
-        for (int c = 0; c < 3; ++c) {
-            if (!(std::isfinite(m.kd[c]) && m.kd[c] > 0.0f)) return "metal eta must be finite and > 0";
-            if (!(std::isfinite(m.kt[c]) && m.kt[c] >= 0.0f)) return "metal k must be finite and >= 0";
-        }
-    return nullptr;
-}
+// roughness_to_alpha, roughness_invalid and material_invalid (the one place materials are checked): host_lobes.h
 
 // ---- PbrtShape: what the constructors make of the arguments (Sphere::new sphere.rs:208-226, Disk::new disk.rs:24-40,
 // Cylinder::new cylinder.rs:23-39): z ordered (sphere: clamped to the radius), phi_max clamped and in radians ----
@@ -939,12 +917,8 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
     for (int32_t i = 0; i < n_lights; ++i) s->light_samples[i] = (dl[i].type == PBRT_LIGHT_PROJECTION || dl[i].type == PBRT_LIGHT_GONIOMETRIC) ? 1 : std::max(1, lights[i].n_samples);
     std::vector<DevMaterial> dm(n_materials);
     for (int32_t i = 0; i < n_materials; ++i) {
-        dm[i].type = materials[i].type;
-        std::memcpy(dm[i].kd, materials[i].kd, 12);
-        std::memcpy(dm[i].kt, materials[i].kt, 12);
-        dm[i].eta = materials[i].eta;
+        dm[i] = row_of_material(materials[i]);
         const bool glossy = materials[i].type == PBRT_MAT_PLASTIC || materials[i].type == PBRT_MAT_METAL;
-        dm[i].alpha_u = dm[i].alpha_v = glossy ? roughness_to_alpha(materials[i].eta) : 0.0f;
         s->glossy = s->glossy || glossy;
     }
     s->h_materials = dm;
@@ -1226,6 +1200,9 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
     {
         std::vector<DevDisney> dz(n_materials, DevDisney{});  // pbrt_hip_scene_set_disney_material fills a row's block
         d.disney = dev_upload(s, dz.data(), dz.size(), &ok);
+        s->h_lobe_rows.assign(n_materials, DevLobeRow{});  // pbrt_hip_scene_set_lobe_material fills a row's list
+        s->h_lobe_origin.assign(n_materials, 0);
+        d.lobe_rows = dev_upload(s, s->h_lobe_rows.data(), s->h_lobe_rows.size(), &ok);
     }
     d.lights = dev_upload(s, dl.data(), dl.size(), &ok);
     if (s->light_maps) {
@@ -1361,8 +1338,9 @@ PB_ABI_CATCH
 
 // which shading-kernel level the table needs beyond plastic / metal, after a row was replaced
 static void refresh_material_levels(PbrtHipScene* s) {
-    s->bxdfs = s->disney = false;
+    s->bxdfs = s->disney = s->lobes = false;
     for (const DevMaterial& row : s->h_materials) {
+        s->lobes = s->lobes || row.type == kMatLobes;
         s->bxdfs = s->bxdfs || (row.type >= kMatOrenNayar && row.type <= kMatSubstrate);
         s->disney = s->disney || row.type == kMatDisney;
     }
@@ -1383,57 +1361,13 @@ extern "C" int pbrt_hip_scene_set_material(PbrtHipScene* s, int32_t material, co
     };
     if (!desc) return invalid("null desc");
     if (material < 0 || material >= (int32_t)s->h_materials.size()) return invalid("material index out of range");
-    const PbrtMaterialDesc& d = *desc;
-    if (d.type != PBRT_MATDESC_MATTE && d.type != PBRT_MATDESC_GLASS && d.type != PBRT_MATDESC_SUBSTRATE)
-        return invalid("unknown material descriptor type");
-    auto bad_colour = [](const float* c) {
-        for (int k = 0; k < 3; ++k)
-            if (!std::isfinite(c[k]) || c[k] < 0.0f) return true;
-        return false;
-    };
-    auto black = [](const float* c) { return c[0] == 0.0f && c[1] == 0.0f && c[2] == 0.0f; };
     DevMaterial m{};
-    if (d.type == PBRT_MATDESC_MATTE) {
-        if (bad_colour(d.kd)) return invalid("Kd must be finite and >= 0");
-        if (!std::isfinite(d.sigma) || d.sigma < 0.0f) return invalid("sigma must be finite and >= 0");
-        std::memcpy(m.kd, d.kd, 12);
-        const double sigma = std::min((double)d.sigma, 90.0) * (3.14159265358979323846 / 180.0);  // MatteMaterial's clamp, then radians
-        if (sigma == 0.0) {
-            m.type = PBRT_MAT_MATTE;
-            m.eta = 1.0f;
-        } else {  // OrenNayar::new (reflection.rs:925-936), in double, rounded once
-            const double sigma2 = sigma * sigma;
-            m.type = kMatOrenNayar;
-            m.alpha_u = (float)(1.0 - sigma2 / (2.0 * (sigma2 + 0.33)));
-            m.alpha_v = (float)(0.45 * sigma2 / (sigma2 + 0.09));
-        }
-    } else {
-        const bool glass = d.type == PBRT_MATDESC_GLASS;
-        const float* c0 = glass ? d.kr : d.kd;
-        const float* c1 = glass ? d.kt : d.ks;
-        if (bad_colour(c0)) return invalid(glass ? "Kr must be finite and >= 0" : "Kd must be finite and >= 0");
-        if (bad_colour(c1)) return invalid(glass ? "Kt must be finite and >= 0" : "Ks must be finite and >= 0");
-        if (glass && !(std::isfinite(d.eta) && d.eta > 0.0f)) return invalid("glass needs a finite eta > 0");
-        const bool remap = d.remap_roughness != 0;
-        if (const char* why = roughness_invalid(d.u_roughness, d.v_roughness, true)) return invalid(why);
-        std::memcpy(m.kd, c0, 12);
-        std::memcpy(m.kt, c1, 12);
-        m.eta = glass ? d.eta : 1.0f;
-        if (glass && d.u_roughness == 0.0f && d.v_roughness == 0.0f) {
-            m.type = PBRT_MAT_GLASS;  // GlassMaterial's isSpecular: FresnelSpecular / the specular lobes
-        } else {
-            // alpha 0 is refused only where a microfacet lobe would carry it
-            if (!(black(c0) && black(c1)))
-                if (const char* why = roughness_invalid(d.u_roughness, d.v_roughness, remap)) return invalid(why);
-            m.type = glass ? kMatRoughGlass : kMatSubstrate;
-            m.alpha_u = remap ? roughness_to_alpha(d.u_roughness) : d.u_roughness;
-            m.alpha_v = remap ? roughness_to_alpha(d.v_roughness) : d.v_roughness;
-        }
-    }
+    if (const char* why = row_of_desc(*desc, &m)) return invalid(why);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy((void*)(s->d.materials + material), &m, sizeof(DevMaterial), hipMemcpyHostToDevice));
     s->h_materials[material] = m;
+    s->h_lobe_origin[material] = 0;
     refresh_material_levels(s);
     return PBRT_HIP_OK;
 }
@@ -1522,6 +1456,58 @@ extern "C" int pbrt_hip_scene_set_disney_material(PbrtHipScene* s, int32_t mater
     HIP_TRY(ctx, hipMemcpy((void*)(s->d.disney + material), &z, sizeof(DevDisney), hipMemcpyHostToDevice));
     HIP_TRY(ctx, hipMemcpy((void*)(s->d.materials + material), &m, sizeof(DevMaterial), hipMemcpyHostToDevice));
     s->h_materials[material] = m;
+    s->h_lobe_origin[material] = 0;
+    refresh_material_levels(s);
+    return PBRT_HIP_OK;
+}
+PB_ABI_CATCH
+
+// pbrt-v3's UberMaterial, TranslucentMaterial and MixMaterial (include/pbrt_hip.h): row `material` becomes a
+// kMatLobes row and its DevLobeRow (scene.h) gets the list host_lobes.cpp makes of the descriptor. The shading kernels' lobe-list
+// builds shade it (wf_lobes.h). A mix copies its operands' lists as they are now.
+extern "C" int pbrt_hip_scene_set_lobe_material(PbrtHipScene* s, int32_t material, const PbrtLobeMaterialDesc* desc) try {
+    if (!s) return PBRT_HIP_ERR_INVALID;
+    PbrtHipContext* ctx = s->ctx;
+    PB_ENTER(ctx);
+    auto invalid = [&](const std::string& why) {
+        ctx->last_error = "pbrt_hip_scene_set_lobe_material: " + why;
+        return PBRT_HIP_ERR_INVALID;
+    };
+    if (!desc) return invalid("null desc");
+    if (material < 0 || material >= (int32_t)s->h_materials.size()) return invalid("material index out of range");
+    if (s->d.bvh.has_spheres == 2) return invalid("scenes with general quadric shapes take no lobe rows (their shading builds stay at level 3)");
+    if (s->light_maps) return invalid("scenes with a projection or goniometric light take no lobe rows (their shading builds stay at level 3)");
+    LobeList la, lb, L;
+    if (desc->type == PBRT_LOBEMAT_MIX) {
+        const int32_t ops[2] = {desc->material_a, desc->material_b};
+        LobeList* lists[2] = {&la, &lb};
+        for (int k = 0; k < 2; ++k) {
+            const std::string name = k ? "material_b" : "material_a";
+            if (ops[k] < 0 || ops[k] >= (int32_t)s->h_materials.size()) return invalid(name + " out of range");
+            const DevMaterial& om = s->h_materials[ops[k]];
+            if (om.type == kMatLobes) {
+                if (s->h_lobe_origin[ops[k]] == PBRT_LOBEMAT_MIX) return invalid(name + " is a mix row");
+                const DevLobeRow& r = s->h_lobe_rows[ops[k]];
+                lists[k]->n = r.n;
+                lists[k]->eta = r.eta;
+                for (int i = 0; i < r.n; ++i) lists[k]->lobes[i] = r.lobes[i];
+            } else if (const char* why = lobes_of_row(om, lists[k])) {
+                return invalid(name + ": " + why);
+            }
+        }
+    }
+    if (const char* why = lobes_of_lobe_desc(*desc, &la, &lb, &L)) return invalid(why);
+    const DevLobeRow row = lobe_row_of(L);
+    DevMaterial m{};
+    m.type = kMatLobes;
+    m.eta = L.eta;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy((void*)(s->d.lobe_rows + material), &row, sizeof(DevLobeRow), hipMemcpyHostToDevice));
+    HIP_TRY(ctx, hipMemcpy((void*)(s->d.materials + material), &m, sizeof(DevMaterial), hipMemcpyHostToDevice));
+    s->h_materials[material] = m;
+    s->h_lobe_rows[material] = row;
+    s->h_lobe_origin[material] = desc->type;
     refresh_material_levels(s);
     return PBRT_HIP_OK;
 }

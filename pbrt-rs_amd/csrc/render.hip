@@ -274,6 +274,49 @@ __global__ void k_bsdf_query_disney(const DevDisney* __restrict__ d, int64_t n, 
     o[11] = __int_as_float(sampled);
 }
 
+// the same for a lobe row (wf_lobes.h): BSDF::f and pdf under BSDF_ALL, sample_f under BSDF_ALL, so a specular lobe can be the
+// pick: sampled then carries bit 16 beside a non-zero pdf_s
+__global__ void k_bsdf_query_lobes(const DevLobeRow* __restrict__ row, int64_t n, const float* __restrict__ wo_in, const float* __restrict__ wi_in,
+                                   const float* __restrict__ u_in, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Frame fr;
+    fr.ss = V3{1.0f, 0.0f, 0.0f};
+    fr.ts = V3{0.0f, 1.0f, 0.0f};
+    fr.ns = V3{0.0f, 0.0f, 1.0f};
+    fr.ng = fr.ns;
+    const V3 wo = V3{wo_in[3 * i], wo_in[3 * i + 1], wo_in[3 * i + 2]};
+    const V3 wi = V3{wi_in[3 * i], wi_in[3 * i + 1], wi_in[3 * i + 2]};
+    V3 f, wi_s = V3{0.0f, 0.0f, 0.0f}, f_s = wi_s;
+    float pdf, pdf_s = 0.0f;
+    int sampled = 0;
+    lobes_f_pdf(row, fr, wo, wi, kBxdfAll, &f, &pdf);
+    bool ok;
+    float ps = 0.0f;
+    V3 w;
+    V3 fs = lobes_sample_f(row, fr, wo, u_in[2 * i], u_in[2 * i + 1], kBxdfAll, &w, &ps, &ok, &sampled);
+    if (ok) {
+        wi_s = w;
+        f_s = fs;
+        pdf_s = ps;
+    } else {
+        sampled = 0;
+    }
+    float* o = out + 12 * i;
+    o[0] = f.x;
+    o[1] = f.y;
+    o[2] = f.z;
+    o[3] = pdf;
+    o[4] = wi_s.x;
+    o[5] = wi_s.y;
+    o[6] = wi_s.z;
+    o[7] = f_s.x;
+    o[8] = f_s.y;
+    o[9] = f_s.z;
+    o[10] = pdf_s;
+    o[11] = __int_as_float(sampled);
+}
+
 extern "C" int pbrt_hip_bsdf_query(PbrtHipScene* s, int32_t material, int64_t n, const float* wo, const float* wi, const float* u, float* f,
                                    float* pdf, float* wi_s, float* f_s, float* pdf_s, int32_t* sampled_flags) try {
     if (!s) return PBRT_HIP_ERR_INVALID;
@@ -300,7 +343,10 @@ extern "C" int pbrt_hip_bsdf_query(PbrtHipScene* s, int32_t material, int64_t n,
         rc = PBRT_HIP_ERR_DEVICE;
     std::vector<float> h;
     if (rc == PBRT_HIP_OK) {
-        if (s->h_materials[material].type == kMatDisney)
+        if (s->h_materials[material].type == kMatLobes)
+            hipLaunchKernelGGL(k_bsdf_query_lobes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, s->d.lobe_rows + material, n,
+                               d_in, d_in + 3 * un, d_in + 6 * un, d_out);
+        else if (s->h_materials[material].type == kMatDisney)
             hipLaunchKernelGGL(k_bsdf_query_disney, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, s->d.disney + material, n,
                                d_in, d_in + 3 * un, d_in + 6 * un, d_out);
         else
@@ -355,6 +401,7 @@ static void scene_shade_consts(const PbrtHipScene* s, ShadeConsts* out) {
     sc.mis_bool = s->ctx->count_traversal != 1 ? 1 : 0;  // wf_state.h: RS_MIS_BOOL
     sc.disney = s->d.disney;
     sc.light_maps = s->d.light_maps;
+    sc.lobe_rows = s->d.lobe_rows;
 }
 
 // Light::sample_li (light.rs:35-42) of one light of the scene from bare interactions at the world points p (normal and error
@@ -1215,7 +1262,7 @@ void RenderJob::shade_wavefront(const PassParams& pp, int cur, int nxt, uint32_t
         hipLaunchKernelGGL(k_shade_sort_keys, dim3((n_shade + 255) / 256), dim3(256), 0, st, sc, ps, q[cur].shade, n_shade, pp.max_depth,
                            ss.keys[0], shade_positions);
         size_t tb = ss.tmp_bytes;
-        if (pb::sort_pairs_u32(st, ss.tmp, &tb, ss.keys[0], ss.keys[1], shade_positions, ss.vals, n_shade, (s->bxdfs || s->disney) ? 4 : 3) != 0 &&
+        if (pb::sort_pairs_u32(st, ss.tmp, &tb, ss.keys[0], ss.keys[1], shade_positions, ss.vals, n_shade, (s->bxdfs || s->disney || s->lobes) ? 4 : 3) != 0 &&
             rc == PBRT_HIP_OK) {
             ctx->last_error = "rocPRIM radix sort failed";
             rc = PBRT_HIP_ERR_DEVICE;

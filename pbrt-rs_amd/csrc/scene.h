@@ -128,6 +128,20 @@ struct DevDisney {
     int sep_trans;       // the transmission lobe masks with G1(wo) G1(wi) (not thin)
 };
 
+// kMatLobes: a row of pbrt_hip_scene_set_lobe_material (wf_lobes.h): the reference's general BSDF, a list of up to 8 lobes of any
+// kind matched by BxDFType flags. The DevMaterial row keeps the BSDF's eta; the list is the DevLobeRow of the same index in
+// DevSceneData::lobe_rows, written by the host (host_lobes.cpp). A lobe is the public PbrtLobe (include/pbrt_hip.h).
+constexpr int kMatLobes = 10;
+constexpr int kMaxLobes = 8;
+typedef PbrtLobe DevLobe;
+struct DevLobeRow {
+    int n;            // 0..8
+    float eta;        // BSDF::eta
+    int n_nonspec;    // num_components(BSDF_ALL & !BSDF_SPECULAR)
+    int type_or;      // the lobes' BxDFType bits or-ed
+    DevLobe lobes[kMaxLobes];
+};
+
 // Distribution1D (src/core/sampling.rs:62-154) flattened: func[n], cdf[n+1]
 struct DevDistribution1D {
     const float* func;
@@ -178,6 +192,7 @@ struct DevSceneData {
     const DevEnvMap* env_maps;  // [n_lights] once a map was set (DevLight::slot names the entry), else null
     const DevDisney* disney;    // [n_materials]: the blocks of the kMatDisney rows
     const DevLightMap* light_maps;  // [n_lights] when the scene holds a projection or goniometric light, else null
+    const DevLobeRow* lobe_rows;    // [n_materials]: the lists of the kMatLobes rows
 };
 
 }  // namespace pb
@@ -193,6 +208,9 @@ struct PbrtHipScene {
     bool glossy = false;  // a plastic or metal material in the table: the shading kernels' glossy instantiations run
     bool bxdfs = false;   // a kMatOrenNayar / kMatRoughGlass / kMatSubstrate row in the table: their level-2 instantiations run
     bool disney = false;  // a kMatDisney row in the table: their level-3 instantiations run
+    bool lobes = false;   // a kMatLobes row in the table: the shading kernels' lobe-list builds run
+    std::vector<pb::DevLobeRow> h_lobe_rows;  // the device table's host copy: a mix reads its operands' lists
+    std::vector<int> h_lobe_origin;           // per row: the PbrtLobeMaterialType that wrote it, 0 for any other row
     bool light_maps = false;  // a projection or goniometric light in the table: the shading kernels' map-light builds run
     std::vector<pb::DevLightMap> h_light_maps;  // the device table's host copy
     std::vector<void*> light_map_allocs;         // per light: its texels on the device (pbrt_hip_scene_set_light_map) or null

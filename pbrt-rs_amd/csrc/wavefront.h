@@ -19,6 +19,7 @@
 #include "wf_generate_trace.h"
 #include "wf_surface.h"
 #include "wf_lights.h"
+#include "wf_lobes.h"
 #include "wf_path.h"
 #include "wf_direct.h"
 #include "wf_film.h"

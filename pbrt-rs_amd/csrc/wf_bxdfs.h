@@ -27,15 +27,16 @@ PB_DEV V3 oren_nayar_f(V3 r, float a, float b, V3 wo, V3 wi) {
     return r * kInvPi * (a + b * max_cos * sin_alpha * tan_beta);
 }
 
-// MicrofacetReflection::f (reflection.rs:1000-1018) with FresnelDielectric(1, eta): the reflection lobe of rough glass
-PB_DEV V3 glass_reflection_f(V3 r, float ax, float ay, float eta, V3 wo, V3 wi) {
+// MicrofacetReflection::f (reflection.rs:1000-1018) with FresnelDielectric(eta_i, eta): (1, eta) is the reflection lobe of rough
+// glass and of uber, (1.5, 1) plastic's in a lobe list (wf_lobes.h)
+PB_DEV V3 glass_reflection_f(V3 r, float ax, float ay, float eta, V3 wo, V3 wi, float eta_i = 1.0f) {
     V3 zero = V3{0.0f, 0.0f, 0.0f};
     float cos_o = __builtin_fabsf(wo.z), cos_i = __builtin_fabsf(wi.z);
     V3 wh = wi + wo;
     if (cos_i == 0.0f || cos_o == 0.0f) return zero;
     if (wh.x == 0.0f && wh.y == 0.0f && wh.z == 0.0f) return zero;
     wh = normalize(wh);
-    float F = fr_dielectric(dot(wi, faceforward(wh, V3{0.0f, 0.0f, 1.0f})), 1.0f, eta);
+    float F = fr_dielectric(dot(wi, faceforward(wh, V3{0.0f, 0.0f, 1.0f})), eta_i, eta);
     return r * tr_d(wh, ax, ay) * tr_g(wo, wi, ax, ay) * F / (4.0f * cos_i * cos_o);
 }
 // MicrofacetReflection::pdf (reflection.rs:1045-1051)

@@ -34,13 +34,17 @@ struct DirectState {
 // body shared through a wrapper: that moved the registers of three of the instantiations for the other scenes.)
 // + 8 in the builds for scenes with a projection or goniometric light (ML as light_sample_li's): <DIRECT, 11> and <WHITTED, 11>;
 // the builds for shapes take ML too. AO samples no light.
-constexpr int kDirectShapes = 4, kDirectMapLights = 8;
+// + 16 in the builds for scenes with a lobe row (wf_lobes.h): <DIRECT, 19> and <WHITTED, 19>, the level-3 set plus the lobe lists.
+// Both run one wave per SIMD: at two the Whitted build spills 104 bytes (profiles/r12_lobe_materials.txt).
+constexpr int kDirectShapes = 4, kDirectMapLights = 8, kDirectLobes = 16;
 template <int MODE, int LEVEL_SHP>
-__global__ void __launch_bounds__(256, ((LEVEL_SHP & 3) >= 1 && MODE == PBRT_INTEGRATOR_DIRECT) ? 1 : PB_DIRECT_WAVES) k_shade_direct(ShadeConsts sc, PathState ps, DirectState ds, Queues qin,
+__global__ void __launch_bounds__(256, (((LEVEL_SHP & 3) >= 1 && MODE == PBRT_INTEGRATOR_DIRECT) || (LEVEL_SHP & 16)) ? 1 : PB_DIRECT_WAVES) k_shade_direct(ShadeConsts sc, PathState ps, DirectState ds, Queues qin,
                                                         Queues qout, PassParams pp, TileList tiles, uint32_t n_in) {
     constexpr int LEVEL = LEVEL_SHP & 3;
     constexpr bool SHP = (LEVEL_SHP & kDirectShapes) != 0;
     constexpr bool ML = SHP || (LEVEL_SHP & kDirectMapLights) != 0;
+    constexpr bool LOBES = (LEVEL_SHP & kDirectLobes) != 0;
+    constexpr int BL = LOBES ? 4 : LEVEL;  // the BSDF type: LevelBsdf<BL>
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool active = i < n_in;
     uint32_t p = active ? qin.shade[i] : 0u;
@@ -218,7 +222,7 @@ __global__ void __launch_bounds__(256, ((LEVEL_SHP & 3) >= 1 && MODE == PBRT_INT
                 V3 f = V3{0.0f, 0.0f, 0.0f};
                 float spdf;
                 if (GLOSSY) {
-                    typename LevelBsdf<LEVEL>::type nsb;
+                    typename LevelBsdf<BL>::type nsb;
                     load_bsdf(sc, sf.material, sc.materials[sf.material], &nsb);  // read again here: keeps the alphas out of the loop's registers
                     if (nsb.n > 0) bsdf_f_pdf(nsb, fr, sf.wo, wi, &f, &spdf);  // BSDF::f, all lobes
                 } else if (mat.type == PBRT_MAT_MATTE && !is_black(kd)) {
@@ -262,7 +266,7 @@ __global__ void __launch_bounds__(256, ((LEVEL_SHP & 3) >= 1 && MODE == PBRT_INT
                 }
                 int nee_flags;
                 if (GLOSSY) {
-                    typename LevelBsdf<LEVEL>::type nsb;
+                    typename LevelBsdf<BL>::type nsb;
                     load_bsdf(sc, sf.material, sc.materials[sf.material], &nsb);
                     nee_flags = estimate_direct_emit<SHP, ML>(sc, RecordSink{ps, p}, sf, fr, nsb.n > 0, nsb, light_num, ul0, ul1, us0, us1, pick_pdf, T);
                 } else {
@@ -293,14 +297,40 @@ __global__ void __launch_bounds__(256, ((LEVEL_SHP & 3) >= 1 && MODE == PBRT_INT
                     // BSDF::sample_f with type = REFLECTION|SPECULAR or TRANSMISSION|SPECULAR (one matching lobe)
                     bool lobe = (mat.type == PBRT_MAT_MIRROR && which == 1 && !is_black(kd)) ||
                                 (mat.type == PBRT_MAT_GLASS && ((which == 1 && !is_black(kd)) || (which == 2 && !is_black(kt))));
+                    // ... over a lobe row's list: there may be several matching lobes (uber with opacity < 1 and Kt has two
+                    // transmissive ones). Written around the older statements, which stay as they were for every other build.
+                    bool lobe_row = false;
+                    V3 lobe_f_s = V3{0, 0, 0}, lobe_wi = V3{0, 0, 0};
+                    float lobe_pdf_s = 0.0f;
+                    if constexpr (LOBES) {
+                        if (mat.type == kMatLobes) {
+                            bool ok;
+                            int sampled;
+                            lobe_row = true;
+                            lobe_f_s = lobes_sample_f(sc.lobe_rows + sf.material, fr, sf.wo, u0, u1,
+                                                      (which == 1 ? kBxdfReflection : kBxdfTransmission) | kBxdfSpecular, &lobe_wi, &lobe_pdf_s,
+                                                      &ok, &sampled);
+                            if (!ok) lobe_pdf_s = 0.0f;
+                            lobe = lobe_pdf_s != 0.0f;
+                        }
+                    }
                     if (!lobe || wol.z == 0.0f) continue;
                     float ur = fminr(u0 * 1.0f - 0.0f, kOneMinusEpsilon);
                     V3 wil = V3{0, 0, 0};
                     float pdf;
                     bool tr;
                     V3 f = sample_specular_local(mat, kd, kt, wol, ur, which, &wil, &pdf, &tr);
+                    if constexpr (LOBES) {
+                        if (lobe_row) {
+                            f = lobe_f_s;
+                            pdf = lobe_pdf_s;
+                        }
+                    }
                     if (pdf == 0.0f) continue;
                     V3 wi = to_world(fr, wil);
+                    if constexpr (LOBES) {
+                        if (lobe_row) wi = lobe_wi;
+                    }
                     float ad = absdot(wi, fr.ns);
                     if (!(pdf > 0.0f && !is_black(f) && ad != 0.0f)) continue;  // integrator.rs:316
                     if (which == 1) {

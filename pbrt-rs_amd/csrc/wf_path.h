@@ -42,8 +42,9 @@ __global__ void k_shade_sort_keys(ShadeConsts sc, PathState ps, const uint32_t* 
 }
 
 // keys: 0 nothing to shade, 1 + DevMaterial::type (none, matte, mirror, glass; level 1: plastic, metal as well; level 2: the
-// three kinds of set_material rows as well; level 3: Disney rows as well), the last = no queue entry (block tail)
-constexpr int shade_keys(int level) { return level == 3 ? 12 : level == 2 ? 11 : level == 1 ? 8 : 6; }
+// three kinds of set_material rows as well; level 3: Disney rows as well; level 4: lobe rows as well), the last = no queue entry
+// (block tail)
+constexpr int shade_keys(int level) { return level == 4 ? 13 : level == 3 ? 12 : level == 2 ? 11 : level == 1 ? 8 : 6; }
 template <int KEYS>
 struct ShadeBins {
     uint32_t count[4][KEYS];  // per wave of the block, per key
@@ -60,7 +61,8 @@ struct ShadeBins {
 // glossy transmission, FresnelBlend: GenBsdf, wf_bxdfs.h), the rows of level 1 through the functions of level 1. Level 2
 // fits the same launch bounds without scratch: 162 / 164 VGPRs (profiles/r08_bxdf_set.txt). 3: a Disney row as well (DisneyBsdf,
 // wf_disney.h). At three waves per SIMD the binned level 3 spills 12 bytes, so level 3 alone is bounded at two
-// (profiles/r09_disney.txt).
+// (profiles/r09_disney.txt). 4: a lobe row as well (LobeBsdf, wf_lobes.h: a list of specular and non-specular lobes matched by
+// flags); only k_shade_lobes below is built at it, and the rows of every other kind go through level 3's code there.
 // Thread i takes the shade-queue entry at position rec = i (order: rec = order[i], the queue in material order): the path
 // p = qin.shade[rec] with its persistent state at p, and the transient records of this generation at rec. What the path
 // hands to the next launch is staged in LDS and written to the next generation at its position in qout.shade.
@@ -71,6 +73,7 @@ template <bool BIN, int LEVEL, bool SHP, bool ML = false>
 PB_DEV void shade_bounce(const ShadeConsts& sc, const PathState& ps, const Queues& qin, const Queues& qout, const PassParams& pp,
                          const TileList& tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
     constexpr bool GLOSSY = LEVEL >= 1;
+    constexpr bool LOBES = LEVEL == 4;
     constexpr int kShadeKeys = shade_keys(LEVEL);
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool active = i < n_in;
@@ -175,6 +178,8 @@ PB_DEV void shade_bounce(const ShadeConsts& sc, const PathState& ps, const Queue
                         if (mat.type == PBRT_MAT_GLASS) has_lobe = !(is_black(kd) && is_black(kt));
                         else if (mat.type == PBRT_MAT_MIRROR) has_lobe = !is_black(kd);
                         else has_lobe = nonspecular;
+                        if constexpr (LOBES)
+                            if (nsb.row) has_lobe = nsb.row->n > 0;  // nonspecular: num_components(BSDF_ALL & !BSDF_SPECULAR) > 0
                     } else {
                         if (mat.type == PBRT_MAT_GLASS) has_lobe = !(is_black(kd) && is_black(kt));
                         else has_lobe = !is_black(kd);
@@ -209,7 +214,19 @@ PB_DEV void shade_bounce(const ShadeConsts& sc, const PathState& ps, const Queue
                     V3 wi = V3{0.0f, 0.0f, 0.0f}, f = V3{0.0f, 0.0f, 0.0f};
                     float pdf = 0.0f;
                     bool sampled_specular = false, sampled_transmission = false;
-                    if (has_lobe) {
+                    bool lobe_row = false;
+                    if constexpr (LOBES) lobe_row = nsb.row != nullptr;
+                    if (lobe_row) {
+                        // BSDF::sample_f(BSDF_ALL) over the row's list: the flag and eta_scale follow the SAMPLED lobe's type
+                        if constexpr (LOBES) {
+                            bool ok;
+                            int sampled = 0;
+                            f = lobes_sample_f(nsb.row, fr, wo, u0, u1, kBxdfAll, &wi, &pdf, &ok, &sampled);
+                            if (!ok) pdf = 0.0f;
+                            sampled_specular = ok && (sampled & kBxdfSpecular) != 0;
+                            sampled_transmission = ok && (sampled & kBxdfTransmission) != 0;
+                        }
+                    } else if (has_lobe) {
                         if (GLOSSY && nonspecular) {  // glossy lobes, transmission included: not specular, PF_SPECULAR_BOUNCE stays clear
                             bool ok;
                             f = bsdf_sample_f(nsb, fr, wo, u0, u1, &wi, &pdf, &ok);
@@ -234,7 +251,7 @@ PB_DEV void shade_bounce(const ShadeConsts& sc, const PathState& ps, const Queue
                         beta = mulv(beta, f * (absdot(wi, fr.ns) / pdf));
                         flags = (flags & ~PF_SPECULAR_BOUNCE) | (sampled_specular ? PF_SPECULAR_BOUNCE : 0);
                         if (sampled_specular && sampled_transmission) {
-                            float eta = mat.eta;
+                            float eta = mat.eta;  // a lobe row's DevMaterial::eta is its BSDF's eta
                             eta_scale *= (dot(wo, sf.n) > 0.0f) ? (eta * eta) : 1.0f / (eta * eta);
                         }
                         V3 o = offset_ray_origin(sf.p, sf.p_error, sf.n, wi);
@@ -285,6 +302,13 @@ template <bool BIN>
 __global__ void __launch_bounds__(256, 2) k_shade_maps(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
                                                       TileList tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
     shade_bounce<BIN, 3, false, true>(sc, ps, qin, qout, pp, tiles, n_in, order);
+}
+// scenes with a lobe row (pbrt_hip_scene_set_lobe_material): level 4 only. Bounded at two waves per SIMD as level 3 is: the
+// lobe loop's live state comes on top of level 3's, which spills at three (profiles/r12_lobe_materials.txt).
+template <bool BIN>
+__global__ void __launch_bounds__(256, 2) k_shade_lobes(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
+                                                       TileList tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
+    shade_bounce<BIN, 4, false, false>(sc, ps, qin, qout, pp, tiles, n_in, order);
 }
 
 }  // namespace pb

@@ -415,6 +415,7 @@ struct ShadeConsts {
     int mis_bool;
     const DevDisney* disney;  // [n_materials]: the blocks of the kMatDisney rows (wf_disney.h)
     const DevLightMap* light_maps;  // side table of the projection / goniometric lights (DevLight::slot), null when there are none
+    const DevLobeRow* lobe_rows;  // [n_materials]: the lobe lists of the kMatLobes rows (wf_lobes.h)
 };
 
 // ---- InfiniteAreaLight with an image map (DevEnvMap): one lookup and one Distribution2D for le, sample_li and pdf_li ----

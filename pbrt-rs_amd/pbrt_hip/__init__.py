@@ -43,6 +43,7 @@ EXPORTS = [
     "pbrt_hip_scene_set_material", "pbrt_hip_scene_set_disney_material",
     "pbrt_hip_shape_world_bounds", "pbrt_hip_scene_create_with_shapes",
     "pbrt_hip_scene_set_light_map", "pbrt_hip_light_map_tables", "pbrt_hip_light_sample_li",
+    "pbrt_hip_scene_set_lobe_material", "pbrt_hip_material_lobes",
 ]
 MAT_NONE, MAT_MATTE, MAT_MIRROR, MAT_GLASS, MAT_PLASTIC, MAT_METAL = (scenes.MAT_NONE, scenes.MAT_MATTE, scenes.MAT_MIRROR,
                                                                       scenes.MAT_GLASS, scenes.MAT_PLASTIC, scenes.MAT_METAL)
@@ -88,6 +89,35 @@ class MaterialDesc(ctypes.Structure):
 class DisneyDesc(ctypes.Structure):
     """PbrtDisneyDesc (pbrt_hip_scene_set_disney_material); scenes.disney gives the keyword form"""
     _fields_ = [("color", ctypes.c_float * 3)] + [(k, ctypes.c_float) for k in scenes.DISNEY_SCALARS] + [("thin", ctypes.c_int32)]
+
+
+_LOBE_COLOURS = ("kd", "ks", "kr", "kt", "opacity", "reflect", "transmit", "amount")
+
+
+class LobeMaterialDesc(ctypes.Structure):
+    """PbrtLobeMaterialDesc (pbrt_hip_scene_set_lobe_material); scenes.uber / translucent / mix give the keyword form"""
+    _fields_ = ([("type", ctypes.c_int32)] + [(k, ctypes.c_float * 3) for k in _LOBE_COLOURS] +
+                [("eta", ctypes.c_float), ("u_roughness", ctypes.c_float), ("v_roughness", ctypes.c_float),
+                 ("remap_roughness", ctypes.c_int32), ("material_a", ctypes.c_int32), ("material_b", ctypes.c_int32)])
+
+
+class Lobe(ctypes.Structure):
+    """PbrtLobe: one lobe of a list (pbrt_hip_material_lobes)"""
+    _fields_ = [("kind", ctypes.c_int32), ("type", ctypes.c_int32), ("fresnel", ctypes.c_int32), ("scale", ctypes.c_float * 3),
+                ("r", ctypes.c_float * 3), ("s", ctypes.c_float * 3), ("ax", ctypes.c_float), ("ay", ctypes.c_float),
+                ("eta_i", ctypes.c_float), ("eta_t", ctypes.c_float), ("eta", ctypes.c_float * 3), ("k", ctypes.c_float * 3),
+                ("A", ctypes.c_float), ("B", ctypes.c_float)]
+
+
+def _struct_from(cls, desc, colours):
+    if desc is None or isinstance(desc, cls):
+        return desc
+    d = cls()
+    for k, v in desc.items():
+        if k in ("lobe", "row"):  # scenes.py's marks of the descriptor's kind
+            continue
+        setattr(d, k, (ctypes.c_float * 3)(*[float(c) for c in v]) if k in colours else v)
+    return d
 
 
 class PbrtHipError(RuntimeError):
@@ -190,6 +220,9 @@ def lib():
         L.pbrt_hip_light_map_tables.argtypes = [i32, ctypes.c_float, vp, i32, i32, ctypes.POINTER(i32), ctypes.POINTER(i32), vp, vp, vp,
                                                 ctypes.POINTER(ctypes.c_float), vp, ctypes.POINTER(ctypes.c_char_p)]
         L.pbrt_hip_light_sample_li.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp]
+        L.pbrt_hip_scene_set_lobe_material.argtypes = [vp, i32, vp]
+        L.pbrt_hip_material_lobes.argtypes = [vp, vp, vp, vp, i32, ctypes.c_float, vp, i32, vp, ctypes.POINTER(i32),
+                                              ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_char_p)]
         _lib = L
     return _lib
 
@@ -417,6 +450,8 @@ class Scene:
         self.build_ms / self.layout_ms then hold the HIP-event times and self.nodes is None.
         scene["material_descs"] = {row: descriptor} (optional): set_material(row, descriptor) after creation;
         scene["disney_descs"] = {row: descriptor} (optional): set_disney_material(row, descriptor) after that;
+        scene["lobe_descs"] = {row: descriptor} (optional): set_lobe_material(row, descriptor) after that, in insertion order,
+        so a mix's operands come first;
         scene["light_maps"] = {light: rgb} (optional): set_light_map(light, rgb) after that."""
         self._create(ctx, scene, max_prims_in_node, split_method, bvh, device_build)
         try:
@@ -424,6 +459,8 @@ class Scene:
                 self.set_material(row, desc)
             for row, desc in (scene.get("disney_descs") or {}).items():
                 self.set_disney_material(row, desc)
+            for row, desc in (scene.get("lobe_descs") or {}).items():
+                self.set_lobe_material(row, desc)
             for light, rgb in (scene.get("light_maps") or {}).items():
                 self.set_light_map(light, rgb)
         except Exception:
@@ -764,6 +801,14 @@ class Scene:
         self.ctx.check(lib().pbrt_hip_scene_set_disney_material(self.h, int(m), None if desc is None else ctypes.byref(desc)),
                        "pbrt_hip_scene_set_disney_material")
 
+    def set_lobe_material(self, m, desc):
+        """Replaces row m of the material table by a lobe list: scenes.uber(), scenes.translucent() or scenes.mix() (a dict of
+        PbrtLobeMaterialDesc's fields) or a LobeMaterialDesc (pbrt_hip_scene_set_lobe_material). A mix copies its operand rows'
+        lists as they are at the time of the call."""
+        desc = _struct_from(LobeMaterialDesc, desc, _LOBE_COLOURS)
+        self.ctx.check(lib().pbrt_hip_scene_set_lobe_material(self.h, int(m), None if desc is None else ctypes.byref(desc)),
+                       "pbrt_hip_scene_set_lobe_material")
+
     def bsdf_query(self, material, wo, wi, u):
         """BSDF::f / pdf / sample_f of a material on the device, in the shading frame (n = +z): wo, wi (n, 3), u (n, 2).
         Returns dict f (n, 3), pdf (n,), wi_s (n, 3), f_s (n, 3), pdf_s (n,), flags (n,) int32 BxDFType of the sampled lobe."""
@@ -970,6 +1015,58 @@ def envmap_tables(rgb, L=(1.0, 1.0, 1.0)):
     if rc != 0:
         raise PbrtHipError(f"pbrt_hip_envmap_tables failed ({rc}): {(why.value or b'').decode()}")
     return level0, func, power
+
+
+_LOBE_FIELDS = [k for k, _ in Lobe._fields_]
+
+
+def material_lobes(desc, a=None, b=None):
+    """pbrt_hip_material_lobes: (lobes, eta), the lobe list and BSDF eta of a row description, on the host, without a context.
+    desc: scenes.material_row (a PbrtMaterial row), scenes.matte_sigma / rough_glass / substrate (a PbrtMaterialDesc) or
+    scenes.uber / translucent / mix (a PbrtLobeMaterialDesc). For a mix, a and b are the operands' (lobes, eta) as this function returns them. Each lobe is a dict of
+    PbrtLobe's fields, colours as tuples of float32. Raises PbrtHipError with the library's reason for a refused description."""
+    row = mdesc = ldesc = None
+    if desc.get("row"):
+        m = np.zeros(1, dtype=MATERIAL_DTYPE)
+        m["type"] = desc["type"]
+        m["kd"] = desc.get("kd", (0, 0, 0))
+        m["kt"] = desc.get("kt", (0, 0, 0))
+        m["eta"] = desc.get("eta", 0.0)
+        row = m
+    elif desc.get("lobe"):
+        ldesc = _struct_from(LobeMaterialDesc, desc, _LOBE_COLOURS)
+    else:
+        mdesc = _struct_from(MaterialDesc, desc, ("kd", "ks", "kr", "kt"))
+
+    def operand(x):
+        if x is None:
+            return None, 0, 1.0
+        lobes, eta = x
+        arr = (Lobe * max(1, len(lobes)))()
+        for i, l in enumerate(lobes):
+            for k in _LOBE_FIELDS:
+                v = l[k]
+                setattr(arr[i], k, (ctypes.c_float * 3)(*v) if isinstance(v, tuple) else v)
+        return arr, len(lobes), float(eta)
+
+    (la, na, ea), (lb, nb, _) = operand(a), operand(b)
+    out = (Lobe * 8)()
+    n, eta, why = ctypes.c_int32(), ctypes.c_float(), ctypes.c_char_p()
+    rc = lib().pbrt_hip_material_lobes(_p(row), None if mdesc is None else ctypes.addressof(mdesc),
+                                       None if ldesc is None else ctypes.addressof(ldesc),
+                                       None if la is None else ctypes.addressof(la), na, ea,
+                                       None if lb is None else ctypes.addressof(lb), nb, ctypes.addressof(out), ctypes.byref(n),
+                                       ctypes.byref(eta), ctypes.byref(why))
+    if rc != 0:
+        raise PbrtHipError(f"pbrt_hip_material_lobes failed ({rc}): {(why.value or b'').decode()}")
+    lobes = []
+    for i in range(n.value):
+        l = {}
+        for k in _LOBE_FIELDS:
+            v = getattr(out[i], k)
+            l[k] = tuple(np.float32(c) for c in v) if hasattr(v, "__len__") else (np.float32(v) if isinstance(v, float) else v)
+        lobes.append(l)
+    return lobes, np.float32(eta.value)
 
 
 def light_map_tables(light_type, rgb=None, fov=0.0):

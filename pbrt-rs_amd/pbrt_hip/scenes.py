@@ -125,6 +125,42 @@ def disney(color, metallic=0.0, eta=1.5, roughness=0.5, specular_tint=0.0, aniso
                 diff_trans=float(diff_trans), thin=int(bool(thin)))
 
 
+LOBEMAT_UBER, LOBEMAT_TRANSLUCENT, LOBEMAT_MIX = 1, 2, 3  # PbrtLobeMaterialType
+# PbrtLobeKind and PbrtLobeFresnel (pbrt_hip.material_lobes)
+(LOBE_LAMBERTIAN_REFLECTION, LOBE_LAMBERTIAN_TRANSMISSION, LOBE_OREN_NAYAR, LOBE_SPECULAR_REFLECTION, LOBE_SPECULAR_TRANSMISSION,
+ LOBE_MICROFACET_REFLECTION, LOBE_MICROFACET_TRANSMISSION, LOBE_FRESNEL_BLEND) = range(1, 9)
+FRESNEL_NOOP, FRESNEL_DIELECTRIC, FRESNEL_CONDUCTOR = 0, 1, 2
+
+
+def _rgb(c):
+    """a colour given as a number or as three"""
+    return (float(c),) * 3 if np.isscalar(c) else tuple(float(v) for v in c)
+
+
+def uber(kd=0.25, ks=0.25, kr=0.0, kt=0.0, opacity=1.0, eta=1.5, u_roughness=0.1, v_roughness=0.1, remap=True):
+    """Descriptor (Scene.set_lobe_material, scene["lobe_descs"], pbrt_hip.material_lobes) of pbrt-v3's UberMaterial with its
+    defaults; colours are numbers or RGB triples. "lobe" marks the descriptor's kind, it is not a field."""
+    return dict(lobe=True, type=LOBEMAT_UBER, kd=_rgb(kd), ks=_rgb(ks), kr=_rgb(kr), kt=_rgb(kt), opacity=_rgb(opacity), eta=float(eta),
+                u_roughness=float(u_roughness), v_roughness=float(v_roughness), remap_roughness=int(bool(remap)))
+
+
+def translucent(kd=0.25, ks=0.25, reflect=0.5, transmit=0.5, roughness=0.1, remap=True):
+    """Descriptor of pbrt-v3's TranslucentMaterial with its defaults (isotropic; the BSDF's eta is 1.5)."""
+    return dict(lobe=True, type=LOBEMAT_TRANSLUCENT, kd=_rgb(kd), ks=_rgb(ks), reflect=_rgb(reflect), transmit=_rgb(transmit),
+                u_roughness=float(roughness), v_roughness=float(roughness), remap_roughness=int(bool(remap)))
+
+
+def mix(row_a, row_b, amount=0.5):
+    """Descriptor of pbrt-v3's MixMaterial over two rows of the same scene: amount of a, 1 - amount of b. The rows' lobe lists
+    are copied when the descriptor is set."""
+    return dict(lobe=True, type=LOBEMAT_MIX, material_a=int(row_a), material_b=int(row_b), amount=_rgb(amount))
+
+
+def material_row(type, kd=(0, 0, 0), kt=(0, 0, 0), eta=0.0):
+    """A PbrtMaterial row as pbrt_hip.material_lobes takes it ("row" marks the kind)"""
+    return dict(row=True, type=int(type), kd=_rgb(kd), kt=_rgb(kt), eta=float(eta))
+
+
 def disney_invalid(desc):
     """Why pbrt_hip_scene_set_disney_material refuses the descriptor (the same rules, checked before the call), or None"""
     if desc is None:

@@ -106,6 +106,9 @@ PB_DEV bool quadric_disk_test(const DevShape& sh, const SphereRay& q, float tmax
     V3 ph = V3{q.ox + q.dx * t, q.oy + q.dy * t, q.oz + q.dz * t};
     float dist2 = ph.x * ph.x + ph.y * ph.y;
     if (dist2 > sh.radius * sh.radius || dist2 < sh.inner_radius * sh.inner_radius) return false;
+    // the centre (a ray down the axis): dpdv = p (r_i - r) / |p| is 0 / 0 there (disk.rs:98-101 divides all the same); the
+    // sphere's nudge at its pole, so that the hit keeps the tangent of phi = 0 (D94). No other hit's bits change.
+    if (ph.x == 0.0f && ph.y == 0.0f) ph.x = 1e-5f * sh.radius;
     float phi = det_atan2(ph.y, ph.x);
     if (phi < 0.0f) phi += 2.0f * kPi;
     if (phi > sh.phi_max) return false;

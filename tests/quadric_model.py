@@ -98,7 +98,9 @@ def _near_phi(shape, phi):
 
 def intersect(shape, o, d, t_max=np.inf):
     """o, d: (n, 3) world-space rays (d need not be normalised); t_max: scalar or (n,). Returns a dict of arrays:
-    hit (bool), t, p (object-space hit point), phi, n (world-space unit normal as the shading code orients it), near."""
+    hit (bool), t, p (object-space hit point), phi, n (world-space unit normal as the shading code orients it), near.
+    A ray exactly down the axis of a disk with inner_radius 0 hits its centre: p = (0, 0, height), phi = 0, not `near` on account
+    of the sweep (surface_frame gives that hit the tangent of phi = 0)."""
     o, d = np.asarray(o, dtype=np.float64), np.asarray(d, dtype=np.float64)
     n_rays = o.shape[0]
     t_max = np.broadcast_to(np.asarray(t_max, dtype=np.float64), (n_rays,))
@@ -126,11 +128,15 @@ def intersect(shape, o, d, t_max=np.inf):
             near |= (dz != 0.0) & near_t(t)
             p = oo + dd * np.where(ok, t, 0.0)[:, None]
             rho = np.sqrt(p[:, 0] ** 2 + p[:, 1] ** 2)
+            on_axis = rho <= 1e-12 * r  # a ray down the axis, up to float64's own rounding through the transform
+            p[on_axis, :2], rho[on_axis] = 0.0, 0.0
             inside = (rho <= r) & (rho >= shape["inner_radius"])
             near |= ok & ((np.abs(rho - r) <= REL * r) |
                           ((shape["inner_radius"] > 0.0) & (np.abs(rho - shape["inner_radius"]) <= REL * shape["inner_radius"])))
             phi = _phi(p)
-            near |= ok & inside & _near_phi(shape, phi)
+            # the centre (rho == 0: a ray down the axis) belongs to every sector and is no boundary of the sweep: the
+            # hit is taken there with phi = 0, the device's too (it nudges the point to x = 1e-5 r as the sphere's pole)
+            near |= ok & inside & (rho > 0.0) & _near_phi(shape, phi)
             hit = ok & inside & (phi <= shape["phi_max"])
             t_hit = np.where(hit, t, np.inf)
             p_hit = p
@@ -168,20 +174,61 @@ def intersect(shape, o, d, t_max=np.inf):
                 p_hit = np.where(accept[:, None], p, p_hit)
                 hit |= accept
                 pending &= ~accept
-    # the normal: normalize(dpdu x dpdv) points outward for the sphere and the cylinder, along +z for the disk; flipped by
-    # reverse_orientation ^ transform_swaps_handedness; to world space by the inverse transpose
+    return dict(hit=hit, t=t_hit, p=p_hit, phi=_phi(p_hit), n=np.where(hit[:, None], normal_at(shape, p_hit), 0.0), near=near)
+
+
+def normal_at(shape, p_obj):
+    """The world-space unit normal at the object-space points p_obj (n, 3) as the shading code orients it:
+    normalize(dpdu x dpdv) points outward for the sphere and the cylinder, along +z for the disk; flipped by
+    reverse_orientation ^ transform_swaps_handedness; to world space by the inverse transpose."""
+    p_obj = np.asarray(p_obj, dtype=np.float64)
+    r, kind = shape["radius"], shape["type"]
     if kind == "sphere":
-        n_obj = p_hit / r
+        n_obj = p_obj / r
     elif kind == "cylinder":
-        n_obj = np.stack([p_hit[:, 0], p_hit[:, 1], np.zeros(n_rays)], axis=1) / r
+        n_obj = np.stack([p_obj[:, 0], p_obj[:, 1], np.zeros(len(p_obj))], axis=1) / r
     else:
-        n_obj = np.tile(np.array([0.0, 0.0, 1.0]), (n_rays, 1))
+        n_obj = np.tile(np.array([0.0, 0.0, 1.0]), (len(p_obj), 1))
     if shape["reverse"] != bool(swaps_handedness(shape)):
         n_obj = -n_obj
-    n_w = n_obj @ w2o[:3, :3]  # (M^-1)^T n
+    n_w = n_obj @ np.linalg.inv(shape["o2w"])[:3, :3]  # (M^-1)^T n
     with np.errstate(divide="ignore", invalid="ignore"):
-        n_w = n_w / np.sqrt((n_w ** 2).sum(axis=1))[:, None]
-    return dict(hit=hit, t=t_hit, p=p_hit, phi=_phi(p_hit), n=np.where(hit[:, None], n_w, 0.0), near=near)
+        return n_w / np.sqrt((n_w ** 2).sum(axis=1))[:, None]
+
+
+AXIS_NUDGE = 1e-5  # times the radius: where the device puts a hit on a sphere's pole or a disk's centre (phi = 0)
+
+
+def surface_frame(shape, hit):
+    """The shading frame at the hits of intersect() (every row; rows that missed hold zeros and NaNs). World space, float64:
+    dpdu = M dpdu_obj with dpdu_obj = (-phi_max y, phi_max x, 0) at the object-space hit point (the derivative of the
+    parametrisation by u: phi = u phi_max) and M the linear part of o2w; ss = dpdu / |dpdu|; ns = hit["n"] (the shading normal is
+    the geometric one, face-forwarded onto itself); ts = ns x ss. On the axis (x = y = 0: the sphere's pole, the disk's centre)
+    the point is taken at x = AXIS_NUDGE * radius, so dpdu has the direction of M e_y."""
+    p = np.array(hit["p"], dtype=np.float64)
+    on_axis = (p[:, 0] == 0.0) & (p[:, 1] == 0.0)
+    p[on_axis, 0] = AXIS_NUDGE * shape["radius"]
+    dpdu_obj = np.stack([-shape["phi_max"] * p[:, 1], shape["phi_max"] * p[:, 0], np.zeros(len(p))], axis=1)
+    dpdu = dpdu_obj @ shape["o2w"][:3, :3].T
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ss = dpdu / np.sqrt((dpdu ** 2).sum(axis=1))[:, None]
+    ns = np.asarray(hit["n"], dtype=np.float64)
+    return dict(dpdu=dpdu, ss=ss, ns=ns, ts=np.cross(ns, ss))
+
+
+def to_local(frame, w):
+    """World-space directions w (n, 3) in the frame's coordinates: (w . ss, w . ts, w . ns)."""
+    w = np.asarray(w, dtype=np.float64)
+    return np.stack([(w * frame["ss"]).sum(axis=-1), (w * frame["ts"]).sum(axis=-1), (w * frame["ns"]).sum(axis=-1)], axis=-1)
+
+
+def world_point(shape, p_obj):
+    return np.asarray(p_obj, dtype=np.float64) @ shape["o2w"][:3, :3].T + shape["o2w"][:3, 3]
+
+
+def reflect_about(d, n):
+    """The mirror direction of the incoming ray direction d about the normal n (either orientation of n)."""
+    return d - 2.0 * (d * n).sum(axis=-1, keepdims=True) * n
 
 
 def intersect_scene(shapes, o, d, t_max=np.inf):
@@ -217,11 +264,13 @@ def rays_at_unit_cube(n, seed):
 PROBE_OFFSETS = (1e-3, 1e-4)  # how far a shadow ray's origin is pushed off the surface, both tried
 
 
-def occluded_from_surface(shape, p_obj, w):
+def occluded_from_surface(shape, p_obj, w, t_max=np.inf):
     """Does the shape block the world-space direction w (n, 3) seen from its own surface points p_obj (n, 3, object space)? The
     ray starts ON the surface: a sphere's or cylinder's quadratic has the root 0 there (the point itself, not counted) and the
     other root -b / a; a disk cannot block its own points. Returns (blocked, near), `near` as in intersect(): the other root
-    within REL of 0 (a tangent ray), or its point within REL of an edge of the cut."""
+    within REL of 0 (a tangent ray), or its point within REL of an edge of the cut. With t_max the segment p + t w, t < t_max,
+    stands for the ray (t_max = 1 and w the vector to a point light: the part of the ray beyond the light blocks nothing); a
+    root within REL of t_max is `near` as well."""
     n_rays = len(p_obj)
     blocked, near = np.zeros(n_rays, dtype=bool), np.zeros(n_rays, dtype=bool)
     if shape["type"] == "disk":
@@ -235,7 +284,9 @@ def occluded_from_surface(shape, p_obj, w):
     with np.errstate(divide="ignore", invalid="ignore"):
         t = np.where(a > 0.0, -b / a, -np.inf)
         near |= (a <= 0.0) | (np.abs(t) <= REL * r / np.sqrt((dd ** 2).sum(axis=1)))
-        ahead = t > 0.0
+        if np.isfinite(t_max):
+            near |= np.abs(t - t_max) <= REL * t_max
+        ahead = (t > 0.0) & (t < t_max)
         p = p_obj + dd * np.where(ahead, t, 0.0)[:, None]
         if shape["type"] == "sphere":
             z_ok = ((shape["z_min"] <= -r) | (p[:, 2] >= shape["z_min"])) & ((shape["z_max"] >= r) | (p[:, 2] <= shape["z_max"]))
@@ -319,21 +370,54 @@ def annulus_light_floor_radiance(rho, L, R, Ri, h):
     return disk_light_floor_radiance(rho, L, R, h) - disk_light_floor_radiance(rho, L, Ri, h)
 
 
+def frame_about(n):
+    """Some orthonormal frame (ss, ts, ns) with ns = n / |n|, as 3-vectors."""
+    ns = np.asarray(n, dtype=np.float64) / np.linalg.norm(n)
+    a = np.eye(3)[np.argmin(np.abs(ns))]
+    ss = np.cross(a, ns)
+    ss /= np.linalg.norm(ss)
+    return dict(ss=ss, ts=np.cross(ns, ss), ns=ns)
+
+
+def bsdf_patch_radiance_by_quadrature(shape, p, frame, wo, f, L, cells=400, weight=None):
+    """Radiance leaving the world-space point p towards wo (world space) whose BSDF is the callable f(wo_local, wi_local) ->
+    (n,) or (n, 3) in the frame (ss, ts, ns as 3-vectors; to_local's coordinates), under the shape as a diffuse emitter of
+    radiance L that nothing shadows: L * integral of f(wo, wi) |cos_p| |cos_s| / r^2 dA by the midpoint rule over cells x cells
+    cells of the shape's parametrisation (surface_points), through its transform. weight(wi_local, r2, cos_s) -> (n,), if given,
+    multiplies the integrand (cos_s: the unit cosine at the emitter; what a pdf over its area needs). Returns (value, |value -
+    value at cells / 2|): the second is the estimate of the quadrature's error."""
+    wo_l = to_local(frame, np.asarray(wo, dtype=np.float64)[None, :])
+
+    def at(cells):
+        u = (np.arange(cells) + 0.5) / cells
+        uu, vv = np.meshgrid(u, u, indexing="ij")
+        m, h = shape["o2w"], 1e-6
+
+        def world(a, b):
+            return surface_points(shape, a, b) @ m[:3, :3].T + m[:3, 3]
+
+        q = world(uu, vv)
+        normal_da = np.cross((world(uu + h, vv) - world(uu - h, vv)) / (2 * h), (world(uu, vv + h) - world(uu, vv - h)) / (2 * h))
+        w = (q - np.asarray(p, dtype=np.float64)).reshape(-1, 3)
+        r2 = (w ** 2).sum(axis=-1)
+        wi = w / np.sqrt(r2)[:, None]
+        wi_l = to_local(frame, wi)
+        normal_da = normal_da.reshape(-1, 3)
+        cos_s_da = np.abs((wi * normal_da).sum(axis=-1))
+        fv = np.asarray(f(np.broadcast_to(wo_l, wi_l.shape), wi_l), dtype=np.float64)
+        g = np.abs(wi_l[:, 2]) * cos_s_da / r2
+        if weight is not None:
+            g = g * weight(wi_l, r2, cos_s_da / np.sqrt((normal_da ** 2).sum(axis=-1)))
+        return L * (fv * (g[:, None] if fv.ndim == 2 else g)).mean(axis=0)
+
+    fine = at(cells)
+    return fine, np.abs(fine - at(cells // 2))
+
+
 def patch_radiance_by_quadrature(shape, p, n_p, rho, L, cells=400):
     """Radiance leaving a Lambertian patch (albedo rho) at the world-space point p with normal n_p under the shape as a
-    two-sided diffuse emitter of radiance L that nothing shadows: rho / pi * L * integral of max(0, cos_p) |cos_s| / r^2 dA by
-    the midpoint rule over cells x cells cells of the shape's parametrisation (surface_points), through its transform."""
-    u = (np.arange(cells) + 0.5) / cells
-    uu, vv = np.meshgrid(u, u, indexing="ij")
-    m, h = shape["o2w"], 1e-6
-
-    def world(a, b):
-        return surface_points(shape, a, b) @ m[:3, :3].T + m[:3, 3]
-
-    q = world(uu, vv)
-    normal_da = np.cross((world(uu + h, vv) - world(uu - h, vv)) / (2 * h), (world(uu, vv + h) - world(uu, vv - h)) / (2 * h))
-    w = q - np.asarray(p, dtype=np.float64)
-    r2 = (w ** 2).sum(axis=-1)
-    cos_p = np.maximum((w * np.asarray(n_p, dtype=np.float64)).sum(axis=-1), 0.0) / np.sqrt(r2)
-    cos_s_da = np.abs((w * normal_da).sum(axis=-1)) / np.sqrt(r2)
-    return rho / np.pi * L * (cos_p * cos_s_da / r2).mean()
+    two-sided diffuse emitter of radiance L that nothing shadows: rho / pi * L * integral of max(0, cos_p) |cos_s| / r^2 dA: the
+    Lambertian case of bsdf_patch_radiance_by_quadrature (f = rho / pi above the patch, 0 below it; seen from above)."""
+    frame = frame_about(n_p)
+    value, _ = bsdf_patch_radiance_by_quadrature(shape, p, frame, frame["ns"], lambda wo, wi: np.where(wi[:, 2] > 0.0, rho / np.pi, 0.0), L, cells)
+    return value

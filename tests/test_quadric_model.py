@@ -80,6 +80,107 @@ def test_hit_points_satisfy_the_implicit_equations(name, rec):
     assert np.abs(np.sqrt((n ** 2).sum(axis=1)) - 1.0).max() < 1e-12
 
 
+@pytest.mark.parametrize("name,rec", RECORDS, ids=[r[0] for r in RECORDS])
+def test_tangent_frame_against_the_parametrisation(name, rec):
+    """surface_frame at the hits of the GPU tests' rays, held by finite differences of surface_points through o2w (partial
+    sweeps, mirrored and scaled transforms included), not by its own formula: ss is parallel to dp/du and points the same way;
+    ss is perpendicular to ns; (ss, ts, ns) is right-handed, det = +1, under every transform, because ts = ns x ss makes it so
+    whatever the matrix's determinant. What the handedness swap and reverse_orientation change is the normal: ns = +(dp/du x
+    dp/dv) / |...| of the world-space surface unless reverse_orientation is set, the mirror or not (pbrt-v3 flips n by
+    reverse ^ swaps, and the world-space cross product itself turns over under a mirror), so ts points along the part of dp/dv
+    perpendicular to ss, or against it when reversed. The anisotropic lobes cannot see that sign: Trowbridge-Reitz D and Lambda
+    read cos^2 phi and sin^2 phi of the local directions alone, which are even in the ts component."""
+    s = qm.from_record(rec[0])
+    o, d = qm.rays_at_unit_cube(4000, 11)
+    r = qm.intersect(s, o, d)
+    hit = r["hit"]
+    assert hit.sum() > 50
+    fr = qm.surface_frame(s, r)
+    ss, ts, ns = fr["ss"][hit], fr["ts"][hit], fr["ns"][hit]
+    # the parameters of the hit points, by inverting the parametrisation
+    p = r["p"][hit]
+    u = r["phi"][hit] / s["phi_max"]
+    if s["type"] == "disk":
+        v = (np.sqrt(p[:, 0] ** 2 + p[:, 1] ** 2) - s["inner_radius"]) / (s["radius"] - s["inner_radius"])
+    else:
+        v = (p[:, 2] - s["z_min"]) / (s["z_max"] - s["z_min"])
+    assert np.abs(qm.surface_points(s, u, v) - p).max() < 1e-9
+    h = 1e-6
+    lin = s["o2w"][:3, :3]
+    du = (qm.surface_points(s, u + h, v) - qm.surface_points(s, u - h, v)) / (2 * h) @ lin.T
+    dv = (qm.surface_points(s, u, v + h) - qm.surface_points(s, u, v - h)) / (2 * h) @ lin.T
+    du_len = np.sqrt((du ** 2).sum(axis=1))
+    assert np.abs(np.cross(ss, du / du_len[:, None])).max() < 1e-8 and ((ss * du).sum(axis=1) > 0.0).all()
+    assert np.abs(fr["dpdu"][hit] - du).max() < 1e-8 * max(1.0, du_len.max())  # and its length: phi_max is in it
+    assert np.abs((ss * ns).sum(axis=1)).max() < 1e-12
+    assert np.abs(np.sqrt((ss ** 2).sum(axis=1)) - 1.0).max() < 1e-12 and np.abs(np.sqrt((ts ** 2).sum(axis=1)) - 1.0).max() < 1e-12
+    assert np.abs(np.linalg.det(np.stack([ss, ts, ns], axis=1)) - 1.0).max() < 1e-12
+    cross = np.cross(du, dv)
+    sign = -1.0 if s["reverse"] else 1.0
+    if s["type"] == "disk":
+        sign = -sign  # surface_points runs the disk's v from the inner radius outward, Disk::intersect's from the radius inward
+    assert (sign * (ns * cross).sum(axis=1) > 0.0).all() and (sign * (ts * dv).sum(axis=1) > 0.0).all()
+    # to_local: the coordinates rebuild the vector
+    w = np.random.default_rng(3).normal(size=ss.shape)
+    l = qm.to_local(dict(ss=ss, ts=ts, ns=ns), w)
+    assert np.abs(l[:, :1] * ss + l[:, 1:2] * ts + l[:, 2:] * ns - w).max() < 1e-12
+
+
+def test_reversed_orientation_turns_the_frame_over():
+    for name in ("rigid", "mirrored"):
+        a, b = (qm.from_record(scenes.cylinder(0.5, -0.6, 0.7, 270.0, TRANSFORMS[name], reverse_orientation=rev)[0]) for rev in (False, True))
+        o, d = qm.rays_at_unit_cube(2000, 11)
+        ra, rb = qm.intersect(a, o, d), qm.intersect(b, o, d)
+        hit = ra["hit"]
+        fa, fb = qm.surface_frame(a, ra), qm.surface_frame(b, rb)
+        assert hit.sum() > 50 and np.array_equal(hit, rb["hit"])
+        assert np.array_equal(fa["ss"][hit], fb["ss"][hit]) and np.array_equal(fa["ns"][hit], -fb["ns"][hit]) and np.array_equal(fa["ts"][hit], -fb["ts"][hit])
+
+
+@pytest.mark.parametrize("name", ["identity", "scaled"])
+def test_a_ray_down_the_disks_axis_hits_the_centre(name):
+    """intersect's contract for the axis ray: a hit at the centre from either side, not `near`, a finite frame whose tangent is
+    the one of phi = 0 (the direction of M e_y), the limit of the points (x, 0) with x -> 0+"""
+    s = qm.from_record(scenes.disk(0.1, 1.0, to_world=TRANSFORMS[name])[0])
+    m = s["o2w"]  # the record's: rounded to float32
+    centre, axis = m[:3, :3] @ [0.0, 0.0, s["z_min"]] + m[:3, 3], m[:3, :3] @ [0.0, 0.0, 1.0]
+    o = np.stack([centre + 2.0 * axis, centre - 2.0 * axis])
+    r = qm.intersect(s, o, np.stack([-axis, axis]))
+    assert r["hit"].all() and not r["near"].any()
+    assert (r["p"] == [0.0, 0.0, s["z_min"]]).all() and np.abs(r["t"] - 2.0).max() < 1e-7  # (the record's height is a float32)
+    fr = qm.surface_frame(s, r)
+    assert np.isfinite(fr["ss"]).all() and np.isfinite(fr["ts"]).all()
+    e_y = m[:3, :3] @ [0.0, 1.0, 0.0]
+    assert np.abs(fr["ss"] - e_y / np.linalg.norm(e_y)).max() < 1e-12
+    beside = qm.intersect(s, o + m[:3, :3] @ [1e-7, 0.0, 0.0], np.stack([-axis, axis]))
+    assert np.abs(qm.surface_frame(s, beside)["ss"] - fr["ss"]).max() < 1e-8  # (1e-16 of rounding over the 1e-7 of offset)
+    # with a hole there is no centre to hit
+    assert not qm.intersect(qm.from_record(scenes.disk(0.1, 1.0, 0.2, to_world=m)[0]), o, np.stack([-axis, axis]))["hit"].any()
+
+
+def test_bsdf_quadrature_and_its_error_estimate():
+    """bsdf_patch_radiance_by_quadrature with the Lambertian f is the closed form of the disk light, its halving estimate
+    bounds its error (the midpoint rule's error falls by 4 under halved cells: a third of the difference is left), and a
+    cosine-power lobe about the mirror direction agrees with itself at twice the cells within the estimate."""
+    rho, L, h, R = 0.6, 5.0, 1.2, 1.2
+    m = translate(0.3, h, -0.2) @ rot((1, 0, 0), 90.0) @ rot((0, 0, 1), 63.0)
+    disk = qm.make("disk", R, 0.0, 0.0, o2w=m)
+    p0, fr = np.array([0.3, 0.0, -0.2]), qm.frame_about([0.0, 1.0, 0.0])
+    value, err = qm.bsdf_patch_radiance_by_quadrature(disk, p0, fr, [0.3, 0.8, 0.1], lambda wo, wi: np.full(len(wi), rho / np.pi), L, cells=200)
+    closed = qm.disk_light_floor_radiance(rho, L, R, h)
+    assert 0.0 < err < 1e-3 * closed and abs(value - closed) <= err
+    assert value == pytest.approx(qm.patch_radiance_by_quadrature(disk, p0, [0.0, 1.0, 0.0], rho, L, cells=200), rel=1e-12)
+
+    def lobe(wo, wi):
+        mirror = wo * np.array([-1.0, -1.0, 1.0])
+        return np.stack([np.maximum((mirror * wi).sum(axis=1), 0.0) ** 40] * 3, axis=1) * np.array([1.0, 0.5, 0.25])
+    wo = np.array([0.2, 0.9, -0.1]) / np.linalg.norm([0.2, 0.9, -0.1])
+    coarse, e_coarse = qm.bsdf_patch_radiance_by_quadrature(disk, p0, fr, wo, lobe, L, cells=100)
+    fine, e_fine = qm.bsdf_patch_radiance_by_quadrature(disk, p0, fr, wo, lobe, L, cells=400)
+    assert coarse.shape == (3,) and (fine > 0.0).all() and (e_fine < e_coarse).all()
+    assert (np.abs(coarse - fine) <= e_coarse).all()
+
+
 @pytest.mark.parametrize("kind", ["sphere", "disk", "cylinder"])
 def test_area_matches_a_quadrature(kind):
     s = {"sphere": qm.make("sphere", 0.7, -0.4, 0.6, phi_max_deg=270.0),

@@ -563,6 +563,47 @@ int pbrt_hip_scene_create_two_level(PbrtHipContext* ctx, const PbrtObject* objec
                                     const PbrtMaterial* materials, int32_t n_materials, const PbrtLight* lights, int32_t n_lights,
                                     const PbrtLinearBVHNode* tlas_nodes, int32_t n_tlas_nodes, const int32_t* tlas_order,
                                     PbrtHipScene** out);
+/* ---- moving instances: TransformedPrimitive over an AnimatedTransform (src/core/primitive.rs:105-159,
+ * src/core/transform.rs:870-912, 2008-2084) ----
+ * PbrtInstance.to_world is the transform at start_time, end_to_world the one at end_time (row-major, last row 0 0 0 1).
+ * Both are decomposed at scene creation, in double precision, into translation, rotation (a quaternion, the end one negated
+ * when the two have a negative dot product) and the rest (Matrix4x4::decompose, transform.rs:264-330, after pbrt-v3); a ray
+ * meets the instance at T(u) R(u) S(u) with u = (ray.time - start_time) / (end_time - start_time): T and S interpolated
+ * linearly, R by Quaternion::slerp (the normalised linear interpolation above a dot product of 0.9995), and at the stored
+ * matrices themselves for a time at or beyond either end (AnimatedTransform::interpolate). animated == 0: a static instance,
+ * the other fields are not read. */
+typedef struct PbrtInstanceMotion {
+    float end_to_world[16];
+    float start_time, end_time;
+    int32_t animated;
+    int32_t pad;
+} PbrtInstanceMotion;
+/* TransformedPrimitive::world_bound of moving instances (AnimatedTransform::motion_bounds): a box that holds the object bounds
+ * at every time. Host only. Not the reference's derivative-root bound but one that is short and provably conservative
+ * (DESIGN.md D96): static instances get pbrt_hip_instance_bounds; instances whose two rotations are equal the union of the
+ * start and end boxes (every corner moves on a line); the others the union over 32 time segments of each corner's two end
+ * positions, grown by what the corner's speed bound allows it to travel in half a segment, then padded for the device's
+ * float32 interpolation. PBRT_HIP_ERR_INVALID for a non-finite or non-affine matrix, end_time <= start_time or a singular
+ * start or end matrix (scene creation makes the same checks and names the instance in pbrt_hip_last_error). */
+int pbrt_hip_instance_motion_bounds(const float object_min[3], const float object_max[3], const PbrtInstance* instances,
+                                    const PbrtInstanceMotion* motions, int32_t n_instances, float* bounds_min, float* bounds_max);
+/* pbrt_hip_scene_create_two_level with moving instances: motions[i] belongs to instances[i]. The top-level tree must have
+ * been built over pbrt_hip_instance_motion_bounds: creation checks that every instance's box lies inside the leaf box that
+ * holds it and refuses a tree that would drop hits. With no animated instance (or motions == NULL) the scene IS
+ * pbrt_hip_scene_create_two_level's. A scene with an animated instance is walked over the binary records
+ * (pbrt_hip_scene_wide_records reports "scene with moving instances"; PBRT_TRAVERSAL_STACKLESS is refused as for every
+ * two-level scene). pbrt_hip_intersect / _p / _li take PbrtRay.time as given; pbrt_hip_render draws a camera ray's time
+ * as lerp(time sample, shutter_open, shutter_close) and every ray of the path keeps it (Ray::spawn). Such a scene takes no
+ * projection or goniometric light (refused here) and no lobe rows (refused by pbrt_hip_scene_set_lobe_material).
+ * PBRT_HIP_ERR_INVALID (pbrt_hip_last_error names the instance) for what pbrt_hip_instance_motion_bounds refuses. */
+int pbrt_hip_scene_create_two_level_moving(PbrtHipContext* ctx, const PbrtObject* objects, int32_t n_objects,
+                                           const PbrtInstance* instances, const PbrtInstanceMotion* motions,
+                                           const int32_t* instance_object, int32_t n_instances, const float* world_positions,
+                                           int32_t n_world_verts, const int32_t* world_indices, int32_t n_world_tris,
+                                           const int32_t* world_tri_material, const int32_t* world_tri_light,
+                                           const PbrtMaterial* materials, int32_t n_materials, const PbrtLight* lights,
+                                           int32_t n_lights, const PbrtLinearBVHNode* tlas_nodes, int32_t n_tlas_nodes,
+                                           const int32_t* tlas_order, PbrtHipScene** out);
 void pbrt_hip_scene_destroy(PbrtHipScene* scene);
 /* Traversal layout of a scene. Beside the 64-B child-pair records of the reference's tree a scene may carry 4-wide,
  * 48-byte records with 8-bit conservative boxes laid over the same tree (two levels of BVHAccel's nodes per record,

@@ -199,6 +199,26 @@ inline PbrtInstance TransformedPrimitive(const double to_world[16], int32_t mate
     inst.material = material;
     return inst;
 }
+// AnimatedTransform::new(start_transform, start_time, end_transform, end_time) (src/core/transform.rs:870-912): the two
+// object-to-world matrices of a moving TransformedPrimitive, row-major with last row (0, 0, 0, 1). Forwarding only: the library
+// decomposes and interpolates (pbrt_hip_scene_create_two_level_moving).
+struct AnimatedTransform {
+    double start_transform[16];
+    float start_time;
+    double end_transform[16];
+    float end_time;
+};
+// TransformedPrimitive::new(primitive, primitive_to_world: AnimatedTransform): the instance record (at the start transform) and
+// its motion record, for BVHAccel's `motions`
+inline PbrtInstance TransformedPrimitive(const AnimatedTransform& to_world, PbrtInstanceMotion* motion, int32_t material = -1) {
+    std::memset(motion, 0, sizeof(*motion));
+    for (int k = 0; k < 16; ++k) motion->end_to_world[k] = (float)to_world.end_transform[k];
+    motion->end_to_world[12] = motion->end_to_world[13] = motion->end_to_world[14] = 0.0f, motion->end_to_world[15] = 1.0f;
+    motion->start_time = to_world.start_time;
+    motion->end_time = to_world.end_time;
+    motion->animated = 1;
+    return TransformedPrimitive(to_world.start_transform, material);
+}
 
 // ProjectionLight::new(light_to_world, .., I, texname, fov) and GonioPhotometricLight::new(light_to_world, .., I, texname)
 // (lights/projection.rs:36-88, goniometric.rs:32-63) without the map (Scene::set_light_map attaches the texels): the PbrtLight
@@ -361,9 +381,12 @@ public:
     // The general top-level aggregate (primitive.rs:105-159 beside :33-103): TransformedPrimitives of SEVERAL object aggregates
     // (instance i shows objects[instance_object[i]]) and plain world-space triangles beside them — the only primitives that can
     // carry area lights here. Materials and lights are the WORLD mesh's (`world.materials`, `world.lights`; an object's triangles
-    // index the same material table); `world` may hold no triangles.
+    // index the same material table); `world` may hold no triangles. motions: empty, or one PbrtInstanceMotion per instance
+    // (TransformedPrimitive over an AnimatedTransform; a zeroed record = a static instance): the top-level tree is then built over
+    // the motion bounds.
     BVHAccel(std::shared_ptr<Context> ctx, const std::vector<TriangleMesh>& objects, const std::vector<PbrtInstance>& instances,
-             const std::vector<int32_t>& instance_object, const TriangleMesh& world, int max_prims_in_node = 4, SplitMethod split_method = SplitMethod::SAH)
+             const std::vector<int32_t>& instance_object, const TriangleMesh& world, int max_prims_in_node = 4, SplitMethod split_method = SplitMethod::SAH,
+             const std::vector<PbrtInstanceMotion>& motions = {})
         : ctx_(std::move(ctx)) {
         struct Tree {
             PbrtLinearBVHNode* nodes = nullptr;
@@ -375,7 +398,7 @@ public:
             for (Tree& t : trees) pbrt_hip_free(t.nodes), pbrt_hip_free(t.order);
             pbrt_hip_free(top.nodes), pbrt_hip_free(top.order);
         };
-        int rc = instances.size() == instance_object.size() ? PBRT_HIP_OK : PBRT_HIP_ERR_INVALID;
+        int rc = instances.size() == instance_object.size() && (motions.empty() || motions.size() == instances.size()) ? PBRT_HIP_OK : PBRT_HIP_ERR_INVALID;
         for (size_t k = 0; k < objects.size() && rc == PBRT_HIP_OK; ++k)
             rc = pbrt_hip_bvh_build(objects[k].p.data(), objects[k].n_vertices(), objects[k].vertex_indices.data(), objects[k].n_triangles(), max_prims_in_node,
                                     (int)split_method, &trees[k].nodes, &trees[k].n, &trees[k].order);
@@ -384,7 +407,8 @@ public:
         for (size_t i = 0; i < ni && rc == PBRT_HIP_OK; ++i) {  // TransformedPrimitive::world_bound (primitive.rs:126-134)
             const int32_t o = instance_object[i];
             rc = o >= 0 && (size_t)o < objects.size()
-                     ? pbrt_hip_instance_bounds(trees[o].nodes[0].bounds_min, trees[o].nodes[0].bounds_max, &instances[i], 1, &lo[3 * i], &hi[3 * i])
+                     ? pbrt_hip_instance_motion_bounds(trees[o].nodes[0].bounds_min, trees[o].nodes[0].bounds_max, &instances[i],
+                                                       motions.empty() ? nullptr : &motions[i], 1, &lo[3 * i], &hi[3 * i])
                      : PBRT_HIP_ERR_INVALID;
         }
         for (size_t t = 0; t < nw; ++t)
@@ -404,13 +428,14 @@ public:
         for (size_t k = 0; k < objects.size(); ++k)
             objs[k] = {objects[k].p.data(), objects[k].n_vertices(), objects[k].vertex_indices.data(), objects[k].n_triangles(),
                        objects[k].material.empty() ? nullptr : objects[k].material.data(), trees[k].nodes, trees[k].n, trees[k].order};
-        rc = pbrt_hip_scene_create_two_level(ctx_->handle(), objs.data(), (int32_t)objs.size(), instances.data(), instance_object.data(), (int32_t)ni,
+        rc = pbrt_hip_scene_create_two_level_moving(ctx_->handle(), objs.data(), (int32_t)objs.size(), instances.data(), motions.empty() ? nullptr : motions.data(),
+                                             instance_object.data(), (int32_t)ni,
                                              nw ? world.p.data() : nullptr, nw ? world.n_vertices() : 0, nw ? world.vertex_indices.data() : nullptr, (int32_t)nw,
                                              nw ? world.material.data() : nullptr, nw ? world.area_light.data() : nullptr, world.materials.data(),
                                              (int32_t)world.materials.size(), world.lights.empty() ? nullptr : world.lights.data(), (int32_t)world.lights.size(),
                                              top.nodes, top.n, top.order, &h_);
         release();
-        ctx_->check(rc, "BVHAccel::new: pbrt_hip_scene_create_two_level");
+        ctx_->check(rc, "BVHAccel::new: pbrt_hip_scene_create_two_level(_moving)");
     }
     ~BVHAccel() override { pbrt_hip_scene_destroy(h_); }
     BVHAccel(const BVHAccel&) = delete;

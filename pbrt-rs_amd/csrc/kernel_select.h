@@ -14,7 +14,9 @@
 namespace pb {
 
 // ---- traversal ----
-enum class TraceKind { Stackless, Wide, Shapes, Spheres, Binary };
+// Moving: a two-level scene with moving instances (trace_persistent's MOV builds over the binary records; never wide —
+// the scene carries no wide records — and never stackless, which refuses every two-level scene)
+enum class TraceKind { Stackless, Wide, Shapes, Spheres, Binary, Moving };
 struct TraceChoice {
     TraceKind kind;
     int inst;    // trace_persistent.h: INST (0 single level, 1 instances of one aggregate, 2 general top level)
@@ -33,6 +35,8 @@ inline TraceChoice choose_trace(const PbrtHipScene* s) {
         c.count = ctx->count_traversal == 2;
     } else if (s->d.bvh.has_spheres) {  // single-level scenes only (checked at creation); 2: general quadric shapes
         c.kind = s->d.bvh.has_spheres == 2 ? TraceKind::Shapes : TraceKind::Spheres;
+    } else if (s->moving) {
+        c.kind = TraceKind::Moving;
     }
     return c;
 }
@@ -47,7 +51,8 @@ template <TraceKind K>
 using TraceKindC = std::integral_constant<TraceKind, K>;
 
 // Calls f(TraceKindC<kind>, std::bool_constant<COUNT>, std::integral_constant<int, INST>) for the choice. Only the combinations
-// the kernels exist for are ever formed: shapes and spheres are single level, the stackless walk has neither COUNT nor INST.
+// the kernels exist for are ever formed: shapes and spheres are single level, the stackless walk has neither COUNT nor INST,
+// moving scenes have two levels (INST 1 or 2).
 template <class F>
 inline void dispatch(const TraceChoice& c, F&& f) {
     auto with_count = [&](auto kind, auto inst) {
@@ -70,6 +75,12 @@ inline void dispatch(const TraceChoice& c, F&& f) {
         case TraceKind::Shapes: with_count(TraceKindC<TraceKind::Shapes>{}, std::integral_constant<int, 0>{}); break;
         case TraceKind::Spheres: with_count(TraceKindC<TraceKind::Spheres>{}, std::integral_constant<int, 0>{}); break;
         case TraceKind::Binary: with_inst(TraceKindC<TraceKind::Binary>{}); break;
+        case TraceKind::Moving:
+            if (c.inst == 2)
+                with_count(TraceKindC<TraceKind::Moving>{}, std::integral_constant<int, 2>{});
+            else
+                with_count(TraceKindC<TraceKind::Moving>{}, std::integral_constant<int, 1>{});
+            break;
     }
 }
 
@@ -82,10 +93,12 @@ struct SceneNeeds {
     bool light_maps;  // a projection or goniometric light in the table
     int level;        // 0 matte / mirror / glass, 1 plastic or metal, 2 a row of pbrt_hip_scene_set_material, 3 a Disney row
     bool lobes;       // a row of pbrt_hip_scene_set_lobe_material: the lobe-list builds (never with shapes or light_maps: the setter refuses)
+    bool moving;      // moving instances: the builds that interpolate the instance at the path's time (never with shapes, light_maps
+                      // or lobes: creation and the setters refuse)
     int column() const { return shapes ? 0 : light_maps ? 1 : 5 - level; }  // of the tables below: in that precedence, most general first
 };
 inline SceneNeeds scene_needs(const PbrtHipScene* s) {
-    return SceneNeeds{s->d.bvh.has_spheres == 2, s->light_maps, s->disney ? 3 : s->bxdfs ? 2 : s->glossy ? 1 : 0, s->lobes};
+    return SceneNeeds{s->d.bvh.has_spheres == 2, s->light_maps, s->disney ? 3 : s->bxdfs ? 2 : s->glossy ? 1 : 0, s->lobes, s->moving};
 }
 
 #ifdef PB_SELECT_SHADING_KERNELS
@@ -99,6 +112,9 @@ using SpatialKernel = void (*)(ShadeConsts, float*);
 // The lobe-list builds have tables of their own at the END of this file, so that every older instantiation is met first.
 inline DirectKernel lobe_direct_kernel(bool whitted);
 inline PathKernel lobe_path_kernel(bool bin);
+// ... and behind them those of the builds for moving instances
+inline DirectKernel moving_direct_kernel(int integrator);
+inline PathKernel moving_path_kernel(bool bin);
 
 // the build of the SpatialLightDistribution tables (wf_lights.h)
 inline SpatialKernel spatial_tables_kernel(const SceneNeeds& n) {
@@ -116,6 +132,7 @@ inline DirectKernel direct_kernel(const SceneNeeds& n, int integrator) {
                                                {k_shade_direct<D, 1>, k_shade_direct<W, 1>},
                                                {k_shade_direct<D, 0>, k_shade_direct<W, 0>}};
     static constexpr DirectKernel ao[2] = {k_shade_direct<AO, kDirectShapes>, k_shade_direct<AO, 0>};
+    if (n.moving) return moving_direct_kernel(integrator);
     if (n.lobes && (integrator == D || integrator == W)) return lobe_direct_kernel(integrator == W);
     if (integrator == D || integrator == W) return lit[n.column()][integrator == W];
     return ao[n.shapes ? 0 : 1];
@@ -126,6 +143,7 @@ inline PathKernel path_kernel(const SceneNeeds& n, bool bin) {
     static constexpr PathKernel table[2][6] = {
         {k_shade_shapes<true>, k_shade_maps<true>, k_shade<true, 3>, k_shade<true, 2>, k_shade<true, 1>, k_shade<true, 0>},
         {k_shade_shapes<false>, k_shade_maps<false>, k_shade<false, 3>, k_shade<false, 2>, k_shade<false, 1>, k_shade<false, 0>}};
+    if (n.moving) return moving_path_kernel(bin);
     if (n.lobes) return lobe_path_kernel(bin);
     return table[bin ? 0 : 1][n.column()];
 }
@@ -138,6 +156,18 @@ inline DirectKernel lobe_direct_kernel(bool whitted) {
 }
 inline PathKernel lobe_path_kernel(bool bin) {
     static constexpr PathKernel table[2] = {k_shade_lobes<true>, k_shade_lobes<false>};
+    return table[bin ? 0 : 1];
+}
+
+// k_shade_direct<MODE, 3 + kDirectMoving>, the AO build and k_shade_moving<BIN>: scenes with moving instances
+inline DirectKernel moving_direct_kernel(int integrator) {
+    static constexpr DirectKernel table[3] = {k_shade_direct<PBRT_INTEGRATOR_DIRECT, 3 + kDirectMoving>,
+                                              k_shade_direct<PBRT_INTEGRATOR_WHITTED, 3 + kDirectMoving>,
+                                              k_shade_direct<PBRT_INTEGRATOR_AO, kDirectMoving>};
+    return table[integrator == PBRT_INTEGRATOR_DIRECT ? 0 : integrator == PBRT_INTEGRATOR_WHITTED ? 1 : 2];
+}
+inline PathKernel moving_path_kernel(bool bin) {
+    static constexpr PathKernel table[2] = {k_shade_moving<true>, k_shade_moving<false>};
     return table[bin ? 0 : 1];
 }
 #endif  // PB_SELECT_SHADING_KERNELS

@@ -16,8 +16,10 @@
 
 #include "host_envmap.h"
 #include "host_lobes.h"
+#include "host_motion.h"
 #include "host_wide.h"
 #include "kernel_select.h"
+#include "motion.h"
 #include "scene.h"
 #include "trace.h"
 #include "trace_persistent.h"
@@ -380,6 +382,7 @@ struct InstancingArgs {
     const PbrtObject* objects = nullptr;
     int32_t n_objects = 0;
     const int32_t* instance_object = nullptr;  // nullptr = all instances of object 0
+    const PbrtInstanceMotion* motions = nullptr;  // pbrt_hip_scene_create_two_level_moving: one per instance, or nullptr
     std::vector<int32_t> obj_tri_offset;       // n_objects + 1
     int32_t n_world_tris = 0, world_tri_offset = 0;
 };
@@ -483,13 +486,13 @@ extern "C" int pbrt_hip_scene_create_with_shapes(PbrtHipContext* ctx, const floa
 }
 PB_ABI_CATCH
 
-extern "C" int pbrt_hip_scene_create_two_level(PbrtHipContext* ctx, const PbrtObject* objects, int32_t n_objects,
-                                               const PbrtInstance* instances, const int32_t* instance_object, int32_t n_instances,
-                                               const float* world_positions, int32_t n_world_verts, const int32_t* world_indices,
-                                               int32_t n_world_tris, const int32_t* world_tri_material,
-                                               const int32_t* world_tri_light, const PbrtMaterial* materials, int32_t n_materials,
-                                               const PbrtLight* lights, int32_t n_lights, const PbrtLinearBVHNode* tlas_nodes,
-                                               int32_t n_tlas_nodes, const int32_t* tlas_order, PbrtHipScene** out) try {
+// pbrt_hip_scene_create_two_level and, with `motions`, pbrt_hip_scene_create_two_level_moving
+static int create_two_level(PbrtHipContext* ctx, const PbrtObject* objects, int32_t n_objects, const PbrtInstance* instances,
+                            const PbrtInstanceMotion* motions, const int32_t* instance_object, int32_t n_instances,
+                            const float* world_positions, int32_t n_world_verts, const int32_t* world_indices, int32_t n_world_tris,
+                            const int32_t* world_tri_material, const int32_t* world_tri_light, const PbrtMaterial* materials,
+                            int32_t n_materials, const PbrtLight* lights, int32_t n_lights, const PbrtLinearBVHNode* tlas_nodes,
+                            int32_t n_tlas_nodes, const int32_t* tlas_order, PbrtHipScene** out) {
     if (!ctx || !out) return PBRT_HIP_ERR_INVALID;
     auto fail = [&](const char* msg) {
         ctx->last_error = msg;
@@ -509,6 +512,7 @@ extern "C" int pbrt_hip_scene_create_two_level(PbrtHipContext* ctx, const PbrtOb
     ia.objects = objects;
     ia.n_objects = n_objects;
     ia.instance_object = instance_object;
+    ia.motions = motions;
     ia.n_world_tris = n_world_tris;
     int64_t n_verts = 0, n_tris = 0, n_nodes = 0;
     ia.obj_tri_offset.assign(n_objects + 1, 0);
@@ -561,6 +565,36 @@ extern "C" int pbrt_hip_scene_create_two_level(PbrtHipContext* ctx, const PbrtOb
     }
     return scene_create_impl(ctx, pos.data(), (int32_t)n_verts, idx.data(), (int32_t)n_tris, mat.data(), materials, n_materials,
                              lgt.data(), lights, n_lights, nullptr, (int32_t)n_nodes, order.data(), ia, out);
+}
+
+extern "C" int pbrt_hip_scene_create_two_level(PbrtHipContext* ctx, const PbrtObject* objects, int32_t n_objects,
+                                               const PbrtInstance* instances, const int32_t* instance_object, int32_t n_instances,
+                                               const float* world_positions, int32_t n_world_verts, const int32_t* world_indices,
+                                               int32_t n_world_tris, const int32_t* world_tri_material,
+                                               const int32_t* world_tri_light, const PbrtMaterial* materials, int32_t n_materials,
+                                               const PbrtLight* lights, int32_t n_lights, const PbrtLinearBVHNode* tlas_nodes,
+                                               int32_t n_tlas_nodes, const int32_t* tlas_order, PbrtHipScene** out) try {
+    return create_two_level(ctx, objects, n_objects, instances, nullptr, instance_object, n_instances, world_positions, n_world_verts,
+                            world_indices, n_world_tris, world_tri_material, world_tri_light, materials, n_materials, lights, n_lights,
+                            tlas_nodes, n_tlas_nodes, tlas_order, out);
+}
+PB_ABI_CATCH
+
+extern "C" int pbrt_hip_scene_create_two_level_moving(PbrtHipContext* ctx, const PbrtObject* objects, int32_t n_objects,
+                                                      const PbrtInstance* instances, const PbrtInstanceMotion* motions,
+                                                      const int32_t* instance_object, int32_t n_instances,
+                                                      const float* world_positions, int32_t n_world_verts,
+                                                      const int32_t* world_indices, int32_t n_world_tris,
+                                                      const int32_t* world_tri_material, const int32_t* world_tri_light,
+                                                      const PbrtMaterial* materials, int32_t n_materials, const PbrtLight* lights,
+                                                      int32_t n_lights, const PbrtLinearBVHNode* tlas_nodes, int32_t n_tlas_nodes,
+                                                      const int32_t* tlas_order, PbrtHipScene** out) try {
+    // a scene in which nothing moves is pbrt_hip_scene_create_two_level's scene: same records, same kernels
+    bool any = false;
+    for (int32_t i = 0; motions && i < n_instances; ++i) any = any || motions[i].animated != 0;
+    return create_two_level(ctx, objects, n_objects, instances, any ? motions : nullptr, instance_object, n_instances, world_positions,
+                            n_world_verts, world_indices, n_world_tris, world_tri_material, world_tri_light, materials, n_materials,
+                            lights, n_lights, tlas_nodes, n_tlas_nodes, tlas_order, out);
 }
 PB_ABI_CATCH
 
@@ -745,6 +779,7 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
     const int32_t n_top = ia.n_instances + ia.n_world_tris;  // primitives of the top-level aggregate
     TreeLayout top, obj;
     std::vector<TreeLayout> obj_trees;
+    std::vector<DevMotion> motion_rows;  // moving instances: one row per INSTANCE here, per top-level slot on the device
     if (instanced) {
         for (int32_t i = 0; i < n_top; ++i)
             if (ia.tlas_order[i] < 0 || ia.tlas_order[i] >= n_top) return fail("tlas_order entry out of range");
@@ -757,6 +792,39 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
             if (ia.instances[i].material >= n_materials) return fail("instance material out of range");
         }
         if (const char* e = convert_tree(ia.tlas_nodes, ia.n_tlas_nodes, n_top, 0, &top)) return fail(e);
+        if (ia.motions) {
+            // moving instances (host_motion.cpp); the limits of their one general shading build per integrator family: DESIGN.md D96
+            for (int32_t i = 0; i < n_lights; ++i)
+                if (lights[i].type == PBRT_LIGHT_PROJECTION || lights[i].type == PBRT_LIGHT_GONIOMETRIC)
+                    return fail("scenes with moving instances take no projection or goniometric light");
+            motion_rows.resize(ia.n_instances);
+            for (int32_t i = 0; i < ia.n_instances; ++i)
+                if (const char* why = motion_row(ia.instances[i], ia.motions[i], &motion_rows[i])) {
+                    ctx->last_error = "moving instance " + std::to_string(i) + ": " + why;
+                    return PBRT_HIP_ERR_INVALID;
+                }
+            // The caller built the top-level tree; one built over the static bounds would silently drop hits: every
+            // instance's motion bound must lie inside the leaf box that holds it.
+            for (int32_t nd = 0; nd < ia.n_tlas_nodes; ++nd) {
+                const PbrtLinearBVHNode& leaf = ia.tlas_nodes[nd];
+                for (int32_t k = 0; k < (int32_t)leaf.n_primitives; ++k) {
+                    const int32_t slot = leaf.offset + k;
+                    if (slot < 0 || slot >= n_top) return fail("top-level leaf slot out of range");
+                    const int32_t id = ia.tlas_order[slot];
+                    if (id >= ia.n_instances) continue;
+                    const PbrtLinearBVHNode& root = ia.objects[ia.instance_object ? ia.instance_object[id] : 0].nodes[0];
+                    float lo[3], hi[3];
+                    if (pbrt_hip_instance_motion_bounds(root.bounds_min, root.bounds_max, ia.instances + id, ia.motions + id, 1, lo, hi) != PBRT_HIP_OK)
+                        return fail("moving instance: no motion bound");
+                    for (int c = 0; c < 3; ++c)
+                        if (!(lo[c] >= leaf.bounds_min[c] && hi[c] <= leaf.bounds_max[c])) {
+                            ctx->last_error = "instance " + std::to_string(id) + ": its motion bound (pbrt_hip_instance_motion_bounds) leaves the top-level "
+                                              "leaf box that holds it; build the top-level tree over the motion bounds";
+                            return PBRT_HIP_ERR_INVALID;
+                        }
+                }
+            }
+        }
         // the object-level trees behind it in one record array; one leaf-reference width for all of them
         int max_count = 1;
         for (int32_t k = 0; k < ia.n_objects; ++k)
@@ -1002,6 +1070,13 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
         d.bvh.instances = (const float4*)dev_upload(s, inst.data(), inst.size(), &ok);
         d.slot_instance = dev_upload(s, slot_inst.data(), slot_inst.size(), &ok);
         s->n_instances = ia.n_instances;
+        if (!motion_rows.empty()) {
+            std::vector<DevMotion> by_slot(n_top, DevMotion{});
+            for (int32_t slot = 0; slot < n_top; ++slot)
+                if (slot_inst[slot] >= 0) by_slot[slot] = motion_rows[slot_inst[slot]];
+            s->d_motions = dev_upload(s, by_slot.data(), by_slot.size(), &ok);
+            s->moving = true;
+        }
     }
     // ---- 4-wide quantised records over the same tree (wide_bvh.h): single-level triangle scenes whose tree came
     // from the host; PBRT_WIDE_BUILD_NONE keeps the scene on the binary records ----
@@ -1013,6 +1088,8 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
             s->wide_reason = "scene with shapes";
         } else if (sa.n > 0) {
             s->wide_reason = "scene with spheres";
+        } else if (s->moving) {
+            s->wide_reason = "scene with moving instances";
         } else if (dt && dt->wide.n_records >= 0) {
             // laid out on the device beside the tree (wide_gpu.hip): the scene takes the arrays over
             s->wide.nodes = (const uint4*)dt->wide.nodes;
@@ -1477,6 +1554,7 @@ extern "C" int pbrt_hip_scene_set_lobe_material(PbrtHipScene* s, int32_t materia
     if (material < 0 || material >= (int32_t)s->h_materials.size()) return invalid("material index out of range");
     if (s->d.bvh.has_spheres == 2) return invalid("scenes with general quadric shapes take no lobe rows (their shading builds stay at level 3)");
     if (s->light_maps) return invalid("scenes with a projection or goniometric light take no lobe rows (their shading builds stay at level 3)");
+    if (s->moving) return invalid("scenes with moving instances take no lobe rows");
     LobeList la, lb, L;
     if (desc->type == PBRT_LOBEMAT_MIX) {
         const int32_t ops[2] = {desc->material_a, desc->material_b};
@@ -1740,6 +1818,15 @@ struct BatchRayIO {
         *any = ANY;
         return true;
     }
+    // the MOV builds also take PbrtRay.time, as given
+    PB_DEV bool load(uint32_t i, TravRay* r, bool* any, float* time) const {
+        const float4* rp = reinterpret_cast<const float4*>(rays + i);
+        float4 a = rp[0], b = rp[1];
+        *r = TravRay{a.x, a.y, a.z, a.w, b.x, b.y, b.z};
+        *any = ANY;
+        *time = b.w;
+        return true;
+    }
     PB_DEV void store(uint32_t i, bool any, bool found, float t, float b0, float b1, float b2, int slot, int inst) const {
         if (ANY) {
             out_flags[i] = found ? 1 : 0;
@@ -1795,6 +1882,20 @@ __global__ void __launch_bounds__(kTraceBlock, INST ? PB_INST_WAVES : PB_TRACE_W
                                                                          blockIdx.x * kTraceBlock + threadIdx.x, nullptr);
 }
 
+// two-level scenes with moving instances (trace_persistent's MOV builds; INST 1 or 2). Named after every older kernel: the
+// code generated for some kernels depends on the order in which the instantiations are met (kernel_select.h).
+#ifndef PB_MOVING_WAVES
+#define PB_MOVING_WAVES 4  // 128 registers: the interpolation's ~40 live values on top of the two-level walk
+#endif
+template <bool ANY, bool COUNT, int INST>
+__global__ void __launch_bounds__(kTraceBlock, PB_MOVING_WAVES)
+    k_intersect_batch_moving(DevBVH bvh, const DevMotion* __restrict__ motions, BatchRayIO<ANY> io, unsigned int* work_counter,
+                             unsigned long long* counters) {
+    __shared__ uint2 lds_stack[kStackLds * kTraceBlock];
+    trace_persistent<BatchRayIO<ANY>, COUNT, INST, false, false, true>(bvh, io, work_counter, lds_stack + threadIdx.x,
+                                                                       blockIdx.x * kTraceBlock + threadIdx.x, counters, motions);
+}
+
 template <bool ANY>
 static int launch_batch(PbrtHipScene* s, const PbrtRay* d_rays, int64_t n, PbrtHit* d_hits, uint8_t* d_flags) {
     PbrtHipContext* ctx = s->ctx;
@@ -1834,6 +1935,9 @@ static int launch_batch(PbrtHipScene* s, const PbrtRay* d_rays, int64_t n, PbrtH
             hipLaunchKernelGGL((k_intersect_batch_special<ANY, INST>), grid, block, 0, ctx->stream, s->d.bvh, sio, ctx->d_work_counter + kFollowUpCounter);
         } else if constexpr (K == TraceKind::Shapes) {
             hipLaunchKernelGGL((k_intersect_batch_shapes<ANY, COUNT>), grid, block, 0, ctx->stream, s->d.bvh, io, ctx->d_work_counter, ctx->d_counters);
+        } else if constexpr (K == TraceKind::Moving) {
+            hipLaunchKernelGGL((k_intersect_batch_moving<ANY, COUNT, INST>), dim3(persistent_grid(s, PB_MOVING_WAVES)), block, 0, ctx->stream,
+                               s->d.bvh, s->d_motions, io, ctx->d_work_counter, ctx->d_counters);
         } else {
             hipLaunchKernelGGL((k_intersect_batch<ANY, COUNT, INST, K == TraceKind::Spheres>), grid, block, 0, ctx->stream, s->d.bvh, io,
                                ctx->d_work_counter, ctx->d_counters);

@@ -402,6 +402,7 @@ static void scene_shade_consts(const PbrtHipScene* s, ShadeConsts* out) {
     sc.disney = s->d.disney;
     sc.light_maps = s->d.light_maps;
     sc.lobe_rows = s->d.lobe_rows;
+    sc.motions = s->d_motions;
 }
 
 // Light::sample_li (light.rs:35-42) of one light of the scene from bare interactions at the world points p (normal and error
@@ -1239,6 +1240,9 @@ void RenderJob::trace_wavefront(const RenderEvents& ev, const Queues& qcur, uint
         } else if constexpr (K == TraceKind::Shapes) {
             hipLaunchKernelGGL(k_trace_shapes<COUNT>, grid, block, 0, st, s->d.bvh, ps, trace_queue, n_trace, ctx->d_work_counter, ctx->d_counters,
                                segments);
+        } else if constexpr (K == TraceKind::Moving) {
+            hipLaunchKernelGGL((k_trace_moving<COUNT, INST>), dim3(persistent_grid(s, PB_MOVING_TRACE_WAVES)), block, 0, st, s->d.bvh, s->d_motions, ps,
+                               trace_queue, n_trace, ctx->d_work_counter, ctx->d_counters, segments);
         } else {
             hipLaunchKernelGGL((k_trace<COUNT, INST, K == TraceKind::Spheres>), grid, block, 0, st, s->d.bvh, ps, trace_queue, n_trace,
                                ctx->d_work_counter, ctx->d_counters, segments);
@@ -1439,7 +1443,7 @@ int RenderJob::run(const PbrtCamera& camera, PbrtRenderStats* stats) {
             hipLaunchKernelGGL(k_li_generate, dim3((n_paths + 255) / 256), dim3(256), 0, st, ps, q[0], li->d_rays, li->d_keys, (uint32_t)li->n,
                                n_paths, li->skip);
         else
-            hipLaunchKernelGGL(k_generate, dim3((n_paths + 255) / 256), dim3(256), 0, st, ps, q[0], pp, cam, tiles);
+            hipLaunchKernelGGL(s->moving ? k_generate_moving : k_generate, dim3((n_paths + 255) / 256), dim3(256), 0, st, ps, q[0], pp, cam, tiles);
         RENDER_TRY(hipGetLastError());
         if (export_mode) {
             hipLaunchKernelGGL(k_camera_rays_out, dim3((n_paths + 255) / 256), dim3(256), 0, st, ps, pp, tiles, li->out_rays, li->out_keys,

@@ -197,6 +197,9 @@ struct DevSceneData {
 
 }  // namespace pb
 
+namespace pb {
+struct DevMotion;  // motion.h
+}
 struct PbrtHipScene {
     PbrtHipContext* ctx = nullptr;
     pb::DevSceneData d;          // device pointers inside
@@ -227,6 +230,10 @@ struct PbrtHipScene {
     pb::WideTrees wide{};
     int n_wide_records = 0;
     std::string wide_reason;  // why the scene has none
+    // moving instances (pbrt_hip_scene_create_two_level_moving): an instance with PbrtInstanceMotion.animated; the side table
+    // (motion.h) has one row per top-level leaf slot and rides in the MOV kernels' arguments, not in DevBVH
+    bool moving = false;
+    const pb::DevMotion* d_motions = nullptr;
 };
 
 namespace pb {

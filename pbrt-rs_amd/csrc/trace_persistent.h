@@ -24,6 +24,7 @@
 // popped, so a far child whose box already failed is still pushed (entry distance +inf) and
 // counted when popped; entries never popped (any-hit early exit) are not counted.
 #pragma once
+#include "motion.h"
 #include "trace.h"
 
 namespace pb {
@@ -68,6 +69,7 @@ struct InstState {
     int cur_inst, hit_inst;               // instance slots
     int base_sp;                          // stack height when the instance was entered
     bool in_instance, hit_here;
+    float time;                           // MOV: the ray's time (IO::load's fourth output)
 };
 
 PB_DEV void stack_push(const DevBVH& bvh, uint2* lds_stack, int spill_lane, int& sp, int node, float entry) {
@@ -106,9 +108,14 @@ PB_DEV bool root_box_test(const LaneState& s, const float* mn, const float* mx) 
 // rides in the kernel arguments); 2 = the general top level (several objects, world-space triangles beside the instances).
 // A template value rather than a run-time flag: with the general code compiled in, the 96-register build of the
 // single-object kernel spilled 100 B instead of 56 B and config 5 lost 15 %.
-template <class IO, bool COUNT, int INST, bool SPH = false, bool SHP = false>
+// MOV = true (INST only): the scene has moving instances. `motions` holds one DevMotion per top-level leaf slot, IO::load
+// hands over the ray's time, and a slot whose row is animated is entered through the rows AnimatedTransform::interpolate
+// gives at that time (motion.h) instead of the slot's own; every other slot runs the code and the rows of the static build.
+template <class IO, bool COUNT, int INST, bool SPH = false, bool SHP = false, bool MOV = false>
 PB_DEV void trace_persistent(const DevBVH& bvh, const IO& io, unsigned int* __restrict__ work_counter,
-                             uint2* lds_stack, int spill_lane, unsigned long long* counters) {
+                             uint2* lds_stack, int spill_lane, unsigned long long* counters,
+                             const DevMotion* __restrict__ motions = nullptr) {
+    static_assert(!MOV || INST != 0, "moving instances need a two-level scene");
     const uint32_t n = io.n();
     const int lane = threadIdx.x & 63;
     const int count_mask = (1 << bvh.count_bits) - 1;
@@ -144,6 +151,25 @@ PB_DEV void trace_persistent(const DevBVH& bvh, const IO& io, unsigned int* __re
     auto enter_instance = [&](int slot) -> bool {
         const float4* m = bvh.instances + 7 * (size_t)slot;
         float4 r0 = m[0], r1 = m[1], r2 = m[2];
+        if (MOV) {
+            // AnimatedTransform::interpolate (transform.rs:2008-2046): the stored matrices at or beyond either end of the
+            // time range, T(u) R(u) S(u) between them
+            const DevMotion& mo = motions[slot];
+            if (mo.animated && !(w.time <= mo.start_time)) {
+                if (w.time >= mo.end_time) {
+                    const float4* e = reinterpret_cast<const float4*>(mo.end_w2o);
+                    r0 = e[0];
+                    r1 = e[1];
+                    r2 = e[2];
+                } else {
+                    MotionRows rows;
+                    motion_interpolate(mo, w.time, &rows);
+                    r0 = make_float4(rows.w2o[0], rows.w2o[1], rows.w2o[2], rows.w2o[3]);
+                    r1 = make_float4(rows.w2o[4], rows.w2o[5], rows.w2o[6], rows.w2o[7]);
+                    r2 = make_float4(rows.w2o[8], rows.w2o[9], rows.w2o[10], rows.w2o[11]);
+                }
+            }
+        }
         float x = w.wox, y = w.woy, z = w.woz;
         float ox = r0.x * x + r0.y * y + r0.z * z + r0.w;
         float oy = r1.x * x + r1.y * y + r1.z * z + r1.w;
@@ -263,7 +289,11 @@ PB_DEV void trace_persistent(const DevBVH& bvh, const IO& io, unsigned int* __re
             chunk_next += ((uint32_t)n_idle < avail) ? (uint32_t)n_idle : avail;
             if (take) {
                 s.index = io.token(my);
-                bool real = io.load(s.index, &s.r, &s.any);
+                bool real;
+                if constexpr (MOV)
+                    real = io.load(s.index, &s.r, &s.any, &w.time);
+                else
+                    real = io.load(s.index, &s.r, &s.any);
                 s.tmax = s.r.tmax;
                 s.hit_slot = -1;
                 s.b0 = s.b1 = s.b2 = 0.0f;

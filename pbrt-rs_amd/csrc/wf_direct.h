@@ -36,14 +36,17 @@ struct DirectState {
 // the builds for shapes take ML too. AO samples no light.
 // + 16 in the builds for scenes with a lobe row (wf_lobes.h): <DIRECT, 19> and <WHITTED, 19>, the level-3 set plus the lobe lists.
 // Both run one wave per SIMD: at two the Whitted build spills 104 bytes (profiles/r12_lobe_materials.txt).
-constexpr int kDirectShapes = 4, kDirectMapLights = 8, kDirectLobes = 16;
+// + 32 in the builds for scenes with moving instances (MOV as shade_bounce's): <DIRECT, 35>, <WHITTED, 35> and <AO, 32>. The path's
+// time is read from its continuation ray at entry and written back to it, and to every ray the launch emitted, at the end.
+constexpr int kDirectShapes = 4, kDirectMapLights = 8, kDirectLobes = 16, kDirectMoving = 32;
 template <int MODE, int LEVEL_SHP>
-__global__ void __launch_bounds__(256, (((LEVEL_SHP & 3) >= 1 && MODE == PBRT_INTEGRATOR_DIRECT) || (LEVEL_SHP & 16)) ? 1 : PB_DIRECT_WAVES) k_shade_direct(ShadeConsts sc, PathState ps, DirectState ds, Queues qin,
+__global__ void __launch_bounds__(256, (((LEVEL_SHP & 3) >= 1 && MODE == PBRT_INTEGRATOR_DIRECT) || (LEVEL_SHP & (16 | 32))) ? 1 : PB_DIRECT_WAVES) k_shade_direct(ShadeConsts sc, PathState ps, DirectState ds, Queues qin,
                                                         Queues qout, PassParams pp, TileList tiles, uint32_t n_in) {
     constexpr int LEVEL = LEVEL_SHP & 3;
     constexpr bool SHP = (LEVEL_SHP & kDirectShapes) != 0;
     constexpr bool ML = SHP || (LEVEL_SHP & kDirectMapLights) != 0;
     constexpr bool LOBES = (LEVEL_SHP & kDirectLobes) != 0;
+    constexpr bool MOV = (LEVEL_SHP & kDirectMoving) != 0;
     constexpr int BL = LOBES ? 4 : LEVEL;  // the BSDF type: LevelBsdf<BL>
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool active = i < n_in;
@@ -51,6 +54,7 @@ __global__ void __launch_bounds__(256, (((LEVEL_SHP & 3) >= 1 && MODE == PBRT_IN
     bool emit_cont = false, emit_mis = false, emit_shadow = false, mis_bool = false;
     constexpr bool GLOSSY = LEVEL >= 1;
     if (active && !(__float_as_int(ps.beta[p].w) & PF_VALID)) active = false;  // placeholder path outside pixel_bounds
+    float time = 0.0f;  // MOV: the path's time
 
     if (active) {
         float4 Lq = ps.L[p], bq = ps.beta[p];
@@ -63,6 +67,7 @@ __global__ void __launch_bounds__(256, (((LEVEL_SHP & 3) >= 1 && MODE == PBRT_IN
         float4 accq = ds.ld_acc[p];
         V3 ld_acc = V3{accq.x, accq.y, accq.z};
         size_t rbase = ray_index(ps, p, RS_CONT), hbase = hit_index(ps, p, RS_CONT);
+        if (MOV) time = ps.ray[rbase + 1].w;
         constexpr int mode = MODE;
         const bool sample_all = mode == PBRT_INTEGRATOR_DIRECT && ds.light_strategy == 0;
         // stages at a vertex: direct = light samples, Whitted = one per light (whitted.rs:75), AO = hemisphere samples
@@ -124,7 +129,10 @@ __global__ void __launch_bounds__(256, (((LEVEL_SHP & 3) >= 1 && MODE == PBRT_IN
             rd = V3{r0.w, r1.x, r1.y};
             float4 h0 = ps.hit[hbase];
             int hslot = __float_as_int(h0.x);
-            sf = surface_from_hit<SHP>(sc.bvh, hslot, hit_instance(ps, hbase), h0.y, h0.z, h0.w, rd);
+            if constexpr (MOV)
+                sf = surface_from_hit_moving(sc.bvh, sc.motions, time, hslot, hit_instance(ps, hbase), h0.y, h0.z, h0.w, rd);
+            else
+                sf = surface_from_hit<SHP>(sc.bvh, hslot, hit_instance(ps, hbase), h0.y, h0.z, h0.w, rd);
             mat = sc.materials[sf.material];
             fr = make_frame(sf);
             kd = V3{mat.kd[0], mat.kd[1], mat.kd[2]};
@@ -377,6 +385,11 @@ __global__ void __launch_bounds__(256, (((LEVEL_SHP & 3) >= 1 && MODE == PBRT_IN
         ps.beta[p] = make_float4(T.x, T.y, T.z, __int_as_float((depth << 8) | flags));
         ds.stage[p] = (stage & 0xffff) | (sp << 16);
         ds.ld_acc[p] = make_float4(ld_acc.x, ld_acc.y, ld_acc.z, 0.0f);
+        if (MOV) {  // the continuation slot keeps the time for the next launch (the unwind above rewrites it), emitted rays carry it
+            ps.ray[rbase + 1].w = time;
+            if (emit_mis) ps.ray[ray_index(ps, p, RS_MIS) + 1].w = time;
+            if (emit_shadow) ps.ray[ray_index(ps, p, RS_SHADOW) + 1].w = time;
+        }
     }
 
     __shared__ BlockAppend sh;

@@ -4,7 +4,11 @@
 
 namespace pb {
 
-__global__ void k_generate(PathState ps, Queues q, PassParams pp, DevCamera cam, TileList tiles) {
+// TIME: the ray carries its time, lerp(time sample, shutter_open, shutter_close) as the reference's cameras set it
+// (perspective.rs:107), in the free fourth component of its second float4 (wf_state.h). Only scenes with moving instances read
+// it, so only their k_generate_moving writes it; k_generate is the code it always was.
+template <bool TIME>
+PB_DEV void generate_camera_rays(const PathState& ps, const Queues& q, const PassParams& pp, const DevCamera& cam, const TileList& tiles) {
     uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t n = (uint32_t)pp.n_pix * pp.n_samples;
     if (p >= n) return;
@@ -67,7 +71,7 @@ __global__ void k_generate(PathState ps, Queues q, PassParams pp, DevCamera cam,
                 d = normalize(p_focus - o);
             }
         }
-        (void)time_u;  // ray.time only feeds animated transforms / media (out of scope)
+        (void)time_u;  // ray.time only feeds animated transforms (TIME, below) and media (out of scope)
         // Ray through camera_to_world with origin error (geometry.rs:865-881, 898-935)
         const float* m = cam.c2w;
         V3 ow = xform_point(m, o);
@@ -84,6 +88,7 @@ __global__ void k_generate(PathState ps, Queues q, PassParams pp, DevCamera cam,
             tmax -= dt;
         }
         store_ray(ps, p, RS_CONT, ow, dw, tmax);
+        if (TIME) ps.ray[ray_index(ps, p, RS_CONT) + 1].w = (1.0f - time_u) * cam.shutter_open + time_u * cam.shutter_close;
         samp_store(ps, p, sm);
         ps.pfilm[p] = make_float2(pfx, pfy);
         flags = PF_VALID | PF_ALIVE;
@@ -97,6 +102,9 @@ __global__ void k_generate(PathState ps, Queues q, PassParams pp, DevCamera cam,
     if (!valid) store_ray(ps, p, RS_CONT, V3{0.0f, 0.0f, 0.0f}, V3{0.0f, 0.0f, 1.0f}, -1.0f);
     q.trace[p] = p * 4u + RS_CONT;
     q.shade[p] = p;
+}
+__global__ void k_generate(PathState ps, Queues q, PassParams pp, DevCamera cam, TileList tiles) {
+    generate_camera_rays<false>(ps, q, pp, cam, tiles);
 }
 
 // ---- pbrt_hip_li: a batch of Integrator::li calls (integrator.rs:29-42). The caller made the rays (its own Camera) and
@@ -116,6 +124,7 @@ __global__ void k_li_generate(PathState ps, Queues q, const PbrtRay* __restrict_
         const float4* rp = reinterpret_cast<const float4*>(rays + p);
         float4 a = rp[0], b = rp[1];
         store_ray(ps, p, RS_CONT, V3{a.x, a.y, a.z}, V3{a.w, b.x, b.y}, b.z);
+        ps.ray[ray_index(ps, p, RS_CONT) + 1].w = b.w;  // PbrtRay.time as given: read by the kernels of moving scenes only
         flags = PF_VALID | PF_ALIVE;
     } else {
         store_ray(ps, p, RS_CONT, V3{0.0f, 0.0f, 0.0f}, V3{0.0f, 0.0f, 1.0f}, -1.0f);  // padding: misses at once, not a ray
@@ -149,7 +158,7 @@ __global__ void k_camera_rays_out(PathState ps, PassParams pp, TileList tiles, P
     float4 a = ps.ray[ri], b = ps.ray[ri + 1];
     float4* out = reinterpret_cast<float4*>(rays + p);
     out[0] = a;
-    out[1] = make_float4(b.x, b.y, b.z, 0.0f);
+    out[1] = b;  // .w: the ray's time (0 unless k_generate_moving wrote it)
     keys[p] = sample_sequence(pp, x, y, pp.sample0 + s_local);
     float2 pf = ps.pfilm[p];
     pfilm[2 * (size_t)p] = pf.x;
@@ -181,6 +190,16 @@ struct WavefrontRayIO {
         *r = TravRay{a.x, a.y, a.z, a.w, b.x, b.y, b.z};
         *any = slot >= RS_SHADOW;  // RS_SHADOW, RS_MIS_BOOL: only the boolean is wanted
         // t_max < 0 marks the placeholder ray of a path outside pixel_bounds (k_generate): not a ray of the frame
+        return !(b.z < 0.0f);
+    }
+    // the MOV builds also take the ray's time (the fourth component of its second float4)
+    PB_DEV bool load(uint32_t e, TravRay* r, bool* any, float* time) const {
+        uint32_t p = e >> 2, slot = e & 3u;
+        size_t ri = ray_index(ps, p, slot == RS_MIS_BOOL ? (uint32_t)RS_MIS : slot);
+        float4 a = ps.ray[ri], b = ps.ray[ri + 1];
+        *r = TravRay{a.x, a.y, a.z, a.w, b.x, b.y, b.z};
+        *any = slot >= RS_SHADOW;
+        *time = b.w;
         return !(b.z < 0.0f);
     }
     PB_DEV void store(uint32_t e, bool any, bool found, float t, float b0, float b1, float b2, int slot, int inst) const {
@@ -257,6 +276,24 @@ __global__ void __launch_bounds__(kTraceBlock, INST ? PB_INST_WAVES : PB_TRACE_W
     SpecialListIO<WavefrontRayIO<INST != 0>> io{WavefrontRayIO<INST != 0>{ps, queue, n, 1}, list, count};
     trace_persistent<SpecialListIO<WavefrontRayIO<INST != 0>>, false, INST, false>(bvh, io, work_counter, lds_stack + threadIdx.x,
                                                                         blockIdx.x * kTraceBlock + threadIdx.x, nullptr);
+}
+
+// ---- scenes with moving instances: named after every older kernel (kernel_select.h: the code generated for some kernels
+// depends on the order in which the instantiations are met) ----
+__global__ void k_generate_moving(PathState ps, Queues q, PassParams pp, DevCamera cam, TileList tiles) {
+    generate_camera_rays<true>(ps, q, pp, cam, tiles);
+}
+#ifndef PB_MOVING_TRACE_WAVES
+#define PB_MOVING_TRACE_WAVES 3  // 168 registers: at four waves two of the four builds spill 12 and 20 bytes
+#endif
+template <bool COUNT, int INST>
+__global__ void __launch_bounds__(kTraceBlock, PB_MOVING_TRACE_WAVES)
+    k_trace_moving(DevBVH bvh, const DevMotion* __restrict__ motions, PathState ps, const uint32_t* __restrict__ queue, uint32_t n,
+                   unsigned int* work_counter, unsigned long long* counters, int segments) {
+    __shared__ uint2 lds_stack[kStackLds * kTraceBlock];
+    WavefrontRayIO<true> io{ps, queue, n, segments};
+    trace_persistent<WavefrontRayIO<true>, COUNT, INST, false, false, true>(bvh, io, work_counter, lds_stack + threadIdx.x,
+                                                                            blockIdx.x * kTraceBlock + threadIdx.x, counters, motions);
 }
 
 }  // namespace pb

@@ -68,8 +68,10 @@ struct ShadeBins {
 // hands to the next launch is staged in LDS and written to the next generation at its position in qout.shade.
 // SHP: the scene may hold general quadric shapes (surface_from_hit, light_sample_li); k_shade_shapes below is that build, so the
 // kernels of every other scene compile as they did without it. ML: it may hold a projection or goniometric light (light_sample_li);
-// k_shade_maps below is that build, and k_shade_shapes takes it too.
-template <bool BIN, int LEVEL, bool SHP, bool ML = false>
+// k_shade_maps below is that build, and k_shade_shapes takes it too. MOV: it holds moving instances (sc.motions): the surface is
+// rebuilt through the instance's rows at the path's time, which rides in the fourth component of the ray's second float4 and is
+// copied to every ray the path emits (spawn_ray keeps the time); k_shade_moving below is that build.
+template <bool BIN, int LEVEL, bool SHP, bool ML = false, bool MOV = false>
 PB_DEV void shade_bounce(const ShadeConsts& sc, const PathState& ps, const Queues& qin, const Queues& qout, const PassParams& pp,
                          const TileList& tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
     constexpr bool GLOSSY = LEVEL >= 1;
@@ -111,6 +113,7 @@ PB_DEV void shade_bounce(const ShadeConsts& sc, const PathState& ps, const Queue
     bool emit_cont = false, emit_mis = false, emit_shadow = false, mis_bool = false;
 
     uint32_t cell = 0;  // sort cell of the rays this path emits
+    float time = 0.0f;  // MOV: the path's time
     if (active) {
         float4 Lq = ps.L[p], bq = ps.beta[p];
         V3 L = V3{Lq.x, Lq.y, Lq.z};
@@ -139,8 +142,12 @@ PB_DEV void shade_bounce(const ShadeConsts& sc, const PathState& ps, const Queue
             int hslot = __float_as_int(h0.x);
             bool found = hslot >= 0;
             Surf sf;
+            if (MOV) time = r1.w;
             if (found) {
-                sf = surface_from_hit<SHP>(sc.bvh, hslot, hit_instance(ps, hbase), h0.y, h0.z, h0.w, rd);
+                if constexpr (MOV)
+                    sf = surface_from_hit_moving(sc.bvh, sc.motions, time, hslot, hit_instance(ps, hbase), h0.y, h0.z, h0.w, rd);
+                else
+                    sf = surface_from_hit<SHP>(sc.bvh, hslot, hit_instance(ps, hbase), h0.y, h0.z, h0.w, rd);
                 if (qout.keys) cell = ray_sort_cell(sf.p.x, sf.p.y, sf.p.z, qout.key_lo, qout.key_inv);
             }
             // path.rs:80-88
@@ -282,6 +289,11 @@ PB_DEV void shade_bounce(const ShadeConsts& sc, const PathState& ps, const Queue
     __shared__ BlockAppend sh;
     const bool again = emit_cont || emit_mis || emit_shadow;
     const AppendSlots slots = block_reserve(sh, qout, emit_cont, emit_mis, emit_shadow, again);
+    if (MOV) {  // rays are only emitted from a continuation hit, where the time was read
+        if (emit_cont) staged.ray[RS_CONT][1][threadIdx.x].w = time;
+        if (emit_mis) staged.ray[RS_MIS][1][threadIdx.x].w = time;
+        if (emit_shadow) staged.ray[RS_SHADOW][1][threadIdx.x].w = time;
+    }
     stage.flush(ps, slots.shade, emit_cont, emit_mis, emit_shadow);
     block_write(qout, slots, p, slots.shade, emit_cont, emit_mis, emit_shadow, again, cell, mis_bool);
 }
@@ -309,6 +321,12 @@ template <bool BIN>
 __global__ void __launch_bounds__(256, 2) k_shade_lobes(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
                                                        TileList tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
     shade_bounce<BIN, 4, false, false>(sc, ps, qin, qout, pp, tiles, n_in, order);
+}
+// scenes with moving instances: the level-3 BSDF set, which serves every material table; bounded at two waves as level 3 is
+template <bool BIN>
+__global__ void __launch_bounds__(256, 2) k_shade_moving(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
+                                                        TileList tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
+    shade_bounce<BIN, 3, false, false, true>(sc, ps, qin, qout, pp, tiles, n_in, order);
 }
 
 }  // namespace pb

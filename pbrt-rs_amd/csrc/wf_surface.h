@@ -107,10 +107,8 @@ PB_DEV Surf make_surface(const DevBVH& bvh, int slot, float b0, float b1, float 
 }
 // Transform::operator()(SurfaceInteraction) of pbrt-v3 (transform.rs:620-627 is a TODO in the reference, D6):
 // object-space hit -> world space through the instance's matrices (primitive.rs:145-147).
-PB_DEV void instance_to_world(const DevBVH& bvh, int inst_slot, Surf* s) {
-    const float4* m = bvh.instances + 7 * (size_t)inst_slot;
-    float4 o0 = m[0], o1 = m[1], o2 = m[2];  // to_object rows (= inverse of to_world)
-    float4 w0 = m[3], w1 = m[4], w2 = m[5];  // to_world rows
+// o0..o2: to_object rows (= inverse of to_world), w0..w2: to_world rows, mat: the instance's material override or -1
+PB_DEV void instance_to_world_rows(float4 o0, float4 o1, float4 o2, float4 w0, float4 w1, float4 w2, int mat, Surf* s) {
     V3 p = s->p, pe = s->p_error;
     // point with incoming absolute error (geometry.rs:936-1000)
     float xp = w0.x * p.x + w0.y * p.y + w0.z * p.z + w0.w;
@@ -143,9 +141,44 @@ PB_DEV void instance_to_world(const DevBVH& bvh, int inst_slot, Surf* s) {
                          w2.x * wo.x + w2.y * wo.y + w2.z * wo.z});
     s->dpdu = V3{w0.x * du.x + w0.y * du.y + w0.z * du.z, w1.x * du.x + w1.y * du.y + w1.z * du.z,
                  w2.x * du.x + w2.y * du.y + w2.z * du.z};
-    int mat = __float_as_int(m[6].x);
     if (mat >= 0) s->material = mat;
     s->light = -1;  // instanced primitives carry no area lights
+}
+PB_DEV void instance_to_world(const DevBVH& bvh, int inst_slot, Surf* s) {
+    const float4* m = bvh.instances + 7 * (size_t)inst_slot;
+    instance_to_world_rows(m[0], m[1], m[2], m[3], m[4], m[5], __float_as_int(m[6].x), s);
+}
+// The rows of a moving scene's instance slot at the path's time, as the traversal kernel entered it (trace_persistent.h,
+// MOV): the slot's own for a static instance and up to the start time, the stored end rows from the end time on,
+// AnimatedTransform::interpolate's (motion.h) between them.
+PB_DEV void instance_rows_at(const DevBVH& bvh, const DevMotion* __restrict__ motions, int inst_slot, float time, float4* o, float4* w) {
+    const float4* m = bvh.instances + 7 * (size_t)inst_slot;
+    for (int k = 0; k < 3; ++k) {
+        o[k] = m[k];
+        w[k] = m[3 + k];
+    }
+    const DevMotion& mo = motions[inst_slot];
+    if (!mo.animated || time <= mo.start_time) return;
+    if (time >= mo.end_time) {
+        const float4* eo = reinterpret_cast<const float4*>(mo.end_w2o);
+        const float4* ew = reinterpret_cast<const float4*>(mo.end_o2w);
+        for (int k = 0; k < 3; ++k) {
+            o[k] = eo[k];
+            w[k] = ew[k];
+        }
+        return;
+    }
+    MotionRows rows;
+    motion_interpolate(mo, time, &rows);
+    for (int k = 0; k < 3; ++k) {
+        o[k] = make_float4(rows.w2o[4 * k], rows.w2o[4 * k + 1], rows.w2o[4 * k + 2], rows.w2o[4 * k + 3]);
+        w[k] = make_float4(rows.o2w[4 * k], rows.o2w[4 * k + 1], rows.o2w[4 * k + 2], rows.o2w[4 * k + 3]);
+    }
+}
+// TransformedPrimitive::intersect's second half over an AnimatedTransform (primitive.rs:140-147): the same interpolation at
+// the path's time, then the formulas of instance_to_world
+PB_DEV void instance_to_world_moving(const DevBVH& bvh, const float4* o, const float4* w, int inst_slot, Surf* s) {
+    instance_to_world_rows(o[0], o[1], o[2], w[0], w[1], w[2], __float_as_int(bvh.instances[7 * (size_t)inst_slot + 6].x), s);
 }
 // Sphere::intersect past the hit test (sphere.rs:38-92) for a full sphere placed by translate(centre): partial
 // derivatives, SurfaceInteraction::new, then pbrt-v3's Transform(SurfaceInteraction) through that translation (every
@@ -287,6 +320,18 @@ PB_DEV Surf surface_from_hit(const DevBVH& bvh, int slot, int inst_slot, float b
     }
     return make_surface(bvh, slot, b0, b1, b2, rd);
 }
+// ... in a scene with moving instances (two levels, triangles only): `time` is the path's
+PB_DEV Surf surface_from_hit_moving(const DevBVH& bvh, const DevMotion* __restrict__ motions, float time, int slot, int inst_slot,
+                                    float b0, float b1, float b2, V3 rd) {
+    if (inst_slot < 0) return make_surface(bvh, slot, b0, b1, b2, rd);
+    float4 o[3], w[3];
+    instance_rows_at(bvh, motions, inst_slot, time, o, w);
+    V3 d_obj = V3{o[0].x * rd.x + o[0].y * rd.y + o[0].z * rd.z, o[1].x * rd.x + o[1].y * rd.y + o[1].z * rd.z,
+                  o[2].x * rd.x + o[2].y * rd.y + o[2].z * rd.z};
+    Surf s = make_surface(bvh, slot, b0, b1, b2, d_obj);
+    instance_to_world_moving(bvh, o, w, inst_slot, &s);
+    return s;
+}
 // SurfaceInteraction::n of a hit at barycentrics (b0, b1, b2): the geometric normal, on the shading normal's side
 template <bool SHP = false>
 PB_DEV V3 tri_interaction_normal(const DevBVH& bvh, int slot, float b0, float b1, float b2) {
@@ -416,6 +461,7 @@ struct ShadeConsts {
     const DevDisney* disney;  // [n_materials]: the blocks of the kMatDisney rows (wf_disney.h)
     const DevLightMap* light_maps;  // side table of the projection / goniometric lights (DevLight::slot), null when there are none
     const DevLobeRow* lobe_rows;  // [n_materials]: the lobe lists of the kMatLobes rows (wf_lobes.h)
+    const DevMotion* motions;     // [top-level leaf slots]: the side table of a scene with moving instances (motion.h), else null
 };
 
 // ---- InfiniteAreaLight with an image map (DevEnvMap): one lookup and one Distribution2D for le, sample_li and pdf_li ----

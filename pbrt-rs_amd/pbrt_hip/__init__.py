@@ -44,6 +44,7 @@ EXPORTS = [
     "pbrt_hip_shape_world_bounds", "pbrt_hip_scene_create_with_shapes",
     "pbrt_hip_scene_set_light_map", "pbrt_hip_light_map_tables", "pbrt_hip_light_sample_li",
     "pbrt_hip_scene_set_lobe_material", "pbrt_hip_material_lobes",
+    "pbrt_hip_instance_motion_bounds", "pbrt_hip_scene_create_two_level_moving",
 ]
 MAT_NONE, MAT_MATTE, MAT_MIRROR, MAT_GLASS, MAT_PLASTIC, MAT_METAL = (scenes.MAT_NONE, scenes.MAT_MATTE, scenes.MAT_MIRROR,
                                                                       scenes.MAT_GLASS, scenes.MAT_PLASTIC, scenes.MAT_METAL)
@@ -164,6 +165,9 @@ def lib():
                                                       vp, i32, vp, ctypes.POINTER(vp)]
         L.pbrt_hip_scene_create_two_level.argtypes = [vp, vp, i32, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp,
                                                       ctypes.POINTER(vp)]
+        L.pbrt_hip_scene_create_two_level_moving.argtypes = [vp, vp, i32, vp, vp, vp, i32, vp, i32, vp, i32, vp, vp, vp, i32, vp, i32, vp, i32,
+                                                             vp, ctypes.POINTER(vp)]
+        L.pbrt_hip_instance_motion_bounds.argtypes = [vp, vp, vp, vp, i32, vp, vp]
         L.pbrt_hip_scene_destroy.argtypes = [vp]
         L.pbrt_hip_scene_destroy.restype = None
         L.pbrt_hip_scene_wide_records.argtypes = [vp, ctypes.POINTER(i32), ctypes.POINTER(ctypes.c_char_p)]
@@ -401,6 +405,37 @@ def instance_bounds(object_min, object_max, instances):
     return lo, hi
 
 
+def make_instance_motions(scene):
+    """scene["instance_motion"] = {instance: scenes.instance_motion(...)} -> PbrtInstanceMotion array, one per instance
+    (animated = 0 for the instances the dictionary does not name); None when the scene has no such entry."""
+    motion = scene.get("instance_motion")
+    if motion is None:
+        return None
+    n = len(scene["instances"])
+    out = np.zeros(n, dtype=scenes.INSTANCE_MOTION_DTYPE)
+    for i, rec in motion.items():
+        if not 0 <= int(i) < n:
+            raise PbrtHipError(f"instance_motion names instance {i}: the scene has {n}")
+        out[int(i)] = np.asarray(rec, dtype=scenes.INSTANCE_MOTION_DTYPE).reshape(())
+    return out
+
+
+def instance_motion_bounds(object_min, object_max, instances, motions):
+    """TransformedPrimitive::world_bound per moving instance (pbrt_hip_instance_motion_bounds): boxes that hold the object
+    bounds at every time. motions: PbrtInstanceMotion records (scenes.INSTANCE_MOTION_DTYPE), one per instance. Host only."""
+    n = len(instances)
+    instances = np.ascontiguousarray(instances, dtype=INSTANCE_DTYPE)
+    motions = np.ascontiguousarray(motions, dtype=scenes.INSTANCE_MOTION_DTYPE)
+    if len(motions) != n:
+        raise PbrtHipError("instance_motion_bounds: one motion record per instance")
+    lo, hi = np.zeros((n, 3), dtype=np.float32), np.zeros((n, 3), dtype=np.float32)
+    omin, omax = np.ascontiguousarray(object_min, dtype=np.float32), np.ascontiguousarray(object_max, dtype=np.float32)
+    rc = lib().pbrt_hip_instance_motion_bounds(_p(omin), _p(omax), _p(instances), _p(motions), n, _p(lo), _p(hi))
+    if rc != 0:
+        raise PbrtHipError(f"pbrt_hip_instance_motion_bounds failed ({rc}): a non-finite, non-affine or singular matrix, or end_time <= start_time")
+    return lo, hi
+
+
 def shape_world_bounds(shapes):
     """Shape::world_bound per PbrtShape record (scenes.SHAPE_DTYPE): (n, 3) mins and (n, 3) maxs. Host only."""
     shapes = np.ascontiguousarray(shapes, dtype=scenes.SHAPE_DTYPE)
@@ -416,11 +451,15 @@ def build_general_two_level(scene, max_prims_in_node=4, split_method=SPLIT_SAH):
     world bounds followed by the world triangles' bounds. Returns (object trees [(nodes, order)], instances, tlas_nodes, tlas_order)."""
     trees = [bvh_build(o["positions"], o["indices"], max_prims_in_node, split_method) for o in scene["objects"]]
     inst = make_instances(scene)
+    motions = make_instance_motions(scene)   # moving instances: the top-level tree is built over their motion bounds
     io = np.asarray(scene["instance_object"], dtype=np.int32)
     lo, hi = np.zeros((len(inst), 3), dtype=np.float32), np.zeros((len(inst), 3), dtype=np.float32)
     for k, (nodes, _) in enumerate(trees):
         sel = np.flatnonzero(io == k)
-        if len(sel):
+        if len(sel) and motions is not None:
+            a, b = instance_motion_bounds(nodes[0]["bmin"], nodes[0]["bmax"], np.ascontiguousarray(inst[sel]), np.ascontiguousarray(motions[sel]))
+            lo[sel], hi[sel] = a, b
+        elif len(sel):
             a, b = instance_bounds(nodes[0]["bmin"], nodes[0]["bmax"], np.ascontiguousarray(inst[sel]))
             lo[sel], hi[sel] = a, b
     w = scene["world"]
@@ -471,6 +510,14 @@ class Scene:
         self.ctx = ctx
         if "objects" in scene:
             self._init_two_level(scene, max_prims_in_node, split_method, bvh)
+            return
+        if "instances" in scene and scene.get("instance_motion") is not None:
+            # moving instances of one aggregate: the general creation call with one object and no world-space triangles
+            one = dict(scene, objects=[dict(positions=scene["positions"], indices=scene["indices"], tri_material=scene["tri_material"])],
+                       instance_object=np.zeros(len(scene["instances"]), dtype=np.int32),
+                       world=dict(positions=np.zeros((0, 3), np.float32), indices=np.zeros((0, 3), np.int32),
+                                  tri_material=np.zeros(0, np.int32), tri_light=np.zeros(0, np.int32)))
+            self._init_two_level(one, max_prims_in_node, split_method, bvh)
             return
         if "instances" in scene:
             self._init_instanced(scene, max_prims_in_node, split_method, bvh)
@@ -643,6 +690,18 @@ class Scene:
         materials = np.ascontiguousarray(scene["materials"], dtype=MATERIAL_DTYPE)
         lights = np.ascontiguousarray(scene["lights"], dtype=LIGHT_DTYPE)
         h = ctypes.c_void_p()
+        self.motions = make_instance_motions(scene)
+        if self.motions is not None:
+            rc = lib().pbrt_hip_scene_create_two_level_moving(
+                self.ctx.h, ctypes.addressof(objs), len(objs), _p(self.instances), _p(self.motions), _p(io), len(self.instances),
+                _p(wp) if len(wi) else None, len(wp) if len(wi) else 0, _p(wi) if len(wi) else None, len(wi),
+                _p(wm) if len(wi) else None, _p(wl) if len(wi) else None, _p(materials), len(materials),
+                _p(lights) if len(lights) else None, len(lights), _p(self.tlas_nodes), len(self.tlas_nodes), _p(self.tlas_order),
+                ctypes.byref(h))
+            self.ctx.check(rc, "pbrt_hip_scene_create_two_level_moving")
+            self.h = h
+            self.ctx._scenes.add(self)
+            return
         rc = lib().pbrt_hip_scene_create_two_level(
             self.ctx.h, ctypes.addressof(objs), len(objs), _p(self.instances), _p(io), len(self.instances),
             _p(wp) if len(wi) else None, len(wp) if len(wi) else 0, _p(wi) if len(wi) else None, len(wi),

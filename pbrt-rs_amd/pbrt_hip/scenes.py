@@ -21,6 +21,8 @@ RAY_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("t_max", "<f4"), ("time
 HIT_DTYPE = np.dtype([("t", "<f4"), ("b0", "<f4"), ("b1", "<f4"), ("b2", "<f4"), ("prim_id", "<i4"),
                       ("instance_id", "<i4"), ("pad", "<i4", 2)])
 INSTANCE_DTYPE = np.dtype([("to_world", "<f4", 16), ("to_object", "<f4", 16), ("material", "<i4"), ("pad", "<i4", 3)])
+INSTANCE_MOTION_DTYPE = np.dtype([("end_to_world", "<f4", 16), ("start_time", "<f4"), ("end_time", "<f4"), ("animated", "<i4"),
+                                  ("pad", "<i4")])   # PbrtInstanceMotion
 # PbrtShape (pbrt_hip_scene_create_with_shapes): scene["shapes"] is an array of these, shape i is primitive n_tris + i
 SHAPE_DTYPE = np.dtype([("type", "<i4"), ("reverse_orientation", "<i4"), ("material", "<i4"), ("light", "<i4"), ("radius", "<f4"),
                         ("z_min", "<f4"), ("z_max", "<f4"), ("inner_radius", "<f4"), ("phi_max", "<f4"), ("pad", "<f4", 3),
@@ -637,6 +639,15 @@ def world_space_instances(scene):
     mat = np.where(im[:, None] >= 0, im[:, None], scene["tri_material"][None, :]).astype(np.int32)
     return dict(positions=pos.reshape(-1, 3), indices=idx.reshape(-1, 3), tri_material=mat.reshape(-1),
                 materials=scene["materials"], tri_light=np.full(n * nt, -1, dtype=np.int32), lights=scene["lights"])
+
+
+def instance_motion(end_to_world, start_time, end_time):
+    """A PbrtInstanceMotion record (AnimatedTransform, transform.rs:870-912): the instance's own to_world is its transform at
+    start_time, end_to_world (4x4, last row 0 0 0 1) the one at end_time. scene["instance_motion"] = {instance: record}."""
+    rec = np.zeros((), dtype=INSTANCE_MOTION_DTYPE)
+    rec["end_to_world"] = np.asarray(end_to_world, dtype=np.float32).reshape(16)
+    rec["start_time"], rec["end_time"], rec["animated"] = start_time, end_time, 1
+    return rec
 
 
 def instanced_camera(width, height, extent=4.0):

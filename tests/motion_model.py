@@ -9,6 +9,8 @@ src/core/transform.rs:264-330, 870-912, 2008-2046 and src/core/quaternion.rs), i
   closest_hits            brute-force closest hit over all triangles of all instances, every ray at its own time, with the
                           margins the tests exclude rays by
   hit_normal              the geometric normal of a hit triangle in world space at the ray's time
+  shading_frames          normal through (M^-1)^T, dpdu through M and the BSDF's frame at hits of one instance at one time, with the
+                          frames a wrong transform would give; to_local takes world vectors into a frame
 """
 import numpy as np
 
@@ -184,6 +186,32 @@ def closest_hits(instances, rays_o, rays_d, t_max, time, margin=1e-4):
         close_pair = hit & np.isfinite(second) & ((second - t_best) <= margin * np.abs(t_best))
     return dict(hit=hit, t=np.where(hit, t_best, np.inf), inst=np.where(hit, ids[best, 0], -1), prim=np.where(hit, ids[best, 1], -1),
                 b=np.where(hit[:, None], b[rows, best], 0.0), unsure=near_edge | close_pair)
+
+
+FRAME_VARIANTS = ("right", "normal_through_m", "dpdu_in_object_space")
+
+
+def shading_frames(motion, positions, indices, prim, time, variant="right"):
+    """The shading frame of hits on triangles `prim` (n,) of one instance at one time, in world space, from M = M(time):
+    n the unit normal (p0 - p2) x (p1 - p2) of the OBJECT-space triangle taken through (M^-1)^T, dpdu = p1 - p0 (the default
+    parametrisation (0, 0), (1, 0), (1, 1)) taken through M, ss = dpdu normalised, ts = n x ss (BSDF::new). Returns a dict of
+    (n, 3) arrays n, dpdu, ss, ts. The wrong frames a defective kernel would give: `normal_through_m` takes the normal through M
+    itself, `dpdu_in_object_space` leaves dpdu untransformed."""
+    m = motion.interpolate(np.float64(time))[:3, :3]
+    p = np.asarray(positions, dtype=np.float64)[np.asarray(indices)[np.asarray(prim)]]
+    n_obj = np.cross(p[:, 0] - p[:, 2], p[:, 1] - p[:, 2])
+    n = n_obj @ (m.T if variant == "normal_through_m" else np.linalg.inv(m))     # rows: (M^-1)^T n = n^T M^-1
+    n /= np.linalg.norm(n, axis=1, keepdims=True)
+    dpdu = p[:, 1] - p[:, 0]
+    if variant != "dpdu_in_object_space":
+        dpdu = dpdu @ m.T
+    ss = dpdu / np.linalg.norm(dpdu, axis=1, keepdims=True)
+    return dict(n=n, dpdu=dpdu, ss=ss, ts=np.cross(n, ss))
+
+
+def to_local(frame, v):
+    """world vectors (n, 3) in the frame's (ss, ts, n) coordinates"""
+    return np.stack([(v * frame["ss"]).sum(axis=1), (v * frame["ts"]).sum(axis=1), (v * frame["n"]).sum(axis=1)], axis=1)
 
 
 def hit_normal(motion, positions, indices, prim, time):

@@ -18,124 +18,14 @@ from pbrt_hip import scenes
 
 pytestmark = pytest.mark.gpu
 
-T0, T1 = 0.25, 1.75
-N_RAYS = 4096
-QUAD = (np.array([[-0.5, -0.5, 0], [0.5, -0.5, 0], [0.5, 0.5, 0], [-0.5, 0.5, 0]], dtype=np.float32),
-        np.array([[0, 1, 2], [0, 2, 3]], dtype=np.int32))
-_c = np.array([[x, y, z] for z in (-0.25, 0.25) for y in (-0.3, 0.3) for x in (-0.4, 0.4)], dtype=np.float32)
-BOX = (_c, np.array([[0, 2, 1], [1, 2, 3], [4, 5, 6], [5, 7, 6], [0, 1, 4], [1, 5, 4], [2, 6, 3], [3, 6, 7], [0, 4, 2], [2, 4, 6],
-                     [1, 3, 5], [3, 7, 5]], dtype=np.int32))
-OBJECTS = (QUAD, BOX)
-KD, LIGHT_L = 0.5, 3.0
-
-
-def rot(axis, degrees):
-    a = np.asarray(axis, dtype=np.float64)
-    a = a / np.linalg.norm(a)
-    h = np.radians(degrees) / 2
-    m = np.eye(4)
-    m[:3, :3] = mm.quat_to_matrix(np.concatenate([a * np.sin(h), [np.cos(h)]]))
-    return m
-
-
-def tr(x, y, z):
-    m = np.eye(4)
-    m[:3, 3] = (x, y, z)
-    return m
-
-
-def sc(x, y, z):
-    return np.diag([x, y, z, 1.0])
-
-
-def f32(m):
-    return np.asarray(m, dtype=np.float32).astype(np.float64)
-
-
-# (object, start matrix, end matrix or None): translation, 170 degree rotation, rotation + translation + non-uniform scale, the
-# normalised-lerp branch, and a static box
-FIVE = [(0, tr(-2, 0, 0) @ rot((0, 1, 0), 20), tr(-2, 1, 0.5) @ rot((0, 1, 0), 20)),
-        (1, rot((0.3, 1.0, 0.2), 5), rot((0.3, 1.0, 0.2), 175)),
-        (1, tr(2, 0, 0) @ rot((1, 0.2, -0.4), -30) @ sc(1.0, 0.7, 1.3), tr(2.3, 0.6, 0.2) @ rot((0.1, 1, 0.5), 75) @ sc(1.6, 0.5, 0.9)),
-        (0, tr(0, -2, 0) @ rot((0, 0, 1), 10), tr(0.2, -2, 0) @ rot((0, 0, 1), 13)),
-        (1, tr(0, 2, 0) @ rot((1, 1, 0), 35), None)]
-CENTRES = np.array([[-2, 0.5, 0.25], [0, 0, 0], [2.15, 0.3, 0.1], [0.1, -2, 0], [0, 2, 0]], dtype=np.float64)
-
-
-MATERIALS = [(scenes.MAT_MATTE, (KD, KD, KD), (0, 0, 0), 1.0), (scenes.MAT_GLASS, (1.0, 1.0, 1.0), (1.0, 1.0, 1.0), 1.5),
-             (scenes.MAT_MIRROR, (0.9, 0.9, 0.9), (0, 0, 0), 1.0)]
-
-
-def make_scene(instances, world=None, lights=(), moving=True, objects=OBJECTS, instance_material=None):
-    """A general two-level scene of `objects`. instances: (object, m0, m1 or None). moving=False: no "instance_motion" entry at all
-    (pbrt_hip_scene_create_two_level), every instance at m0. One object and no world triangles: the traversal kernels' INST = 1
-    builds; otherwise INST = 2."""
-    n = len(instances)
-    inst = np.zeros((n, 2, 4, 4), dtype=np.float32)
-    motion = {}
-    for i, (_, m0, m1) in enumerate(instances):
-        inst[i, 0] = np.asarray(m0, dtype=np.float32)
-        inst[i, 1] = np.linalg.inv(f32(m0)).astype(np.float32)
-        if m1 is not None:
-            motion[i] = scenes.instance_motion(m1, T0, T1)
-    inst[:, :, 3, :] = (0, 0, 0, 1)
-    if world is None:
-        world = dict(positions=np.zeros((0, 3), np.float32), indices=np.zeros((0, 3), np.int32), tri_material=np.zeros(0, np.int32),
-                     tri_light=np.zeros(0, np.int32))
-    out = dict(objects=[dict(positions=p, indices=i, tri_material=np.zeros(len(i), np.int32)) for p, i in objects], instances=inst,
-               instance_object=np.array([k for k, _, _ in instances], dtype=np.int32), instance_material=np.full(n, -1, np.int32) if instance_material is None else np.asarray(instance_material, dtype=np.int32),
-               world=world, materials=scenes._materials(MATERIALS), lights=scenes._lights(list(lights)))
-    if moving:
-        out["instance_motion"] = motion
-    return out
-
-
-def model_instances(instances, objects=OBJECTS, t0=T0, t1=T1):
-    return [(mm.Motion(f32(m0), None if m1 is None else f32(m1), t0, t1), *objects[k]) for k, m0, m1 in instances]
-
-
-def rays_at(centres, seed, times, spread=0.6, radius=6.0):
-    """N_RAYS rays from a sphere of `radius` towards points around the centres, each at one of `times`; no zero direction component"""
-    rng = np.random.default_rng(seed)
-    v = rng.normal(size=(N_RAYS, 3))
-    o = radius * v / np.linalg.norm(v, axis=1, keepdims=True)
-    target = centres[rng.integers(0, len(centres), N_RAYS)] + rng.uniform(-spread, spread, size=(N_RAYS, 3))
-    rays = np.zeros(N_RAYS, dtype=scenes.RAY_DTYPE)
-    rays["o"], rays["d"] = o, target - o
-    rays["t_max"] = np.inf
-    rays["time"] = np.asarray(times, dtype=np.float32)[rng.integers(0, len(times), N_RAYS)]
-    assert np.all(rays["d"] != 0)
-    return rays
-
-
-def some_times(seed):
-    """8 times: six inside (T0, T1), one before the start, one after the end"""
-    rng = np.random.default_rng(seed)
-    return np.concatenate([rng.uniform(T0, T1, 6), [T0 - 0.4, T1 + 0.3]]).astype(np.float32)
-
-
-def model_hits(instances, rays, objects=OBJECTS):
-    return mm.closest_hits(model_instances(instances, objects), rays["o"], rays["d"], rays["t_max"], rays["time"].astype(np.float64))
-
-
-def check_ids(name, hits, m):
-    keep = ~m["unsure"]
-    print(f"{name}: {m['hit'].sum()} model hits, {(~keep).sum()} of {len(keep)} rays excluded")
-    assert 1.0 - keep.mean() <= 0.02, name
-    assert np.array_equal((hits["prim_id"] >= 0)[keep], m["hit"][keep]), name
-    assert np.array_equal(hits["prim_id"][keep], m["prim"][keep]), name
-    assert np.array_equal(hits["instance_id"][keep], m["inst"][keep]), name
-    sel = keep & m["hit"]
-    return sel, np.abs(hits["t"][sel].astype(np.float64) - m["t"][sel]) / m["t"][sel]
+# the scenes' parts and helpers live in tests/motion_cases.py, which test_gpu_motion_paths.py shares
+from motion_cases import (BLUR_SHIFT, BLUR_START, BOX, CENTRES, FIVE, FLOOR, KD, LIGHT_L, N_RAYS, NORMAL_TOL, QUAD, RES, SPP, SUN, T0, T1,  # noqa: F401
+                          blur_scene, check_ids, make_scene, model_hits, model_instances, rays_at, rot, some_times, tr)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # a scene in which nothing moves is the old scene
 # ---------------------------------------------------------------------------------------------------------------------
-FLOOR = dict(positions=np.array([[-6, -6, -3], [6, -6, -3], [6, 6, -3], [-6, 6, -3]], dtype=np.float32),
-             indices=np.array([[0, 1, 2], [0, 2, 3]], dtype=np.int32), tri_material=np.zeros(2, np.int32), tri_light=np.full(2, -1, np.int32))
-SUN = (scenes.distant_light((0.2, 0.3, 1.0), (LIGHT_L, LIGHT_L, LIGHT_L)),)
-
 
 def test_all_static_scene_is_the_old_scene(hip_ctx):
     static = [(k, m0, None) for k, m0, _ in FIVE]
@@ -267,11 +157,6 @@ def test_hits_against_the_model(hip_ctx):
 # ---------------------------------------------------------------------------------------------------------------------
 # normals: Lambert's law on a rotating box
 # ---------------------------------------------------------------------------------------------------------------------
-# the tolerance of tests/test_gpu_shapes.py's Lambert test: N_FACTOR * NORMAL_PROBE_SPHERE_PATH_WORST * cond_2 of the transform's
-# linear part, which is 1 for a rotation
-NORMAL_TOL = 4.0 * 4.9379e-05
-
-
 def test_normals_of_a_rotating_box(hip_ctx):
     spin = [(0, rot((0.2, 0.1, 1.0), 0), rot((0.2, 0.1, 1.0), 120))]   # of the one object (BOX,): the INST = 1 kernels
     wi = np.array([0.3, -0.5, 0.8]) / np.linalg.norm([0.3, -0.5, 0.8])
@@ -339,18 +224,6 @@ def test_shadow_of_a_moving_occluder(hip_ctx):
 # ---------------------------------------------------------------------------------------------------------------------
 # motion blur: the coverage trapezoid
 # ---------------------------------------------------------------------------------------------------------------------
-RES, SPP = 64, 64
-BLUR_START, BLUR_SHIFT = (-0.73, 0.02, 0.0), 1.5
-
-
-def blur_scene():
-    x, y, z = BLUR_START
-    scene = make_scene([(0, tr(x, y, z), tr(x + BLUR_SHIFT, y, z))], lights=(scenes.distant_light((0, 0, 1.0), (LIGHT_L, LIGHT_L, LIGHT_L)),),
-                       objects=(QUAD,))
-    scene["instance_motion"] = {0: scenes.instance_motion(tr(x + BLUR_SHIFT, y, z), 0.0, 1.0)}
-    return scene
-
-
 def pixel_edges(cam):
     """world x of the RES + 1 column edges and world y of the row edges (orthographic: raster -> camera -> world is affine)"""
     m = cam["camera_to_world"].astype(np.float64).reshape(4, 4) @ cam["raster_to_camera"].astype(np.float64).reshape(4, 4)

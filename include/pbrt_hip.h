@@ -730,6 +730,39 @@ int pbrt_hip_li_device(PbrtHipScene* scene, const PbrtLiParams* params, const Pb
 int pbrt_hip_camera_rays(PbrtHipScene* scene, const PbrtCamera* camera, const PbrtRenderParams* params, int64_t capacity,
                          PbrtRay* rays, uint64_t* stream_keys, float* p_film, int32_t* pixel_sample, int64_t* n_out);
 
+/* ---- camera motion blur: Camera::camera_to_world as an AnimatedTransform (src/core/camera.rs:80-115) ----
+ * Every generate_ray of the reference ends by taking the camera-space ray through the animated camera_to_world at the ray's
+ * time (perspective.rs:108-110, geometry.rs:1177-1190). PbrtCamera.camera_to_world is the camera at start_time,
+ * end_camera_to_world the one at end_time; shape and rules are PbrtInstanceMotion's: both matrices row-major with last row
+ * 0 0 0 1, decomposed in double precision, the end quaternion negated when the two have a negative dot product. A ray of time
+ * t = lerp(time sample, shutter_open, shutter_close) goes through the start matrix as given for t <= start_time, the end matrix
+ * as given for t >= end_time and T(u) R(u) S(u), recomposed in float32, between them. animated == 0, or a NULL pointer: the
+ * static camera, and the calls below ARE pbrt_hip_render / _render_device / _camera_rays (which are these with NULL). Only the
+ * ray generator reads the camera, so a static scene keeps its traversal kernels (the 4-wide records included). With an
+ * animated camera the ray's time is always written, so pbrt_hip_camera_rays_moving_camera returns it in PbrtRay.time for
+ * static scenes too and pbrt_hip_li over those rays is the render. A camera with scale is accepted (the reference only
+ * warns, camera.rs:105). PBRT_HIP_ERR_INVALID before anything is launched, the context still usable and pbrt_hip_last_error
+ * saying which, for a non-finite or non-affine matrix, a singular start or end matrix, or end_time <= start_time. */
+typedef struct PbrtCameraMotion {
+    float end_camera_to_world[16];
+    float start_time, end_time;
+    int32_t animated;
+    int32_t pad;
+} PbrtCameraMotion;
+int pbrt_hip_render_moving_camera(PbrtHipScene* scene, const PbrtCamera* camera, const PbrtCameraMotion* motion,
+                                  const PbrtRenderParams* params, float* film_xyzw, PbrtRenderStats* stats);
+int pbrt_hip_render_device_moving_camera(PbrtHipScene* scene, const PbrtCamera* camera, const PbrtCameraMotion* motion,
+                                         const PbrtRenderParams* params, float* d_film_xyzw, PbrtRenderStats* stats);
+int pbrt_hip_camera_rays_moving_camera(PbrtHipScene* scene, const PbrtCamera* camera, const PbrtCameraMotion* motion,
+                                       const PbrtRenderParams* params, int64_t capacity, PbrtRay* rays, uint64_t* stream_keys,
+                                       float* p_film, int32_t* pixel_sample, int64_t* n_out);
+/* AnimatedTransform::interpolate (src/core/transform.rs:2010-2030) of the camera's two matrices at `time`, in double precision,
+ * rounded to float once. Host only, no GPU and no context: at or before start_time the start matrix, at or after end_time the
+ * end matrix, both as given; with motion NULL or animated == 0 the camera's own matrix. Refuses what the entry points above
+ * refuse; pbrt_hip_last_error(NULL) then says which, for the calling thread. */
+int pbrt_hip_camera_motion_interpolate(const PbrtCamera* camera, const PbrtCameraMotion* motion, float time,
+                                       float out_camera_to_world[16]);
+
 /* A film on the context's device ({xyz[3], filter_weight_sum} per pixel, zero-filled) for a host that has no HIP binding of
  * its own (a Rust or C caller of this header): pbrt_hip_render_device renders into it, pbrt_hip_film_reduce merges the ranks'
  * films in it, pbrt_hip_film_download (which first waits for the context's stream) copies it to the host. Destroy before the

@@ -581,11 +581,26 @@ class Camera {
 public:
     virtual ~Camera() = default;
     PbrtCamera cam;
+    PbrtCameraMotion motion;  // animated == 0 unless set_camera_to_world made the camera move
     std::shared_ptr<Film> film;
+    // camera_to_world as an AnimatedTransform (camera.rs:80-115): the camera at start_time and at end_time, row-major with last
+    // row (0, 0, 0, 1), in place of the look_at matrix of the constructor. Forwarding only: the library decomposes and
+    // interpolates (pbrt_hip_render_moving_camera); a ray's time comes from the shutter (cam.shutter_open / shutter_close).
+    void set_camera_to_world(const AnimatedTransform& camera_to_world) {
+        for (int k = 0; k < 12; ++k) {
+            cam.camera_to_world[k] = (float)camera_to_world.start_transform[k];
+            motion.end_camera_to_world[k] = (float)camera_to_world.end_transform[k];
+        }
+        for (int k = 12; k < 16; ++k) cam.camera_to_world[k] = motion.end_camera_to_world[k] = k == 15 ? 1.0f : 0.0f;
+        motion.start_time = camera_to_world.start_time;
+        motion.end_time = camera_to_world.end_time;
+        motion.animated = 1;
+    }
 
 protected:
     Camera(const Point3f& eye, const Point3f& look, const Vector3f& up_in, std::shared_ptr<Film> film_in, PbrtCameraKind kind) : film(std::move(film_in)) {
         std::memset(&cam, 0, sizeof(cam));
+        std::memset(&motion, 0, sizeof(motion));
         double d[3] = {look.x - eye.x, look.y - eye.y, look.z - eye.z}, up[3] = {up_in.x, up_in.y, up_in.z}, right[3], new_up[3];
         auto norm = [](double v[3]) {
             double l = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
@@ -784,12 +799,13 @@ private:
         PbrtRenderStats st;
         const auto& ctx = scene.aggregate().context();
         if (!comm) {
-            ctx->check(pbrt_hip_render(scene.aggregate().handle(), &camera->cam, &rp, film.pixels.data(), &st), "Integrator::render");
+            ctx->check(pbrt_hip_render_moving_camera(scene.aggregate().handle(), &camera->cam, &camera->motion, &rp, film.pixels.data(), &st),
+                       "Integrator::render");
         } else {
             const int64_t n_pixels = (int64_t)film.width * film.height;
             float* d_film = nullptr;
             ctx->check(pbrt_hip_film_create(ctx->handle(), n_pixels, &d_film), "Integrator::render: pbrt_hip_film_create");
-            int rc = pbrt_hip_render_device(scene.aggregate().handle(), &camera->cam, &rp, d_film, &st);
+            int rc = pbrt_hip_render_device_moving_camera(scene.aggregate().handle(), &camera->cam, &camera->motion, &rp, d_film, &st);
             const char* what = "Integrator::render: pbrt_hip_render_device";
             if (rc == PBRT_HIP_OK) rc = pbrt_hip_film_reduce(comm->handle(), d_film, n_pixels, root), what = "Integrator::render: pbrt_hip_film_reduce";
             if (rc == PBRT_HIP_OK && (root < 0 || root == comm->rank))

@@ -1,6 +1,7 @@
 // host_motion.cpp — moving instances on the host (no device code): Matrix4x4::decompose (src/core/transform.rs:264-330,
 // after pbrt-v3's AnimatedTransform::Decompose), AnimatedTransform::new's choice of the shorter rotation (transform.rs:870-912),
-// the device side table's rows (motion.h) and pbrt_hip_instance_motion_bounds.
+// the device side table's rows (motion.h) and pbrt_hip_instance_motion_bounds; the animated camera's row, built by the same code,
+// and pbrt_hip_camera_motion_interpolate.
 //
 // The motion bound is NOT AnimatedTransform::motion_bounds / bound_point_motion (transform.rs:913-2084): that one finds the
 // roots of the motion's derivative with a thousand lines of precomputed coefficients and, where r0 . r1 >= 0.9995, falls back
@@ -18,6 +19,7 @@
 #include <cmath>
 #include <cstddef>
 #include <cstring>
+#include <string>
 
 #include "abi_guard.h"
 #include "motion.h"
@@ -26,6 +28,11 @@ static_assert(sizeof(PbrtInstanceMotion) == 80 && offsetof(PbrtInstanceMotion, e
                   offsetof(PbrtInstanceMotion, start_time) == 64 && offsetof(PbrtInstanceMotion, end_time) == 68 &&
                   offsetof(PbrtInstanceMotion, animated) == 72 && offsetof(PbrtInstanceMotion, pad) == 76,
               "PbrtInstanceMotion layout (include/pbrt_hip.h; pbrt_hip/scenes.py INSTANCE_MOTION_DTYPE)");
+
+static_assert(sizeof(PbrtCameraMotion) == 80 && offsetof(PbrtCameraMotion, end_camera_to_world) == 0 &&
+                  offsetof(PbrtCameraMotion, start_time) == 64 && offsetof(PbrtCameraMotion, end_time) == 68 &&
+                  offsetof(PbrtCameraMotion, animated) == 72 && offsetof(PbrtCameraMotion, pad) == 76,
+              "PbrtCameraMotion layout (include/pbrt_hip.h; pbrt_hip/scenes.py CAMERA_MOTION_DTYPE)");
 
 namespace pb {
 
@@ -165,22 +172,26 @@ const char* motion_decompose(const float m[16], MotionParts* out) {
     return nullptr;
 }
 
-const char* motion_parts(const PbrtInstance& inst, const PbrtInstanceMotion& mo, MotionParts* p0, MotionParts* p1) {
-    if (!std::isfinite(mo.start_time) || !std::isfinite(mo.end_time)) return "a non-finite start or end time";
-    if (!(mo.end_time > mo.start_time)) return "end_time <= start_time";
-    if (const char* why = motion_decompose(inst.to_world, p0)) return why;
-    if (const char* why = motion_decompose(mo.end_to_world, p1)) return why;
+const char* motion_parts(const float start[16], const float end[16], float start_time, float end_time, MotionParts* p0, MotionParts* p1) {
+    if (!std::isfinite(start_time) || !std::isfinite(end_time)) return "a non-finite start or end time";
+    if (!(end_time > start_time)) return "end_time <= start_time";
+    if (const char* why = motion_decompose(start, p0)) return why;
+    if (const char* why = motion_decompose(end, p1)) return why;
     const double d = p0->q[0] * p1->q[0] + p0->q[1] * p1->q[1] + p0->q[2] * p1->q[2] + p0->q[3] * p1->q[3];
     if (d < 0.0)
         for (int k = 0; k < 4; ++k) p1->q[k] = -p1->q[k];
     return nullptr;
 }
 
-const char* motion_row(const PbrtInstance& inst, const PbrtInstanceMotion& mo, DevMotion* row) {
-    std::memset(row, 0, sizeof(*row));
-    if (!mo.animated) return nullptr;
+const char* motion_parts(const PbrtInstance& inst, const PbrtInstanceMotion& mo, MotionParts* p0, MotionParts* p1) {
+    return motion_parts(inst.to_world, mo.end_to_world, mo.start_time, mo.end_time, p0, p1);
+}
+
+namespace {
+// the row of a transform animated from `start` to `end_to_world`, for instances and the camera alike
+const char* animated_row(const float start[16], const float end_to_world[16], float start_time, float end_time, DevMotion* row) {
     MotionParts p[2];
-    if (const char* why = motion_parts(inst, mo, &p[0], &p[1])) return why;
+    if (const char* why = motion_parts(start, end_to_world, start_time, end_time, &p[0], &p[1])) return why;
     for (int e = 0; e < 2; ++e) {
         for (int k = 0; k < 3; ++k) row->t[e][k] = (float)p[e].t[k];
         for (int k = 0; k < 4; ++k) row->r[e][k] = (float)p[e].q[k];
@@ -189,18 +200,31 @@ const char* motion_row(const PbrtInstance& inst, const PbrtInstanceMotion& mo, D
     // the end transform's rows as given, and its inverse in double, rounded once
     double M[9], I[9];
     for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) M[3 * i + j] = mo.end_to_world[4 * i + j];
+        for (int j = 0; j < 3; ++j) M[3 * i + j] = end_to_world[4 * i + j];
     if (!inv3(M, I)) return "a singular matrix";
     for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 4; ++j) row->end_o2w[4 * i + j] = mo.end_to_world[4 * i + j];
+        for (int j = 0; j < 4; ++j) row->end_o2w[4 * i + j] = end_to_world[4 * i + j];
         for (int j = 0; j < 3; ++j) row->end_w2o[4 * i + j] = (float)I[3 * i + j] + 0.0f;
-        const double t = -(I[3 * i] * (double)mo.end_to_world[3] + I[3 * i + 1] * (double)mo.end_to_world[7] + I[3 * i + 2] * (double)mo.end_to_world[11]);
+        const double t = -(I[3 * i] * (double)end_to_world[3] + I[3 * i + 1] * (double)end_to_world[7] + I[3 * i + 2] * (double)end_to_world[11]);
         row->end_w2o[4 * i + 3] = (float)t + 0.0f;
     }
-    row->start_time = mo.start_time;
-    row->end_time = mo.end_time;
+    row->start_time = start_time;
+    row->end_time = end_time;
     row->animated = 1;
     return nullptr;
+}
+}  // namespace
+
+const char* motion_row(const PbrtInstance& inst, const PbrtInstanceMotion& mo, DevMotion* row) {
+    std::memset(row, 0, sizeof(*row));
+    if (!mo.animated) return nullptr;
+    return animated_row(inst.to_world, mo.end_to_world, mo.start_time, mo.end_time, row);
+}
+
+const char* camera_motion_row(const PbrtCamera& camera, const PbrtCameraMotion& mo, DevMotion* row) {
+    std::memset(row, 0, sizeof(*row));
+    if (!mo.animated) return nullptr;
+    return animated_row(camera.camera_to_world, mo.end_camera_to_world, mo.start_time, mo.end_time, row);
 }
 
 }  // namespace pb
@@ -284,6 +308,48 @@ extern "C" int pbrt_hip_instance_motion_bounds(const float object_min[3], const 
             hi[k] = round_up(mx[k] + pad);
         }
     }
+    return PBRT_HIP_OK;
+}
+PB_ABI_CATCH
+
+// AnimatedTransform::interpolate (transform.rs:2010-2030) of the camera's two matrices, in double, rounded once
+extern "C" int pbrt_hip_camera_motion_interpolate(const PbrtCamera* camera, const PbrtCameraMotion* motion, float time,
+                                                  float out_camera_to_world[16]) try {
+    using namespace pb;
+    if (!camera || !out_camera_to_world) return PBRT_HIP_ERR_INVALID;
+    if (!motion || !motion->animated) {
+        std::memcpy(out_camera_to_world, camera->camera_to_world, 64);
+        return PBRT_HIP_OK;
+    }
+    MotionParts p0, p1;
+    if (const char* why = motion_parts(camera->camera_to_world, motion->end_camera_to_world, motion->start_time, motion->end_time, &p0, &p1)) {
+        set_thread_error(std::string("camera motion: ") + why);
+        return PBRT_HIP_ERR_INVALID;
+    }
+    if (!std::isfinite(time)) {
+        set_thread_error("camera motion: a non-finite time");
+        return PBRT_HIP_ERR_INVALID;
+    }
+    if (time <= motion->start_time) {
+        std::memcpy(out_camera_to_world, camera->camera_to_world, 64);
+        return PBRT_HIP_OK;
+    }
+    if (time >= motion->end_time) {
+        std::memcpy(out_camera_to_world, motion->end_camera_to_world, 64);
+        return PBRT_HIP_OK;
+    }
+    const double u = ((double)time - (double)motion->start_time) / ((double)motion->end_time - (double)motion->start_time);
+    double q[4], R[9], S[9], A[9];
+    slerp(u, p0.q, p1.q, q);
+    quat_to_matrix(q, R);
+    for (int k = 0; k < 9; ++k) S[k] = (1.0 - u) * p0.s[k] + u * p1.s[k];
+    mul3(R, S, A);
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) out_camera_to_world[4 * i + j] = (float)A[3 * i + j];
+        out_camera_to_world[4 * i + 3] = (float)((1.0 - u) * p0.t[i] + u * p1.t[i]);
+    }
+    out_camera_to_world[12] = out_camera_to_world[13] = out_camera_to_world[14] = 0.0f;
+    out_camera_to_world[15] = 1.0f;
     return PBRT_HIP_OK;
 }
 PB_ABI_CATCH

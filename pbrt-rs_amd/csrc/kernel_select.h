@@ -170,6 +170,23 @@ inline PathKernel moving_path_kernel(bool bin) {
     static constexpr PathKernel table[2] = {k_shade_moving<true>, k_shade_moving<false>};
     return table[bin ? 0 : 1];
 }
+
+// ---- camera rays ----
+// The generator by a two-bit key: bit 0 the scene has moving instances, bit 1 camera_to_world is animated. With a static camera
+// the kernels are k_generate / k_generate_moving with the arguments they always had; an animated camera has one build for both
+// kinds of scene, which also takes the camera's DevMotion row (wf_camera_motion.h). Behind every older table, as above.
+using GenerateKernel = void (*)(PathState, Queues, PassParams, DevCamera, TileList);
+using GenerateCameraKernel = void (*)(PathState, Queues, PassParams, DevCamera, DevMotion, TileList);
+constexpr int kGenerateCameraAnimated = 2;
+inline int generate_key(bool scene_moving, bool camera_animated) { return (scene_moving ? 1 : 0) | (camera_animated ? kGenerateCameraAnimated : 0); }
+inline GenerateKernel generate_kernel(int key) {
+    static constexpr GenerateKernel table[2] = {k_generate, k_generate_moving};
+    return table[key & 1];
+}
+inline GenerateCameraKernel generate_camera_kernel(int key) {
+    static constexpr GenerateCameraKernel table[2] = {k_generate_moving_camera, k_generate_moving_camera};
+    return table[key & 1];
+}
 #endif  // PB_SELECT_SHADING_KERNELS
 
 }  // namespace pb

@@ -97,4 +97,22 @@ PB_DEV void motion_interpolate(const DevMotion& mo, float time, MotionRows* out)
     }
 }
 
+// The forward rows alone, for a transform that is only ever applied forwards (the animated camera's camera_to_world,
+// wf_generate_trace.h): motion_interpolate's arithmetic for o2w, expression by expression, without the inverse.
+PB_DEV void motion_interpolate_forward(const DevMotion& mo, float time, float* o2w) {
+    const float u = (time - mo.start_time) / (mo.end_time - mo.start_time);
+    float q[4];
+    motion_slerp(u, mo.r[0], mo.r[1], q);
+    const float x = q[0], y = q[1], z = q[2], w = q[3];
+    const float R[9] = {1.0f - 2.0f * (y * y + z * z), 2.0f * (x * y - z * w),        2.0f * (x * z + y * w),
+                        2.0f * (x * y + z * w),        1.0f - 2.0f * (x * x + z * z), 2.0f * (y * z - x * w),
+                        2.0f * (x * z - y * w),        2.0f * (y * z + x * w),        1.0f - 2.0f * (x * x + y * y)};
+    float S[9];
+    for (int k = 0; k < 9; ++k) S[k] = (1.0f - u) * mo.s[0][k] + u * mo.s[1][k];
+    for (int i = 0; i < 3; ++i) {
+        for (int j = 0; j < 3; ++j) o2w[4 * i + j] = (R[3 * i] * S[j] + R[3 * i + 1] * S[3 + j] + R[3 * i + 2] * S[6 + j]) + 0.0f;
+        o2w[4 * i + 3] = ((1.0f - u) * mo.t[0][i] + u * mo.t[1][i]) + 0.0f;
+    }
+}
+
 }  // namespace pb

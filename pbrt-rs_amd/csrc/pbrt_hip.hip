@@ -31,6 +31,9 @@ using namespace pb;
 // why the calling THREAD's last pbrt_hip_context_create failed (pbrt_hip_last_error(NULL)): contexts may be created from several
 // host threads at once, and a failed creation has no context to carry its message
 static thread_local std::string g_create_error;
+namespace pb {
+void set_thread_error(const std::string& message) { g_create_error = message; }  // host_motion.h: entry points without a context
+}
 
 
 

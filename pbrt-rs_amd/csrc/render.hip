@@ -15,6 +15,7 @@
 #include <thread>
 #include <vector>
 
+#include "host_motion.h"
 #include "scene.h"
 #include "trace.h"
 #include "wavefront.h"
@@ -26,26 +27,56 @@ using namespace pb;
 // ------------------------------------------------------------------------------------
 // render: see wavefront.h
 // ------------------------------------------------------------------------------------
-extern "C" int pbrt_hip_render_device(PbrtHipScene* s, const PbrtCamera* camera, const PbrtRenderParams* params,
-                                      float* d_film, PbrtRenderStats* stats) try {
+// The animated camera's DevMotion row, checked before anything is launched (host_motion.cpp). *row stays null for the static
+// camera: a null motion or animated == 0.
+static int camera_row(PbrtHipContext* ctx, const PbrtCamera& camera, const PbrtCameraMotion* motion, DevMotion* storage,
+                      const DevMotion** row) {
+    *row = nullptr;
+    if (!motion || !motion->animated) return PBRT_HIP_OK;
+    if (const char* why = camera_motion_row(camera, *motion, storage)) {
+        ctx->last_error = std::string("camera motion: ") + why;
+        return PBRT_HIP_ERR_INVALID;
+    }
+    *row = storage;
+    return PBRT_HIP_OK;
+}
+
+extern "C" int pbrt_hip_render_device_moving_camera(PbrtHipScene* s, const PbrtCamera* camera, const PbrtCameraMotion* motion,
+                                                    const PbrtRenderParams* params, float* d_film, PbrtRenderStats* stats) try {
     if (!s || !camera || !params || !d_film) return PBRT_HIP_ERR_INVALID;
     PB_ENTER(s->ctx);
+    DevMotion storage;
+    const DevMotion* row;
+    if (int rc = camera_row(s->ctx, *camera, motion, &storage, &row)) return rc;
     HIP_TRY(s->ctx, hipSetDevice(s->ctx->device));
-    return wavefront_render(s, *camera, *params, d_film, stats);
+    return wavefront_render(s, *camera, *params, d_film, stats, nullptr, row);
+}
+PB_ABI_CATCH
+extern "C" int pbrt_hip_render_device(PbrtHipScene* s, const PbrtCamera* camera, const PbrtRenderParams* params,
+                                      float* d_film, PbrtRenderStats* stats) try {
+    return pbrt_hip_render_device_moving_camera(s, camera, nullptr, params, d_film, stats);
 }
 PB_ABI_CATCH
 
 extern "C" int pbrt_hip_render(PbrtHipScene* s, const PbrtCamera* camera, const PbrtRenderParams* params,
                                float* film_xyzw, PbrtRenderStats* stats) try {
+    return pbrt_hip_render_moving_camera(s, camera, nullptr, params, film_xyzw, stats);
+}
+PB_ABI_CATCH
+extern "C" int pbrt_hip_render_moving_camera(PbrtHipScene* s, const PbrtCamera* camera, const PbrtCameraMotion* motion,
+                                             const PbrtRenderParams* params, float* film_xyzw, PbrtRenderStats* stats) try {
     if (!s || !camera || !params || !film_xyzw) return PBRT_HIP_ERR_INVALID;
     PbrtHipContext* ctx = s->ctx;
     PB_ENTER(ctx);
+    DevMotion storage;
+    const DevMotion* row;
+    if (int rc = camera_row(ctx, *camera, motion, &storage, &row)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (params->width <= 0 || params->height <= 0) return PBRT_HIP_ERR_INVALID;
     size_t bytes = (size_t)params->width * params->height * 4 * sizeof(float);
     float* d_film = nullptr;
     HIP_TRY(ctx, hipMalloc((void**)&d_film, bytes));
-    int rc = wavefront_render(s, *camera, *params, d_film, stats);
+    int rc = wavefront_render(s, *camera, *params, d_film, stats, nullptr, row);
     if (rc == PBRT_HIP_OK && !hip_ok(ctx, hipMemcpy(film_xyzw, d_film, bytes, hipMemcpyDeviceToHost), "film D2H"))
         rc = PBRT_HIP_ERR_DEVICE;
     // after a deadline (ctx->lost) an abandoned kernel may still write the film and hipFree waits for the device: it stays
@@ -514,9 +545,18 @@ static const char* sampler_spp(const PbrtRenderParams& rp, int32_t* spp) {
 
 extern "C" int pbrt_hip_camera_rays(PbrtHipScene* s, const PbrtCamera* camera, const PbrtRenderParams* params, int64_t capacity,
                                     PbrtRay* rays, uint64_t* stream_keys, float* p_film, int32_t* pixel_sample, int64_t* n_out) try {
+    return pbrt_hip_camera_rays_moving_camera(s, camera, nullptr, params, capacity, rays, stream_keys, p_film, pixel_sample, n_out);
+}
+PB_ABI_CATCH
+extern "C" int pbrt_hip_camera_rays_moving_camera(PbrtHipScene* s, const PbrtCamera* camera, const PbrtCameraMotion* motion,
+                                                  const PbrtRenderParams* params, int64_t capacity, PbrtRay* rays,
+                                                  uint64_t* stream_keys, float* p_film, int32_t* pixel_sample, int64_t* n_out) try {
     if (!s || !camera || !params || !n_out) return PBRT_HIP_ERR_INVALID;
     PbrtHipContext* ctx = s->ctx;
     PB_ENTER(ctx);
+    DevMotion storage;
+    const DevMotion* row;
+    if (int rc = camera_row(ctx, *camera, motion, &storage, &row)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (params->width <= 0 || params->height <= 0 || params->spp <= 0 || params->x0 > params->x1 || params->y0 > params->y1)
         return PBRT_HIP_ERR_INVALID;
@@ -546,7 +586,7 @@ extern "C" int pbrt_hip_camera_rays(PbrtHipScene* s, const PbrtCamera* camera, c
         !hip_ok(ctx, hipMalloc((void**)&b.out_pfilm, (size_t)n * 2 * sizeof(float)), "hipMalloc") ||
         !hip_ok(ctx, hipMalloc((void**)&b.out_pixel_sample, (size_t)n * 3 * sizeof(int32_t)), "hipMalloc"))
         rc = PBRT_HIP_ERR_OOM;
-    if (rc == PBRT_HIP_OK) rc = wavefront_render(s, *camera, *params, nullptr, nullptr, &b);
+    if (rc == PBRT_HIP_OK) rc = wavefront_render(s, *camera, *params, nullptr, nullptr, &b, row);
     if (rc == PBRT_HIP_OK && (!hip_ok(ctx, hipMemcpy(rays, b.out_rays, (size_t)n * sizeof(PbrtRay), hipMemcpyDeviceToHost), "D2H") ||
                               !hip_ok(ctx, hipMemcpy(stream_keys, b.out_keys, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost), "D2H") ||
                               !hip_ok(ctx, hipMemcpy(p_film, b.out_pfilm, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost), "D2H") ||
@@ -829,6 +869,7 @@ struct RenderJob {
     hipStream_t st;
     const LiBatch* li;
     float* d_film;
+    const DevMotion* camera_motion;  // the animated camera's row, or null (kernel_select.h: generate_key)
     // stage 1, the caller's parameters checked and normalised
     PbrtRenderParams rp;  // li substitution, the sampler's samples per pixel, AO's round_count, an export's single pass
     bool li_mode, export_mode;
@@ -1442,8 +1483,10 @@ int RenderJob::run(const PbrtCamera& camera, PbrtRenderStats* stats) {
         if (li_mode)
             hipLaunchKernelGGL(k_li_generate, dim3((n_paths + 255) / 256), dim3(256), 0, st, ps, q[0], li->d_rays, li->d_keys, (uint32_t)li->n,
                                n_paths, li->skip);
+        else if (const int key = generate_key(s->moving, camera_motion != nullptr); key & kGenerateCameraAnimated)
+            hipLaunchKernelGGL(generate_camera_kernel(key), dim3((n_paths + 255) / 256), dim3(256), 0, st, ps, q[0], pp, cam, *camera_motion, tiles);
         else
-            hipLaunchKernelGGL(s->moving ? k_generate_moving : k_generate, dim3((n_paths + 255) / 256), dim3(256), 0, st, ps, q[0], pp, cam, tiles);
+            hipLaunchKernelGGL(generate_kernel(key), dim3((n_paths + 255) / 256), dim3(256), 0, st, ps, q[0], pp, cam, tiles);
         RENDER_TRY(hipGetLastError());
         if (export_mode) {
             hipLaunchKernelGGL(k_camera_rays_out, dim3((n_paths + 255) / 256), dim3(256), 0, st, ps, pp, tiles, li->out_rays, li->out_keys,
@@ -1477,8 +1520,8 @@ int RenderJob::run(const PbrtCamera& camera, PbrtRenderStats* stats) {
 }  // namespace
 
 int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRenderParams& rp_in, float* d_film,
-                     PbrtRenderStats* stats, const LiBatch* li) {
-    RenderJob job{s, s->ctx, s->ctx->stream, li, d_film};
+                     PbrtRenderStats* stats, const LiBatch* li, const DevMotion* camera_motion) {
+    RenderJob job{s, s->ctx, s->ctx->stream, li, d_film, camera_motion};
     if (const char* why = job.normalise_params(rp_in)) return job.invalid(why);
     return job.run(camera, stats);
 }

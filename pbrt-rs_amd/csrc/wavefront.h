@@ -23,6 +23,7 @@
 #include "wf_path.h"
 #include "wf_direct.h"
 #include "wf_film.h"
+#include "wf_camera_motion.h"  // last: defined after every older kernel
 
 // The same loop driven from outside the render form:
 //   li:     a batch of Integrator::li calls on the caller's rays (pbrt_hip_li): rays / keys in, radiance out, no film;
@@ -38,5 +39,6 @@ struct LiBatch {
     float* out_pfilm = nullptr;
     int32_t* out_pixel_sample = nullptr;
 };
+// camera_motion: the animated camera's row (host_motion.h: camera_motion_row), or null for the static camera
 int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRenderParams& rp, float* d_film,
-                     PbrtRenderStats* stats, const LiBatch* li = nullptr);
+                     PbrtRenderStats* stats, const LiBatch* li = nullptr, const pb::DevMotion* camera_motion = nullptr);

@@ -4,11 +4,32 @@
 
 namespace pb {
 
+// Rows 0-2 of an animated camera's camera_to_world at `time`, by the rule of impl From<(&AnimatedTransform, &Ray)> for Ray
+// (geometry.rs:1181-1188) and AnimatedTransform::interpolate's own early returns (transform.rs:2010-2030): the start matrix at or
+// before start_time, the end matrix at or after end_time, both as given, and T(u) R(u) S(u) in float32 between them (motion.h).
+PB_DEV void camera_rows_at(const DevCamera& cam, const DevMotion& mo, float time, float* rows) {
+    if (time <= mo.start_time) {
+        for (int k = 0; k < 12; ++k) rows[k] = cam.c2w[k];
+    } else if (time >= mo.end_time) {
+        for (int k = 0; k < 12; ++k) rows[k] = mo.end_o2w[k];
+    } else {
+        motion_interpolate_forward(mo, time, rows);
+    }
+}
+// Transform::transform_point of an affine matrix given by its rows 0-2: wp == 1 (transform.rs:351-370)
+PB_DEV V3 xform_point_rows(const float* m, V3 p) {
+    return V3{m[0] * p.x + m[1] * p.y + m[2] * p.z + m[3], m[4] * p.x + m[5] * p.y + m[6] * p.z + m[7],
+              m[8] * p.x + m[9] * p.y + m[10] * p.z + m[11]};
+}
+
 // TIME: the ray carries its time, lerp(time sample, shutter_open, shutter_close) as the reference's cameras set it
 // (perspective.rs:107), in the free fourth component of its second float4 (wf_state.h). Only scenes with moving instances read
 // it, so only their k_generate_moving writes it; k_generate is the code it always was.
-template <bool TIME>
-PB_DEV void generate_camera_rays(const PathState& ps, const Queues& q, const PassParams& pp, const DevCamera& cam, const TileList& tiles) {
+// CAMERA_MOTION: camera_to_world is an AnimatedTransform (camera.rs:80-115) and the camera-space ray goes through it at the ray's
+// time (geometry.rs:1177-1190): camera_rows_at, above. That build always writes the time, in static scenes too.
+template <bool TIME, bool CAMERA_MOTION = false>
+PB_DEV void generate_camera_rays(const PathState& ps, const Queues& q, const PassParams& pp, const DevCamera& cam, const TileList& tiles,
+                                 const DevMotion* cmo = nullptr) {
     uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t n = (uint32_t)pp.n_pix * pp.n_samples;
     if (p >= n) return;
@@ -74,7 +95,13 @@ PB_DEV void generate_camera_rays(const PathState& ps, const Queues& q, const Pas
         (void)time_u;  // ray.time only feeds animated transforms (TIME, below) and media (out of scope)
         // Ray through camera_to_world with origin error (geometry.rs:865-881, 898-935)
         const float* m = cam.c2w;
-        V3 ow = xform_point(m, o);
+        float rows[12], time = 0.0f;
+        if (CAMERA_MOTION) {
+            time = (1.0f - time_u) * cam.shutter_open + time_u * cam.shutter_close;
+            camera_rows_at(cam, *cmo, time, rows);
+            m = rows;
+        }
+        V3 ow = CAMERA_MOTION ? xform_point_rows(m, o) : xform_point(m, o);
         float xa = __builtin_fabsf(m[0] * o.x) + __builtin_fabsf(m[1] * o.y) + __builtin_fabsf(m[2] * o.z) + __builtin_fabsf(m[3]);
         float ya = __builtin_fabsf(m[4] * o.x) + __builtin_fabsf(m[5] * o.y) + __builtin_fabsf(m[6] * o.z) + __builtin_fabsf(m[7]);
         float za = __builtin_fabsf(m[8] * o.x) + __builtin_fabsf(m[9] * o.y) + __builtin_fabsf(m[10] * o.z) + __builtin_fabsf(m[11]);
@@ -88,7 +115,10 @@ PB_DEV void generate_camera_rays(const PathState& ps, const Queues& q, const Pas
             tmax -= dt;
         }
         store_ray(ps, p, RS_CONT, ow, dw, tmax);
-        if (TIME) ps.ray[ray_index(ps, p, RS_CONT) + 1].w = (1.0f - time_u) * cam.shutter_open + time_u * cam.shutter_close;
+        if (CAMERA_MOTION)
+            ps.ray[ray_index(ps, p, RS_CONT) + 1].w = time;
+        else if (TIME)
+            ps.ray[ray_index(ps, p, RS_CONT) + 1].w = (1.0f - time_u) * cam.shutter_open + time_u * cam.shutter_close;
         samp_store(ps, p, sm);
         ps.pfilm[p] = make_float2(pfx, pfy);
         flags = PF_VALID | PF_ALIVE;
@@ -158,7 +188,7 @@ __global__ void k_camera_rays_out(PathState ps, PassParams pp, TileList tiles, P
     float4 a = ps.ray[ri], b = ps.ray[ri + 1];
     float4* out = reinterpret_cast<float4*>(rays + p);
     out[0] = a;
-    out[1] = b;  // .w: the ray's time (0 unless k_generate_moving wrote it)
+    out[1] = b;  // .w: the ray's time (0 unless k_generate_moving or k_generate_moving_camera wrote it)
     keys[p] = sample_sequence(pp, x, y, pp.sample0 + s_local);
     float2 pf = ps.pfilm[p];
     pfilm[2 * (size_t)p] = pf.x;

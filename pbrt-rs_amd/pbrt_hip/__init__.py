@@ -45,6 +45,8 @@ EXPORTS = [
     "pbrt_hip_scene_set_light_map", "pbrt_hip_light_map_tables", "pbrt_hip_light_sample_li",
     "pbrt_hip_scene_set_lobe_material", "pbrt_hip_material_lobes",
     "pbrt_hip_instance_motion_bounds", "pbrt_hip_scene_create_two_level_moving",
+    "pbrt_hip_render_moving_camera", "pbrt_hip_render_device_moving_camera", "pbrt_hip_camera_rays_moving_camera",
+    "pbrt_hip_camera_motion_interpolate",
 ]
 MAT_NONE, MAT_MATTE, MAT_MIRROR, MAT_GLASS, MAT_PLASTIC, MAT_METAL = (scenes.MAT_NONE, scenes.MAT_MATTE, scenes.MAT_MIRROR,
                                                                       scenes.MAT_GLASS, scenes.MAT_PLASTIC, scenes.MAT_METAL)
@@ -204,6 +206,10 @@ def lib():
         L.pbrt_hip_li.argtypes = [vp, ctypes.POINTER(LiParams), vp, vp, i64, vp, ctypes.POINTER(RenderStats)]
         L.pbrt_hip_li_device.argtypes = [vp, ctypes.POINTER(LiParams), vp, vp, i64, vp, ctypes.POINTER(RenderStats)]
         L.pbrt_hip_camera_rays.argtypes = [vp, vp, ctypes.POINTER(RenderParams), i64, vp, vp, vp, vp, ctypes.POINTER(i64)]
+        L.pbrt_hip_render_moving_camera.argtypes = [vp, vp, vp, ctypes.POINTER(RenderParams), vp, ctypes.POINTER(RenderStats)]
+        L.pbrt_hip_render_device_moving_camera.argtypes = [vp, vp, vp, ctypes.POINTER(RenderParams), vp, ctypes.POINTER(RenderStats)]
+        L.pbrt_hip_camera_rays_moving_camera.argtypes = [vp, vp, vp, ctypes.POINTER(RenderParams), i64, vp, vp, vp, vp, ctypes.POINTER(i64)]
+        L.pbrt_hip_camera_motion_interpolate.argtypes = [vp, vp, ctypes.c_float, vp]
         L.pbrt_hip_tile_partition.argtypes = [i32, i32, i32, i32, i32, i32, vp, i32, ctypes.POINTER(i32)]
         L.pbrt_hip_tile_partition_order.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, i32, ctypes.POINTER(i32)]
         L.pbrt_hip_filter_table.argtypes = [i32, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp]
@@ -434,6 +440,19 @@ def instance_motion_bounds(object_min, object_max, instances, motions):
     if rc != 0:
         raise PbrtHipError(f"pbrt_hip_instance_motion_bounds failed ({rc}): a non-finite, non-affine or singular matrix, or end_time <= start_time")
     return lo, hi
+
+
+def camera_motion_interpolate(camera, motion, time):
+    """AnimatedTransform::interpolate of an animated camera_to_world (pbrt_hip_camera_motion_interpolate): the 4x4 float32 matrix
+    camera rays of that time go through. camera: a CAMERA_DTYPE record (camera_to_world is the camera at start_time), motion:
+    scenes.camera_motion(...) or None (the static camera). Host only."""
+    camera = np.ascontiguousarray(camera, dtype=CAMERA_DTYPE)
+    motion = None if motion is None else np.ascontiguousarray(motion, dtype=scenes.CAMERA_MOTION_DTYPE)
+    out = np.zeros((4, 4), dtype=np.float32)
+    rc = lib().pbrt_hip_camera_motion_interpolate(_p(camera), None if motion is None else _p(motion), float(time), _p(out))
+    if rc != 0:
+        raise PbrtHipError(f"pbrt_hip_camera_motion_interpolate failed ({rc}): {lib().pbrt_hip_last_error(None).decode()}")
+    return out
 
 
 def shape_world_bounds(shapes):
@@ -758,8 +777,9 @@ class Scene:
     def render(self, camera, width, height, spp, integrator=INTEGRATOR_PATH, max_depth=5, rr_threshold=1.0,
                light_strategy=1, seed=0, bounds=None, tile_rank=0, tile_world=1, spp_per_pass=0, d_film_ptr=None,
                filter=None, ao_samples=64, cos_sample=True, sampler=None, max_sample_luminance=0.0, shade_order=0, ray_order=0,
-               tile_order=0, samples_per_wave=0):
+               tile_order=0, samples_per_wave=0, camera_motion=None):
         """Integrator::render. Returns (film[h,w,4] or None when d_film_ptr is given, stats dict).
+        camera_motion: scenes.camera_motion(...) for an animated camera_to_world (pbrt_hip_render_moving_camera), None = static.
         integrator: INTEGRATOR_PATH / _DIRECT / _WHITTED / _AO (ao_samples, cos_sample: AOIntegrator::new).
         sampler: None (RandomSampler), ("stratified", nx, ny, jitter, n_dims) or ("zerotwo", n_dims); the samples
         per pixel then become nx * ny / the next power of two of spp.
@@ -775,13 +795,15 @@ class Scene:
                           tile_rank, tile_world, spp_per_pass, filter, ao_samples, sampler, max_sample_luminance, shade_order, ray_order,
                           tile_order, samples_per_wave)
         st = RenderStats()
-        if d_film_ptr is None:
-            film = np.zeros((height, width, 4), dtype=np.float32)
-            rc = lib().pbrt_hip_render(self.h, _p(camera), ctypes.byref(rp), _p(film), ctypes.byref(st))
+        film = None if d_film_ptr is not None else np.zeros((height, width, 4), dtype=np.float32)
+        target = _p(film) if d_film_ptr is None else ctypes.c_void_p(d_film_ptr)
+        if camera_motion is None:
+            call = lib().pbrt_hip_render if d_film_ptr is None else lib().pbrt_hip_render_device
+            rc = call(self.h, _p(camera), ctypes.byref(rp), target, ctypes.byref(st))
         else:
-            film = None
-            rc = lib().pbrt_hip_render_device(self.h, _p(camera), ctypes.byref(rp), ctypes.c_void_p(d_film_ptr),
-                                              ctypes.byref(st))
+            camera_motion = np.ascontiguousarray(camera_motion, dtype=scenes.CAMERA_MOTION_DTYPE)
+            call = lib().pbrt_hip_render_moving_camera if d_film_ptr is None else lib().pbrt_hip_render_device_moving_camera
+            rc = call(self.h, _p(camera), _p(camera_motion), ctypes.byref(rp), target, ctypes.byref(st))
         self.ctx.check(rc, "pbrt_hip_render")
         stats = {name: getattr(st, name) for name, _ in RenderStats._fields_}
         return film, stats
@@ -883,20 +905,28 @@ class Scene:
                        "pbrt_hip_bsdf_query")
         return out
 
-    def camera_rays(self, camera, width, height, spp, seed=0, bounds=None, tile_rank=0, tile_world=1, tile_order=0, sampler=None, filter=None):
+    def camera_rays(self, camera, width, height, spp, seed=0, bounds=None, tile_rank=0, tile_world=1, tile_order=0, sampler=None, filter=None,
+                    camera_motion=None):
         """The camera-ray stage of render(): (rays[RAY_DTYPE], stream_keys[uint64], p_film[n, 2], pixel_sample[n, 3]).
-        sampler as in render(): the camera sample is the sampler's first 2D, first 1D (ray.time) and second 2D draw (sampler.rs:66-73)."""
+        sampler as in render(): the camera sample is the sampler's first 2D, first 1D (ray.time) and second 2D draw (sampler.rs:66-73).
+        camera_motion as in render(): with it every ray carries its time, in static scenes too."""
         camera = np.ascontiguousarray(camera, dtype=CAMERA_DTYPE)
         rp = self._params(width, height, spp, INTEGRATOR_PATH, 5, 1.0, 1, seed, bounds, tile_rank, tile_world, 0, filter, 64, sampler, 0.0,
                           tile_order=tile_order)
         n = ctypes.c_int64()
-        lib().pbrt_hip_camera_rays(self.h, _p(camera), ctypes.byref(rp), 0, None, None, None, None, ctypes.byref(n))
+        if camera_motion is None:
+            call = lambda *a: lib().pbrt_hip_camera_rays(self.h, _p(camera), ctypes.byref(rp), *a)
+        else:
+            camera_motion = np.ascontiguousarray(camera_motion, dtype=scenes.CAMERA_MOTION_DTYPE)
+            call = lambda *a: lib().pbrt_hip_camera_rays_moving_camera(self.h, _p(camera), _p(camera_motion), ctypes.byref(rp), *a)
+        rc = call(0, None, None, None, None, ctypes.byref(n))
+        if n.value == 0:   # no tiles, or refused before the count (a bad motion)
+            self.ctx.check(rc, "pbrt_hip_camera_rays")
         rays = np.zeros(n.value, dtype=RAY_DTYPE)
         keys = np.zeros(n.value, dtype=np.uint64)
         pfilm = np.zeros((n.value, 2), dtype=np.float32)
         pix = np.zeros((n.value, 3), dtype=np.int32)
-        self.ctx.check(lib().pbrt_hip_camera_rays(self.h, _p(camera), ctypes.byref(rp), n.value, _p(rays), _p(keys), _p(pfilm), _p(pix),
-                                                  ctypes.byref(n)), "pbrt_hip_camera_rays")
+        self.ctx.check(call(n.value, _p(rays), _p(keys), _p(pfilm), _p(pix), ctypes.byref(n)), "pbrt_hip_camera_rays")
         return rays, keys, pfilm, pix
 
     def close(self):

@@ -16,6 +16,8 @@ LIGHT_DTYPE = np.dtype([("type", "<i4"), ("L", "<f4", 3), ("prim", "<i4"), ("two
 CAMERA_DTYPE = np.dtype([("camera_to_world", "<f4", 16), ("raster_to_camera", "<f4", 16),
                          ("lens_radius", "<f4"), ("focal_distance", "<f4"),
                          ("shutter_open", "<f4"), ("shutter_close", "<f4"), ("kind", "<i4"), ("pad", "<i4", 3)])
+CAMERA_MOTION_DTYPE = np.dtype([("end_camera_to_world", "<f4", 16), ("start_time", "<f4"), ("end_time", "<f4"), ("animated", "<i4"),
+                                ("pad", "<i4")])   # PbrtCameraMotion
 CAMERA_PERSPECTIVE, CAMERA_ORTHOGRAPHIC, CAMERA_ENVIRONMENT = 0, 1, 2
 RAY_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("t_max", "<f4"), ("time", "<f4")])
 HIT_DTYPE = np.dtype([("t", "<f4"), ("b0", "<f4"), ("b1", "<f4"), ("b2", "<f4"), ("prim_id", "<i4"),
@@ -646,6 +648,16 @@ def instance_motion(end_to_world, start_time, end_time):
     start_time, end_to_world (4x4, last row 0 0 0 1) the one at end_time. scene["instance_motion"] = {instance: record}."""
     rec = np.zeros((), dtype=INSTANCE_MOTION_DTYPE)
     rec["end_to_world"] = np.asarray(end_to_world, dtype=np.float32).reshape(16)
+    rec["start_time"], rec["end_time"], rec["animated"] = start_time, end_time, 1
+    return rec
+
+
+def camera_motion(end_camera_to_world, start_time, end_time):
+    """A PbrtCameraMotion record (Camera::camera_to_world as an AnimatedTransform, camera.rs:80-115): the camera record's own
+    camera_to_world is the camera at start_time, end_camera_to_world (4x4, last row 0 0 0 1) the one at end_time. Pass it as
+    Scene.render(..., camera_motion=record)."""
+    rec = np.zeros((), dtype=CAMERA_MOTION_DTYPE)
+    rec["end_camera_to_world"] = np.asarray(end_camera_to_world, dtype=np.float32).reshape(16)
     rec["start_time"], rec["end_time"], rec["animated"] = start_time, end_time, 1
     return rec
 

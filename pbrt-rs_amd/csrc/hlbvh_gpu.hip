@@ -675,6 +675,12 @@ int sort_pairs_u32(hipStream_t st, void* temp, size_t* temp_bytes, const uint32_
     hipError_t e = rocprim::radix_sort_pairs(temp, *temp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0u, (unsigned)bits, st);
     return e == hipSuccess ? 0 : 1;
 }
+// Exclusive prefix sums of n 64-bit counts (rocPRIM), used by the render loop for the block offsets of the ray-queue
+// expansion (wf_ray_expand.h). temp == nullptr: only reports the scratch size.
+int exclusive_scan_u64(hipStream_t st, void* temp, size_t* temp_bytes, const unsigned long long* in, unsigned long long* out, size_t n) {
+    hipError_t e = rocprim::exclusive_scan(temp, *temp_bytes, in, out, 0ull, n, rocprim::plus<unsigned long long>(), st);
+    return e == hipSuccess ? 0 : 1;
+}
 }  // namespace pb
 
 // Tree + triangle records + leaf order for a single-level scene, all produced on the device. Inputs are

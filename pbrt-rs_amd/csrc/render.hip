@@ -767,6 +767,7 @@ PB_ABI_CATCH
 namespace pb {
 int sort_pairs_u32(hipStream_t st, void* temp, size_t* temp_bytes, const uint32_t* keys_in, uint32_t* keys_out,
                    const uint32_t* vals_in, uint32_t* vals_out, size_t n, int bits);
+int exclusive_scan_u64(hipStream_t st, void* temp, size_t* temp_bytes, const unsigned long long* in, unsigned long long* out, size_t n);
 }
 
 // ---- HaltonSampler host side: prime tables and compute_radical_inverse_permutations (lowdiscrepancy.rs:11-170,
@@ -859,7 +860,18 @@ struct SortBufs {
     size_t tmp_bytes = 0;
 };
 
-constexpr int kSortFrom = 2;  // first sorted wavefront: the first bounce still follows the pixel order of its camera rays
+// the ray-queue expansion's scratch (wf_ray_expand.h): per-block token counts, their exclusive scan, rocPRIM scratch
+struct ExpandBufs {
+    unsigned long long *counts = nullptr, *offsets = nullptr;
+    void* tmp = nullptr;
+    size_t tmp_bytes = 0;
+};
+
+#ifndef PB_SORT_FROM
+#define PB_SORT_FROM 2  // 1 (the first bounce sorted as well) measured in profiles/r13_path_sort.txt
+#endif
+constexpr int kSortFrom = PB_SORT_FROM;  // first sorted wavefront: the first bounce still follows the pixel order of its camera rays
+static_assert(kSortFrom >= 1, "wavefront 0 is the identity queue k_generate leaves: it has no sort entries");
 
 // One render: what it holds between its stages, and the stages in the order run() goes through them. The device blocks belong to
 // the DevBuf of run()'s own frame.
@@ -886,7 +898,8 @@ struct RenderJob {
     PathState ps;
     Queues q[2];
     bool sort_rays = false, sort_shade = false, bin_shade = false;
-    SortBufs ray_sort;    // Morton order of the bounce rays
+    SortBufs ray_sort;    // Morton order of the bounce rays: one (cell, packed rays) pair per path
+    ExpandBufs ray_expand;
     SortBufs shade_sort;  // shade_order 2: keys, the sorted queue positions (vals)
     uint32_t* shade_positions = nullptr;
     TraceChoice trace;                 // kernel_select.h
@@ -915,7 +928,7 @@ struct RenderJob {
     int setup_light_distribution(const SceneNeeds& needs);
     PassParams pass_params(int s0) const;
     void wait_for_counts(int& rc);
-    void trace_wavefront(const RenderEvents& ev, const Queues& qcur, uint32_t n_trace, int wavefront, int& rc);
+    void trace_wavefront(const RenderEvents& ev, const Queues& qcur, uint32_t n_trace, uint32_t n_shade, int wavefront, int& rc);
     void shade_wavefront(const PassParams& pp, int cur, int nxt, uint32_t n_shade, int wavefront, int& rc);
     void run_wavefronts(const RenderEvents& ev, const PassParams& pp, uint32_t n_paths, int& rc);
     void film_stage(const PassParams& pp, uint32_t n_paths, bool last_pass, int& rc);
@@ -984,18 +997,19 @@ int RenderJob::size_pass() {
     spp_pass = rp.spp_per_pass > 0 ? rp.spp_per_pass : 0;
     if (spp_pass == 0) {
         // As many samples of a pixel in flight as two thirds of the free HBM hold (the other integrators: half of it, as
-        // ever). The path integrator takes 524 B per path:
+        // ever). The path integrator takes 500 B per path:
         // 192 B rays (two generations) + 96 B hits + 104 B pending estimates (two generations) + 52 B persistent state +
-        // 32 B queues + 48 B sort and special-list slots; 550 leaves room for the sampler tables. The others keep one
-        // generation and add their stage machine's frame stack. A whole 64-spp 1080p frame is 133 M paths = 70 GB of the
+        // 32 B queues + 12 B sort pairs (one per path: keys in / out, sorted values) + 12 B special-list slots; 526 leaves
+        // room for the sampler tables. The others keep one
+        // generation and add their stage machine's frame stack. A whole 64-spp 1080p frame is 133 M paths = 67 GB of the
         // 288 GB and runs 6 large wavefronts instead of 48 small ones (+10 % on config 3: fewer launches and host round
-        // trips, shorter tails). The share was one half while a path took 376 B; at 524 B a half no longer admits the
-        // 265 M paths (145 GB) of a 32-spp pass of a 4K frame, two thirds (of 280 GB free: 340 M paths) do.
+        // trips, shorter tails). The share was one half while a path took 376 B; at 500 B a half of 280 GB free would just
+        // admit the 265 M paths (133 GB) of a 32-spp pass of a 4K frame, two thirds (355 M paths) do with room to spare.
         size_t free_b = 0, total_b = 0;
         HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
         for (const auto& b : ctx->block_cache)
             if (!b.in_use) free_b += b.bytes;  // blocks kept from the previous render are available to this one
-        const int64_t per_path = rp.integrator == PBRT_INTEGRATOR_PATH ? 550 : 400 + 24 + 48ll * std::max(1, rp.max_depth);
+        const int64_t per_path = rp.integrator == PBRT_INTEGRATOR_PATH ? 526 : 400 + 24 + 48ll * std::max(1, rp.max_depth);
         const size_t share = rp.integrator == PBRT_INTEGRATOR_PATH ? free_b / 3 * 2 : free_b / 2;
         const int64_t target_paths = std::max<int64_t>(1ll << 20, std::min<int64_t>(1ll << 28, (int64_t)share / per_path));
         spp_pass = (int)std::max<int64_t>(1, std::min<int64_t>(rp.spp, target_paths / n_pix));
@@ -1041,15 +1055,24 @@ int RenderJob::alloc_path_buffers(DevBuf& buf, bool* ok) {
     // shooting from the camera rays' hit points, which are already in pixel order (AO: -6 % with the sort).
     // PbrtRenderParams.ray_order = 1 leaves the queues as the shading kernel filled them (results do not depend on it).
     if (rp.ray_order < 0 || rp.ray_order > 1) return invalid("ray_order must be 0 (Morton order from the second bounce on) or 1 (queue order)");
-    sort_rays = rp.ray_order == 0 && rp.integrator == PBRT_INTEGRATOR_PATH;
+    // What is sorted is one pair per path (wf_ray_expand.h), whose value packs the record index into kPathRecBits bits: the
+    // passes size_pass makes stay within that; a caller's own spp_per_pass beyond it is traced in queue order.
+    sort_rays = rp.ray_order == 0 && rp.integrator == PBRT_INTEGRATOR_PATH && N <= ((size_t)1 << kPathRecBits);
     if (sort_rays) {
         SortBufs& rs = ray_sort;
-        rs.keys[0] = buf.alloc<uint32_t>(N * 3, ok);
-        rs.keys[1] = buf.alloc<uint32_t>(N * 3, ok);
-        rs.vals = buf.alloc<uint32_t>(N * 3, ok);
-        if (pb::sort_pairs_u32(st, nullptr, &rs.tmp_bytes, rs.keys[0], rs.keys[1], rs.vals, rs.vals, N * 3, kSortKeyBits) != 0)
+        rs.keys[0] = buf.alloc<uint32_t>(N, ok);
+        rs.keys[1] = buf.alloc<uint32_t>(N, ok);
+        rs.vals = buf.alloc<uint32_t>(N, ok);
+        if (pb::sort_pairs_u32(st, nullptr, &rs.tmp_bytes, rs.keys[0], rs.keys[1], rs.vals, rs.vals, N, kSortKeyBits) != 0)
             return invalid("rocPRIM radix sort: size query failed");
         rs.tmp = buf.alloc<char>(rs.tmp_bytes, ok);
+        ExpandBufs& ex = ray_expand;
+        const size_t n_scan = (size_t)pb::ray_expand_blocks((uint32_t)N) + 1;  // the last element: the sections' totals
+        ex.counts = buf.alloc<unsigned long long>(n_scan, ok);
+        ex.offsets = buf.alloc<unsigned long long>(n_scan, ok);
+        if (pb::exclusive_scan_u64(st, nullptr, &ex.tmp_bytes, ex.counts, ex.offsets, n_scan) != 0)
+            return invalid("rocPRIM scan: size query failed");
+        ex.tmp = buf.alloc<char>(ex.tmp_bytes, ok);
     }
     trace = choose_trace(s);
     if (!trace.ok) return PBRT_HIP_ERR_INVALID;
@@ -1245,20 +1268,34 @@ void RenderJob::wait_for_counts(int& rc) {
 }
 
 // one wavefront's rays: the queue (sorted from the second bounce on when there are enough), then the traversal kernel
-void RenderJob::trace_wavefront(const RenderEvents& ev, const Queues& qcur, uint32_t n_trace, int wavefront, int& rc) {
+void RenderJob::trace_wavefront(const RenderEvents& ev, const Queues& qcur, uint32_t n_trace, uint32_t n_shade, int wavefront, int& rc) {
     RENDER_TRY(hipMemsetAsync(ctx->d_work_counter, 0, kWorkCounters * sizeof(unsigned int), st));
     const uint32_t* trace_queue = qcur.trace;
-    if (sort_rays && wavefront >= kSortFrom && n_trace >= (1u << 20)) {
+    if (sort_rays && wavefront >= kSortFrom) {
         // from the second bounce on the rays of a wavefront start all over the scene (the first bounce still
-        // follows the pixel order of its camera rays): trace them in Morton order of their origins (the keys were
-        // written by k_shade together with the queue entries)
+        // follows the pixel order of its camera rays): trace them in Morton order of their origins. k_shade left one
+        // (cell, packed rays) pair per path of the shade queue (Queues::keys) and no trace-queue entries: sort the n_shade
+        // pairs when there are enough rays, then expand the list into qcur.trace (wf_ray_expand.h); the pairs' values are
+        // moved out of qcur.trace first, by the sort or by a copy.
         const SortBufs& rs = ray_sort;
-        size_t tb = rs.tmp_bytes;
-        if (pb::sort_pairs_u32(st, rs.tmp, &tb, rs.keys[0], rs.keys[1], qcur.trace, rs.vals, n_trace, kSortKeyBits) != 0 && rc == PBRT_HIP_OK) {
-            ctx->last_error = "rocPRIM radix sort failed";
+        const ExpandBufs& ex = ray_expand;
+        if (n_trace >= (1u << 20)) {
+            size_t tb = rs.tmp_bytes;
+            if (pb::sort_pairs_u32(st, rs.tmp, &tb, rs.keys[0], rs.keys[1], qcur.trace, rs.vals, n_shade, kSortKeyBits) != 0 && rc == PBRT_HIP_OK) {
+                ctx->last_error = "rocPRIM radix sort failed";
+                rc = PBRT_HIP_ERR_DEVICE;
+            }
+        } else {
+            RENDER_TRY(hipMemcpyAsync(rs.vals, qcur.trace, (size_t)n_shade * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+        }
+        const uint32_t blocks = pb::ray_expand_blocks(n_shade);
+        hipLaunchKernelGGL(k_ray_expand_count, dim3(blocks), dim3(kExpandBlock), 0, st, rs.vals, n_shade, ex.counts);
+        size_t tb = ex.tmp_bytes;
+        if (pb::exclusive_scan_u64(st, ex.tmp, &tb, ex.counts, ex.offsets, (size_t)blocks + 1) != 0 && rc == PBRT_HIP_OK) {
+            ctx->last_error = "rocPRIM scan failed";
             rc = PBRT_HIP_ERR_DEVICE;
         }
-        trace_queue = rs.vals;
+        hipLaunchKernelGGL(k_ray_expand_scatter, dim3(blocks), dim3(kExpandBlock), 0, st, rs.vals, n_shade, ex.offsets, qcur.trace, n_trace);
     }
     RENDER_TRY(hipEventRecord(ev.t0, st));
     const int segments = (wavefront == 0 && !trace.inst) ? kQueueSegments : 1;  // see trace.h
@@ -1332,10 +1369,11 @@ void RenderJob::run_wavefronts(const RenderEvents& ev, const PassParams& pp, uin
     int cur = 0, wavefront = 0;  // wavefront 0 = camera rays, 1 = first bounce + its shadow rays, ...
     while (rc == PBRT_HIP_OK && counts[1] > 0) {
         uint32_t n_trace = (uint32_t)counts[0], n_shade = (uint32_t)counts[1];
-        if (n_trace > 0) trace_wavefront(ev, q[cur], n_trace, wavefront, rc);
+        if (n_trace > 0) trace_wavefront(ev, q[cur], n_trace, n_shade, wavefront, rc);
         int nxt = cur ^ 1;
         RENDER_TRY(hipMemsetAsync(q[nxt].counts64, 0, 2 * sizeof(unsigned long long), st));
-        // the wavefront this launch of k_shade fills is traced in Morton order: have it write the keys as well
+        // the wavefront this launch of k_shade fills is traced in Morton order: have it write one sort pair per path instead
+        // of the trace-queue entries (trace_wavefront expands them)
         q[nxt].keys = (sort_rays && wavefront + 1 >= kSortFrom) ? ray_sort.keys[0] : nullptr;
         shade_wavefront(pp, cur, nxt, n_shade, wavefront, rc);
         RENDER_TRY(hipGetLastError());

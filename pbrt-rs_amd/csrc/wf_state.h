@@ -7,6 +7,7 @@
 #include "trace_persistent.h"
 #include "trace_wide.h"
 #include "trace_stackless.h"
+#include "wf_ray_expand.h"
 
 namespace pb {
 
@@ -30,6 +31,8 @@ enum RaySlot : int { RS_CONT = 0, RS_MIS = 1, RS_SHADOW = 2 };
 // hit: such a ray is traced as an any-hit ray that skips the triangles Triangle::intersect rejects (IO::strict), ends at its
 // first hit, and sorts with the shadow rays (+2.3 % of a config-3 frame, +4.3 % of config 5's: profiles/r04_wide_kernel_ladder.txt).
 constexpr uint32_t RS_MIS_BOOL = 3;
+static_assert(kTokCont == RS_CONT && kTokMis == RS_MIS && kTokShadow == RS_SHADOW && kTokMisBool == RS_MIS_BOOL,
+              "wf_ray_expand.h writes the tokens of this format");
 // estimate_direct_emit's return value carries this beside the PF_NEE_* bits (it is not a path flag)
 constexpr int NEE_MIS_BOOL = 0x100;
 
@@ -150,8 +153,10 @@ struct Queues {
     // counts64[0]: low 32 bits = trace-queue length, high 32 bits = shadow rays among them;
     // counts64[1]: shade-queue length
     unsigned long long* counts64;
-    // sort key of every trace-queue entry (ray_sort_key), written with the entry when the next wavefront will be
-    // traced in Morton order; null otherwise
+    // set when the next wavefront will be traced in Morton order, null otherwise. While set, the shading kernel writes no
+    // trace-queue entries: per path that emits a ray it leaves ONE sort pair at the path's position j in `shade`, the key
+    // (ray_sort_cell of the point its rays leave from) in keys[j] and the value (path_entry_pack: record, which rays) in
+    // trace[j]; the host sorts the pairs and expands them into `trace` (wf_ray_expand.h). counts64 means what it always means.
     uint32_t* keys;
     float key_lo[3], key_inv[3];  // scene bounds: lower corner, 1 / extent
 };
@@ -159,7 +164,7 @@ struct Queues {
 #ifndef PB_SORT_AXIS_BITS
 #define PB_SORT_AXIS_BITS 5
 #endif
-constexpr int kSortKeyBits = 3 * PB_SORT_AXIS_BITS + 1;
+constexpr int kSortKeyBits = 3 * PB_SORT_AXIS_BITS;  // the any-hit rays are split off after the sort (wf_ray_expand.h), not by a key bit
 // Morton code of the cell of `o` in the scene bounds, PB_SORT_AXIS_BITS bits per axis
 PB_DEV uint32_t ray_sort_cell(float ox, float oy, float oz, const float* lo, const float* inv) {
     constexpr float kCells = (float)(1 << PB_SORT_AXIS_BITS);
@@ -237,18 +242,22 @@ PB_DEV AppendSlots block_reserve(BlockAppend& sh, const Queues& q, bool cont, bo
     return a;
 }
 // The queue writes that go with a reservation: path p into the shade queue, its rays (records at index `rec`) into the
-// trace queue. cell = ray_sort_cell of the point the path's rays leave from (used only when q.keys is set). mis_bool: the
-// MIS ray is queued as RS_MIS_BOOL.
+// trace queue. mis_bool: the MIS ray is queued as RS_MIS_BOOL. With q.keys set the path's rays go into one sort pair at its
+// shade-queue position instead (see Queues::keys): the three rays leave from the same surface point, so one cell
+// (ray_sort_cell of that point) serves them all; a path that stays in the shade queue emits at least one ray.
 PB_DEV void block_write(const Queues& q, const AppendSlots& a, uint32_t p, uint32_t rec, bool cont, bool mis, bool shadow, bool again,
                         uint32_t cell, bool mis_bool) {
+    if (q.keys) {
+        if (again) {
+            q.keys[a.shade] = cell;
+            q.trace[a.shade] = path_entry_pack(rec, cont, mis, shadow, mis_bool);  // rec < 2^kPathRecBits: RenderJob::alloc_path_buffers
+            q.shade[a.shade] = p;
+        }
+        return;
+    }
     if (cont) q.trace[a.cont] = rec * 4u + RS_CONT;
     if (mis) q.trace[a.mis] = rec * 4u + (mis_bool ? RS_MIS_BOOL : (uint32_t)RS_MIS);
     if (shadow) q.trace[a.shadow] = rec * 4u + RS_SHADOW;
-    if (q.keys) {  // the three rays leave from the same surface point: one cell, the any-hit flag on top
-        if (cont) q.keys[a.cont] = cell;
-        if (mis) q.keys[a.mis] = mis_bool ? (cell | (1u << (kSortKeyBits - 1))) : cell;
-        if (shadow) q.keys[a.shadow] = cell | (1u << (kSortKeyBits - 1));
-    }
     if (again) q.shade[a.shade] = p;
 }
 // both at once, for a kernel that keeps its records at the path's number (k_shade_direct)

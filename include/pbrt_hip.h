@@ -635,6 +635,15 @@ int pbrt_hip_context_set_wide_build(PbrtHipContext* ctx, int where);
 enum { PBRT_WIDE_LAYOUT_AUTO = 0, PBRT_WIDE_LAYOUT_PACKED = 1, PBRT_WIDE_LAYOUT_LINES = 2 };
 int pbrt_hip_context_set_wide_layout(PbrtHipContext* ctx, int layout);
 int pbrt_hip_scene_wide_stride(const PbrtHipScene* scene);
+/* The camera rays (wavefront 0) of a render of a one-level scene with wide records, when a wave of paths is the 64 samples of one
+ * pixel (samples_per_wave 64, the default, and a pass whose samples per pixel are a multiple of 64): PBRT_CAMERA_PACKETS_AUTO (the
+ * default) walks the tree once per wave (csrc/trace_wide_packet.h), _OFF keeps one walk per ray. Same film bytes, same ray counts.
+ * pbrt_hip_context_camera_kernel: which of the two traced the camera rays of the context's last render, PBRT_CAMERA_KERNEL_PACKET
+ * or _PER_LANE (every scene, sampler layout and counting mode the packet kernel is not built for); -1 for a null context. */
+enum { PBRT_CAMERA_PACKETS_AUTO = 0, PBRT_CAMERA_PACKETS_OFF = 1 };
+enum { PBRT_CAMERA_KERNEL_PER_LANE = 0, PBRT_CAMERA_KERNEL_PACKET = 1 };
+int pbrt_hip_context_set_camera_packets(PbrtHipContext* ctx, int mode);
+int pbrt_hip_context_camera_kernel(PbrtHipContext* ctx);
 
 /* ---- batch Primitive::intersect / intersect_p (src/core/primitive.rs:17-30 via
  * Scene::intersect / intersect_p, src/core/scene.rs:40-46) ----
@@ -678,6 +687,10 @@ int pbrt_hip_get_wide_counters(PbrtHipContext* ctx, int reset, uint64_t counters
  * Returns records per second. Measurement only. */
 int pbrt_hip_probe_gather(PbrtHipContext* ctx, int64_t table_bytes, int32_t record_bytes, int32_t waves_per_simd, int32_t iters,
                           double* records_per_second);
+/* The same chain one per WAVE over a one-level scene's own wide records, at 8 waves per SIMD: the fetch pattern of the packet
+ * kernel (csrc/trace_wide_packet.h). form 0: scalar loads (s_load_dwordx8 + s_load_dwordx4); form 1: one global_load_dword in
+ * which lane i fetches dword i, then v_readlane. Result: record fetches of all waves per second. Measurement only. */
+int pbrt_hip_probe_packet_fetch(PbrtHipScene* scene, int32_t form, int32_t iters, double* wave_steps_per_second);
 /* The shading kernel's access pattern with a known byte count, for calibrating a profiler's memory counters on it
  * (profiles/r04_fetch_size_calibration_shade.txt): a shade queue of ascending path numbers (density_permille of n_paths) and,
  * per queued path, `parts` of: 1 nine 16-B SoA records, 2 two 32-B ray records (slot-major, 32-B stride), 4 one 8-B and two

@@ -10,6 +10,7 @@
 
 #include "scene.h"
 #include "trace_wide.h"
+#include "trace_wide_packet.h"
 
 namespace pb {
 
@@ -46,6 +47,16 @@ template <bool COUNT, int INST>
 inline int wide_grid(const PbrtHipScene* s) {
     return persistent_grid(s, (COUNT || INST) ? PB_WIDE_INST_WAVES : PB_WIDE_WAVES, wide_stack_lds(INST), wide_world_lds_bytes(INST));
 }
+
+// The camera wavefront as one-pixel wave packets (trace_wide_packet.h: k_trace_wide_packet instead of k_trace_wide<false, 0>): the
+// wide records of a one-level scene, no counting, a wave of paths = the 64 samples of one pixel (PassParams::group_shift == 6), a
+// tree whose walk fits the wave's stack, and pbrt_hip_context_set_camera_packets has not turned it off. Everything else —
+// later wavefronts, two-level, sphere and moving scenes, pbrt_hip_li batches, counting runs — launches what it always did.
+inline bool use_camera_packets(const PbrtHipScene* s, const TraceChoice& c, int wavefront, int group_shift) {
+    return wavefront == 0 && c.kind == TraceKind::Wide && c.inst == 0 && !c.count && group_shift == 6 && s->ctx->camera_packets == 0 &&
+           s->wide_stack_need <= kPacketStack;
+}
+inline int packet_grid(const PbrtHipScene* s) { return s->ctx->n_cus * PB_PACKET_WAVES; }  // 256 bytes of LDS per wave: the registers set it
 
 template <TraceKind K>
 using TraceKindC = std::integral_constant<TraceKind, K>;

@@ -181,6 +181,25 @@ extern "C" int pbrt_hip_context_set_wide_layout(PbrtHipContext* ctx, int layout)
 }
 PB_ABI_CATCH
 
+extern "C" int pbrt_hip_context_set_camera_packets(PbrtHipContext* ctx, int mode) try {
+    if (!ctx) return PBRT_HIP_ERR_INVALID;
+    PB_ENTER(ctx);
+    if (mode < PBRT_CAMERA_PACKETS_AUTO || mode > PBRT_CAMERA_PACKETS_OFF) {
+        ctx->last_error = "camera packets must be PBRT_CAMERA_PACKETS_AUTO or _OFF";
+        return PBRT_HIP_ERR_INVALID;
+    }
+    ctx->camera_packets = mode;
+    return PBRT_HIP_OK;
+}
+PB_ABI_CATCH
+
+extern "C" int pbrt_hip_context_camera_kernel(PbrtHipContext* ctx) try {
+    if (!ctx) return -1;
+    PB_LOCK(ctx);
+    return ctx->camera_kernel;
+}
+PB_ABI_CATCH
+
 extern "C" int pbrt_hip_scene_wide_stride(const PbrtHipScene* s) try {
     return s ? (s->has_wide ? s->wide.vec_stride * 16 : 0) : -1;
 }
@@ -1106,6 +1125,7 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
             s->wide.root_ref = dt->wide.root_ref;
             s->n_wide_records = dt->wide.n_records;
             s->has_wide = true;
+            s->wide_stack_need = dt->wide.stack_need;
             spill_entries = std::max(spill_entries, dt->wide.stack_need + 1 - kWideStackLds);
         } else if (dt && dt->h_nodes.empty()) {
             s->wide_reason = dt->wide_reason ? dt->wide_reason : "tree built on the device: no wide records";
@@ -1200,7 +1220,8 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
                 s->wide.root_ref = wd.root_ref;
                 s->n_wide_records = wd.n_records;
                 s->has_wide = true;
-                spill_entries = std::max(spill_entries, wd.stack_need + 1 - kWideStackLds);
+                s->wide_stack_need = wd.stack_need;
+            spill_entries = std::max(spill_entries, wd.stack_need + 1 - kWideStackLds);
             }
             if (d_flat) {  // only the builder needed it
                 (void)hipFree(d_flat);
@@ -1219,7 +1240,8 @@ static int scene_create_impl(PbrtHipContext* ctx, const float* positions, int32_
                 s->wide.root_ref = wt.root_ref;
                 s->n_wide_records = wt.n_records;
                 s->has_wide = true;
-                spill_entries = std::max(spill_entries, wt.stack_need + 1 - kWideStackLds);
+                s->wide_stack_need = wt.stack_need;
+            spill_entries = std::max(spill_entries, wt.stack_need + 1 - kWideStackLds);
             }
         }
     }

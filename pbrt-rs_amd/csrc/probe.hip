@@ -5,6 +5,9 @@
 // child-pair records (trace.h), from a table of a given size, at a given number of resident waves per SIMD and with
 // nothing else to do. The result is a measured ceiling, for bench.py's roofline line (measurement only: no part of
 // rendering calls this).
+//
+// pbrt_hip_probe_packet_fetch: the same chain ONE PER WAVE over a scene's own wide records, as trace_wide_packet.h walks them,
+// in the two forms a wave can fetch a wave-uniform record in.
 #include <hip/hip_runtime.h>
 #include "abi_guard.h"
 
@@ -236,6 +239,81 @@ extern "C" int pbrt_hip_probe_state_stream(PbrtHipContext* ctx, int64_t n_paths,
     if (parts & 16) wr += (16ll * kProbeWriteVec16 + 32ll * kProbeWriteRaySlots + 16ll + 4ll * kProbeQueueWords) * n_queue;
     *bytes_read = rd;
     *bytes_written = wr;
+    return rc;
+}
+PB_ABI_CATCH
+
+// ------------------------------------------------------------------------------------
+// pbrt_hip_probe_packet_fetch: dependent fetches of 48-byte records, one chain per WAVE (the access pattern of
+// trace_wide_packet.h), over the wide records of a scene, at 8 waves per SIMD and with nothing else to do.
+//   form 0: scalar loads through the constant address space (s_load_dwordx8 + s_load_dwordx4);
+//   form 1: one global_load_dword in which lane i fetches dword i of the record, then twelve v_readlane into SGPRs.
+// Measurement only.
+// ------------------------------------------------------------------------------------
+namespace {
+template <int FORM>
+__global__ void __launch_bounds__(256, 8) k_probe_packet_fetch(const uint4* __restrict__ table, uint32_t n_records, int vec_stride, int iters,
+                                                                uint32_t* out) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    typedef const __attribute__((address_space(4))) uint4 ConstVec;  // a uniform address in the constant address space: scalar loads
+#else  // the host pass only parses this function
+    typedef const uint4 ConstVec;
+#endif
+    const uint32_t wave = (blockIdx.x * 256u + threadIdx.x) >> 6;
+    const int lane = threadIdx.x & 63;
+    uint32_t idx = (uint32_t)__builtin_amdgcn_readfirstlane((int)(wave * 2654435761u % n_records));
+    uint32_t acc = 0;
+    for (int it = 0; it < iters; ++it) {
+        const uint4* r = table + (size_t)vec_stride * idx;
+        uint32_t h;
+        if (FORM == 0) {
+            ConstVec* p = (ConstVec*)r;
+            const uint4 a = p[0], b = p[1], c = p[2];
+            h = a.x ^ a.y ^ a.z ^ a.w ^ b.x ^ b.y ^ b.z ^ b.w ^ c.x ^ c.y ^ c.z ^ c.w;
+        } else {
+            const uint32_t w = ((const uint32_t*)r)[lane < 12 ? lane : 0];
+            h = 0;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) h ^= (uint32_t)__builtin_amdgcn_readlane((int)w, k);
+        }
+        acc += h;
+        idx = (h * 2654435761u + (uint32_t)it) % n_records;  // depends on every dword of this step
+    }
+    if (lane == 0) out[wave] = acc;
+}
+}  // namespace
+
+extern "C" int pbrt_hip_probe_packet_fetch(PbrtHipScene* s, int32_t form, int32_t iters, double* wave_steps_per_second) try {
+    if (!s || !wave_steps_per_second || form < 0 || form > 1 || iters <= 0) return PBRT_HIP_ERR_INVALID;
+    PbrtHipContext* ctx = s->ctx;
+    PB_ENTER(ctx);
+    if (!s->has_wide || s->d.bvh.instanced || s->n_wide_records < 1) {
+        ctx->last_error = "pbrt_hip_probe_packet_fetch: a one-level scene with wide records";
+        return PBRT_HIP_ERR_INVALID;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int blocks = ctx->n_cus * 8;  // 4 SIMDs x 8 waves / 4 waves per block: every block resident
+    uint32_t* out = nullptr;
+    HIP_TRY(ctx, hipMalloc((void**)&out, (size_t)blocks * 4 * sizeof(uint32_t)));
+    hipStream_t st = ctx->stream;
+    int rc = PBRT_HIP_OK;
+    float best = 1e30f;
+    for (int rep = 0; rep < 4 && rc == PBRT_HIP_OK; ++rep) {  // the first repetition warms the caches
+        if (!pb::hip_ok(ctx, hipEventRecord(ctx->ev0, st), "hipEventRecord")) rc = PBRT_HIP_ERR_DEVICE;
+        if (form == 0)
+            hipLaunchKernelGGL(k_probe_packet_fetch<0>, dim3(blocks), dim3(256), 0, st, s->wide.nodes, (uint32_t)s->n_wide_records, s->wide.vec_stride, iters, out);
+        else
+            hipLaunchKernelGGL(k_probe_packet_fetch<1>, dim3(blocks), dim3(256), 0, st, s->wide.nodes, (uint32_t)s->n_wide_records, s->wide.vec_stride, iters, out);
+        if (!pb::hip_ok(ctx, hipGetLastError(), "probe launch") || !pb::hip_ok(ctx, hipEventRecord(ctx->ev1, st), "hipEventRecord") ||
+            !pb::hip_ok(ctx, hipEventSynchronize(ctx->ev1), "hipEventSynchronize"))
+            rc = PBRT_HIP_ERR_DEVICE;
+        float ms = 0.0f;
+        if (rc == PBRT_HIP_OK && !pb::hip_ok(ctx, hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1), "hipEventElapsedTime")) rc = PBRT_HIP_ERR_DEVICE;
+        if (rc == PBRT_HIP_OK && rep > 0 && ms < best) best = ms;
+    }
+    (void)hipStreamSynchronize(st);
+    (void)hipFree(out);
+    if (rc == PBRT_HIP_OK) *wave_steps_per_second = (double)blocks * 4.0 * (double)iters / ((double)best * 1e-3);
     return rc;
 }
 PB_ABI_CATCH

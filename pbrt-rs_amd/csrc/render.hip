@@ -928,7 +928,7 @@ struct RenderJob {
     int setup_light_distribution(const SceneNeeds& needs);
     PassParams pass_params(int s0) const;
     void wait_for_counts(int& rc);
-    void trace_wavefront(const RenderEvents& ev, const Queues& qcur, uint32_t n_trace, uint32_t n_shade, int wavefront, int& rc);
+    void trace_wavefront(const RenderEvents& ev, const Queues& qcur, uint32_t n_trace, uint32_t n_shade, int wavefront, int group_shift, int& rc);
     void shade_wavefront(const PassParams& pp, int cur, int nxt, uint32_t n_shade, int wavefront, int& rc);
     void run_wavefronts(const RenderEvents& ev, const PassParams& pp, uint32_t n_paths, int& rc);
     void film_stage(const PassParams& pp, uint32_t n_paths, bool last_pass, int& rc);
@@ -1268,7 +1268,7 @@ void RenderJob::wait_for_counts(int& rc) {
 }
 
 // one wavefront's rays: the queue (sorted from the second bounce on when there are enough), then the traversal kernel
-void RenderJob::trace_wavefront(const RenderEvents& ev, const Queues& qcur, uint32_t n_trace, uint32_t n_shade, int wavefront, int& rc) {
+void RenderJob::trace_wavefront(const RenderEvents& ev, const Queues& qcur, uint32_t n_trace, uint32_t n_shade, int wavefront, int group_shift, int& rc) {
     RENDER_TRY(hipMemsetAsync(ctx->d_work_counter, 0, kWorkCounters * sizeof(unsigned int), st));
     const uint32_t* trace_queue = qcur.trace;
     if (sort_rays && wavefront >= kSortFrom) {
@@ -1299,6 +1299,7 @@ void RenderJob::trace_wavefront(const RenderEvents& ev, const Queues& qcur, uint
     }
     RENDER_TRY(hipEventRecord(ev.t0, st));
     const int segments = (wavefront == 0 && !trace.inst) ? kQueueSegments : 1;  // see trace.h
+    if (wavefront == 0) ctx->camera_kernel = PBRT_CAMERA_KERNEL_PER_LANE;
     dispatch(trace, [&](auto kind, auto count, auto inst) {
         constexpr TraceKind K = decltype(kind)::value;
         constexpr bool COUNT = decltype(count)::value;
@@ -1311,8 +1312,15 @@ void RenderJob::trace_wavefront(const RenderEvents& ev, const Queues& qcur, uint
             WideTrees wt = s->wide;
             wt.special_list = special_list;
             wt.special_count = ctx->d_work_counter + kSpecialCount;
-            hipLaunchKernelGGL((k_trace_wide<COUNT, INST>), dim3(wide_grid<COUNT, INST>(s)), block, 0, st, wt, ps, trace_queue, n_trace,
-                               ctx->d_work_counter, segments, ctx->d_counters);
+            // the camera rays of a one-level scene, a wave = one pixel's samples: walked once per wave (trace_wide_packet.h)
+            const bool packets = use_camera_packets(s, trace, wavefront, group_shift);
+            if (wavefront == 0) ctx->camera_kernel = packets ? PBRT_CAMERA_KERNEL_PACKET : PBRT_CAMERA_KERNEL_PER_LANE;
+            if (packets)
+                hipLaunchKernelGGL(k_trace_wide_packet<WavefrontRayIO<false>>, dim3(packet_grid(s)), block, 0, st, wt,
+                                   WavefrontRayIO<false>{ps, trace_queue, n_trace, segments}, ctx->d_work_counter);
+            else
+                hipLaunchKernelGGL((k_trace_wide<COUNT, INST>), dim3(wide_grid<COUNT, INST>(s)), block, 0, st, wt, ps, trace_queue, n_trace,
+                                   ctx->d_work_counter, segments, ctx->d_counters);
             hipLaunchKernelGGL(k_trace_special<INST>, grid, block, 0, st, s->d.bvh, ps, trace_queue, n_trace, special_list,
                                ctx->d_work_counter + kSpecialCount, ctx->d_work_counter + kFollowUpCounter);
         } else if constexpr (K == TraceKind::Shapes) {
@@ -1369,7 +1377,7 @@ void RenderJob::run_wavefronts(const RenderEvents& ev, const PassParams& pp, uin
     int cur = 0, wavefront = 0;  // wavefront 0 = camera rays, 1 = first bounce + its shadow rays, ...
     while (rc == PBRT_HIP_OK && counts[1] > 0) {
         uint32_t n_trace = (uint32_t)counts[0], n_shade = (uint32_t)counts[1];
-        if (n_trace > 0) trace_wavefront(ev, q[cur], n_trace, n_shade, wavefront, rc);
+        if (n_trace > 0) trace_wavefront(ev, q[cur], n_trace, n_shade, wavefront, pp.group_shift, rc);
         int nxt = cur ^ 1;
         RENDER_TRY(hipMemsetAsync(q[nxt].counts64, 0, 2 * sizeof(unsigned long long), st));
         // the wavefront this launch of k_shade fills is traced in Morton order: have it write one sort pair per path instead

@@ -53,6 +53,8 @@ struct PbrtHipContext {
     int traversal = 0;  // PBRT_TRAVERSAL_*: pbrt_hip_context_set_traversal
     int wide_build = 0;  // PBRT_WIDE_BUILD_*: pbrt_hip_context_set_wide_build
     int wide_layout = 0;  // PBRT_WIDE_LAYOUT_*: pbrt_hip_context_set_wide_layout
+    int camera_packets = 0;  // 0 auto, 1 off: pbrt_hip_context_set_camera_packets (kernel_select.h: use_camera_packets)
+    int camera_kernel = 0;   // PBRT_CAMERA_KERNEL_*: what traced wavefront 0 of the last render (pbrt_hip_context_camera_kernel)
     unsigned long long* d_counters = nullptr;  // [0..3] mode 1: node, prim, rays, instance tests; [4..7] mode 2
     uint64_t counted_rays = 0;
     // ray-queue heads of the persistent traversal kernels: [0, kQueueSegments) the launch's segments,
@@ -229,6 +231,7 @@ struct PbrtHipScene {
     bool has_wide = false;
     pb::WideTrees wide{};
     int n_wide_records = 0;
+    int wide_stack_need = 0;  // one-level scenes: WideTree::stack_need (the packet kernel's stack holds kPacketStack entries)
     std::string wide_reason;  // why the scene has none
     // moving instances (pbrt_hip_scene_create_two_level_moving): an instance with PbrtInstanceMotion.animated; the side table
     // (motion.h) has one row per top-level leaf slot and rides in the MOV kernels' arguments, not in DevBVH

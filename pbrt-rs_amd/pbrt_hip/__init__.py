@@ -25,6 +25,8 @@ SAMPLER_RANDOM, SAMPLER_STRATIFIED, SAMPLER_ZEROTWO, SAMPLER_HALTON = 0, 1, 2, 3
 TRAVERSAL_AUTO, TRAVERSAL_STACK, TRAVERSAL_STACKLESS = 0, 1, 2   # pbrt_hip_context_set_traversal
 WIDE_BUILD_DEVICE, WIDE_BUILD_HOST, WIDE_BUILD_NONE = 0, 1, 2       # pbrt_hip_context_set_wide_build
 WIDE_LAYOUT_AUTO, WIDE_LAYOUT_PACKED, WIDE_LAYOUT_LINES = 0, 1, 2    # pbrt_hip_context_set_wide_layout
+CAMERA_PACKETS_AUTO, CAMERA_PACKETS_OFF = 0, 1                      # pbrt_hip_context_set_camera_packets
+CAMERA_KERNEL_PER_LANE, CAMERA_KERNEL_PACKET = 0, 1                 # pbrt_hip_context_camera_kernel
 TILE_ORDER_MORTON, TILE_ORDER_ROW_MAJOR = 0, 1                     # PbrtRenderParams.tile_order
 
 EXPORTS = [
@@ -33,6 +35,7 @@ EXPORTS = [
     "pbrt_hip_scene_create_instanced", "pbrt_hip_scene_create_with_spheres", "pbrt_hip_scene_destroy", "pbrt_hip_intersect",
     "pbrt_hip_intersect_p", "pbrt_hip_intersect_device", "pbrt_hip_intersect_p_device", "pbrt_hip_synchronize",
     "pbrt_hip_context_set_deadline", "pbrt_hip_context_set_traversal", "pbrt_hip_context_is_lost", "pbrt_hip_context_set_wide_build", "pbrt_hip_context_set_wide_layout", "pbrt_hip_scene_wide_stride",
+    "pbrt_hip_context_set_camera_packets", "pbrt_hip_context_camera_kernel", "pbrt_hip_probe_packet_fetch",
     "pbrt_hip_trace_timing", "pbrt_hip_set_counting", "pbrt_hip_get_counters", "pbrt_hip_render", "pbrt_hip_render_device", "pbrt_hip_film_to_rgb",
     "pbrt_hip_bvh_build_hlbvh_device", "pbrt_hip_scene_create_hlbvh", "pbrt_hip_scene_set_shading_data", "pbrt_hip_tile_partition", "pbrt_hip_tile_partition_order", "pbrt_hip_filter_table", "pbrt_hip_sample_bounds", "pbrt_hip_write_pfm", "pbrt_hip_write_png", "pbrt_hip_write_exr",
     "pbrt_hip_comm_unique_id", "pbrt_hip_comm_create", "pbrt_hip_comm_destroy", "pbrt_hip_film_reduce",
@@ -197,6 +200,9 @@ def lib():
         L.pbrt_hip_context_set_wide_build.argtypes = [vp, ctypes.c_int]
         L.pbrt_hip_context_set_wide_layout.argtypes = [vp, ctypes.c_int]
         L.pbrt_hip_scene_wide_stride.argtypes = [vp]
+        L.pbrt_hip_context_set_camera_packets.argtypes = [vp, ctypes.c_int]
+        L.pbrt_hip_context_camera_kernel.argtypes = [vp]
+        L.pbrt_hip_probe_packet_fetch.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(ctypes.c_double)]
         L.pbrt_hip_get_counters.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64 * 4)]
         L.pbrt_hip_get_wide_counters.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64 * 4)]
         L.pbrt_hip_probe_gather.argtypes = [vp, i64, i32, i32, i32, ctypes.POINTER(ctypes.c_double)]
@@ -287,6 +293,15 @@ class Context:
         """How scenes created from now on keep their 4-wide records and triangles: WIDE_LAYOUT_AUTO (packed while they fit 8 MiB,
         else one 64-byte line each), WIDE_LAYOUT_PACKED, WIDE_LAYOUT_LINES."""
         self.check(lib().pbrt_hip_context_set_wide_layout(self.h, int(layout)), "context_set_wide_layout")
+
+    def set_camera_packets(self, mode):
+        """CAMERA_PACKETS_AUTO: the camera rays of a one-level scene are walked once per wave where a wave is one pixel's 64
+        samples; CAMERA_PACKETS_OFF: one walk per ray, as every other wavefront."""
+        self.check(lib().pbrt_hip_context_set_camera_packets(self.h, int(mode)), "context_set_camera_packets")
+
+    def camera_kernel(self):
+        """CAMERA_KERNEL_PACKET or CAMERA_KERNEL_PER_LANE: what traced the camera rays of this context's last render."""
+        return int(lib().pbrt_hip_context_camera_kernel(self.h))
 
     def set_counting(self, enable):
         """Instrumented traversal. True / 1: box / triangle test counts of the reference's loops (binary kernels);
@@ -634,6 +649,13 @@ class Scene:
     def wide_stride(self):
         """Bytes between two 4-wide records (and two wide-order triangles) in HBM: 48 packed, 64 one line each, 0 = no wide records."""
         return lib().pbrt_hip_scene_wide_stride(self.h)
+
+    def probe_packet_fetch(self, form=0, iters=256):
+        """Measured rate (wave-steps / s) of one dependent record fetch per wave over this scene's wide records: form 0 scalar
+        loads, form 1 one vector dword load + v_readlane."""
+        r = ctypes.c_double()
+        self.ctx.check(lib().pbrt_hip_probe_packet_fetch(self.h, int(form), int(iters), ctypes.byref(r)), "probe_packet_fetch")
+        return r.value
 
     def _set_shading_data(self, scene):
         """TriangleMesh n / uv (triangle.rs:17-26): scene["normals"] / scene["tangents"] (n_verts, 3), scene["uvs"] (n_verts, 2), optional."""

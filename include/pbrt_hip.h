@@ -545,7 +545,10 @@ int pbrt_hip_scene_create_instanced(PbrtHipContext* ctx, const float* positions,
  *                                        "area lights not supported with object instancing").
  * tlas_nodes / tlas_order: BVHAccel over the world bounds of those primitives in that order (pbrt_hip_bvh_build_boxes
  * over pbrt_hip_instance_bounds of each instance's object bounds, then the triangles' bounds). Hit records name a
- * triangle by its index inside its own object (instance_id >= 0) or among the world triangles (instance_id = -1). */
+ * triangle by its index inside its own object (instance_id >= 0) or among the world triangles (instance_id = -1).
+ * Every argument is checked before anything is allocated on the device: a tlas_order that names a primitive twice
+ * ("tlas_order is not a permutation") is PBRT_HIP_ERR_INVALID like every other bad argument, here and in
+ * pbrt_hip_scene_create_instanced / _two_level_moving (it used to come back as PBRT_HIP_ERR_DEVICE). */
 typedef struct PbrtObject {
     const float* positions;
     int32_t n_verts;

@@ -619,8 +619,7 @@ extern "C" int pbrt_hip_bvh_build_hlbvh_device(PbrtHipContext* ctx, const float*
     if (build_ms) *build_ms = 0.0;
     if (n_tris < 0 || n_verts < 0 || (n_tris > 0 && (!positions || !indices))) return invalid("bad mesh arguments");
     if (n_tris == 0) return PBRT_HIP_OK;  // bvh.rs:228-230
-    for (int64_t i = 0; i < 3 * (int64_t)n_tris; ++i)
-        if (indices[i] < 0 || indices[i] >= n_verts) return invalid("vertex index out of range");
+    if (!pb::mesh_indices_in_range(indices, n_tris, n_verts)) return invalid("vertex index out of range");
     const int n = n_tris;
     HL_TRY(hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
@@ -684,7 +683,7 @@ int exclusive_scan_u64(hipStream_t st, void* temp, size_t* temp_bytes, const uns
 }  // namespace pb
 
 // Tree + triangle records + leaf order for a single-level scene, all produced on the device. Inputs are
-// validated by the caller (scene_create_impl's checks on indices / tri_material / tri_light / lights).
+// validated by the caller (scene_invalid's checks on indices / tri_material / tri_light / lights, host_scene.cpp).
 namespace pb {
 int hlbvh_build_scene_tree(PbrtHipContext* ctx, const float* positions, int32_t n_verts, const int32_t* indices,
                            int32_t n_tris, const int32_t* tri_material, const int32_t* tri_light, const PbrtLight* lights,

@@ -730,8 +730,7 @@ extern "C" int pbrt_hip_scene_set_shading_data(PbrtHipScene* s, const float* pos
     if (!normals && !tangents && !uvs) return fail("no normals, tangents or uvs given");
     if (s->d.bvh.tri_shading) return fail("shading data already set");
     if (s->d.bvh.has_spheres) return fail("per-vertex shading data is not supported for scenes with spheres");
-    for (int64_t i = 0; i < 3 * (int64_t)n_tris; ++i)
-        if (indices[i] < 0 || indices[i] >= n_verts) return fail("vertex index out of range");
+    if (!mesh_indices_in_range(indices, n_tris, n_verts)) return fail("vertex index out of range");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     DevBuf tmp(ctx);
     bool ok = true;

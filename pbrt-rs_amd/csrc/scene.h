@@ -247,34 +247,63 @@ inline bool hip_ok(PbrtHipContext* ctx, hipError_t e, const char* what) {
     return false;
 }
 
+// a device copy of n elements that the caller owns ...
 template <class T>
-inline T* dev_upload(PbrtHipScene* s, const T* src, size_t n, bool* ok) {
+inline T* dev_copy(PbrtHipContext* ctx, const T* src, size_t n, bool* ok) {
     void* p = nullptr;
     size_t bytes = (n ? n : 1) * sizeof(T);
-    if (!hip_ok(s->ctx, hipMalloc(&p, bytes), "hipMalloc")) {
+    if (!hip_ok(ctx, hipMalloc(&p, bytes), "hipMalloc")) {
         *ok = false;
         return nullptr;
     }
-    s->allocs.push_back(p);
-    if (n && !hip_ok(s->ctx, hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy H2D")) *ok = false;
+    if (n && !hip_ok(ctx, hipMemcpy(p, src, n * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy H2D")) *ok = false;
     return (T*)p;
 }
+// ... and one that the scene owns
+template <class T>
+inline T* dev_upload(PbrtHipScene* s, const T* src, size_t n, bool* ok) {
+    T* p = dev_copy(s->ctx, src, n, ok);
+    if (p) s->allocs.push_back(p);
+    return p;
+}
 
-// A single-level scene tree built and re-laid out on the device (hlbvh_gpu.hip): the scene takes
-// ownership of the three device arrays.
-// device arrays of the 4-wide records of one tree, built on the device (wide_gpu.hip); the caller owns them
+// true when every one of the 3 * n_tris indices names a vertex (host_scene.cpp); whoever takes a mesh from the caller asks
+// before the indices become subscripts and reports "vertex index out of range"
+bool mesh_indices_in_range(const int32_t* indices, int64_t n_tris, int32_t n_verts);
+
+// Device arrays of the 4-wide records of one tree, whoever laid them out (wide_gpu.hip on the device, host_wide.cpp on the
+// host). The struct frees what it still owns; a scene that takes the arrays over nulls the pointers.
 struct WideDeviceTree {
     uint32_t* nodes = nullptr;    // 12 dwords per record
     float* tris = nullptr;        // 12 floats per wide-order triangle
     float* leaf_boxes = nullptr;  // 8 floats per wide-order triangle position
     int32_t root_ref = 0;
-    int n_records = -1;  // -1: not built
+    int n_records = -1;  // -1: not built (reason says why, where the builder reports it here)
     int stack_need = 0;
+    const char* reason = nullptr;
+    WideDeviceTree() = default;
+    WideDeviceTree(const WideDeviceTree&) = delete;
+    WideDeviceTree& operator=(const WideDeviceTree&) = delete;
+    ~WideDeviceTree() {
+        if (nodes) (void)hipFree(nodes);
+        if (tris) (void)hipFree(tris);
+        if (leaf_boxes) (void)hipFree(leaf_boxes);
+    }
 };
 bool build_wide_tree_device(PbrtHipContext* ctx, const PbrtLinearBVHNode* d_nodes, int32_t n_nodes, const float* d_tris, int32_t n_slots,
                             const PbrtLinearBVHNode& root, WideDeviceTree* out, const char** reason);
 
+// A single-level scene tree built and re-laid out on the device (hlbvh_gpu.hip). The struct frees the device arrays it
+// still owns; the scene takes them over by nulling the pointers.
 struct DeviceTree {
+    DeviceTree() = default;
+    DeviceTree(const DeviceTree&) = delete;
+    DeviceTree& operator=(const DeviceTree&) = delete;
+    ~DeviceTree() {
+        if (inodes) (void)hipFree(inodes);
+        if (tris) (void)hipFree(tris);
+        if (slot_prim) (void)hipFree(slot_prim);
+    }
     float4* inodes = nullptr;   // 64-B child-pair records
     float4* tris = nullptr;     // 48-B triangles in leaf order
     int* slot_prim = nullptr;   // leaf slot -> caller's triangle index

@@ -111,7 +111,7 @@ __global__ void __launch_bounds__(kWB) k_wide_stack_need(const uint32_t* __restr
 bool build_wide_tree_device(PbrtHipContext* ctx, const PbrtLinearBVHNode* d_nodes, int32_t n_nodes, const float* d_tris,
                             int32_t n_slots, const PbrtLinearBVHNode& root, WideDeviceTree* out, const char** reason) {
     *reason = nullptr;
-    *out = WideDeviceTree();
+    out->n_records = -1;  // *out: a fresh WideDeviceTree, which owns nothing yet
     hipStream_t st = ctx->stream;
     if (n_nodes <= 0 || n_slots <= 0) {
         *reason = "empty tree";

@@ -440,6 +440,40 @@ def test_error_behaviour_of_the_c_abi(hip_ctx):
     g.close()
 
 
+def test_duplicated_tlas_order_entry_is_a_bad_argument(hip_ctx):
+    """A top-level order that names a primitive twice is refused before anything reaches the device, as the bad argument it
+    is: PBRT_HIP_ERR_INVALID (1), not PBRT_HIP_ERR_DEVICE. 2 objects x 3 instances + 2 world triangles, one of them a light;
+    the same context then builds the valid scene, which answers rays as the oracle does."""
+    sc = scenes.two_level_scene(n_instances=3)
+    sc["objects"] = sc["objects"][:2]
+    sc["instance_object"] = np.array([0, 1, 0], dtype=np.int32)
+    w = sc["world"]
+    sc["world"] = dict(positions=w["positions"], indices=w["indices"][2:], tri_material=w["tri_material"][2:],
+                       tri_light=np.array([-1, 0], dtype=np.int32))
+    sc["lights"] = scenes._lights([(scenes.LIGHT_DIFFUSE_AREA, (12.0, 11.0, 9.0), 1, 0, 1)])
+    trees, inst, tlas_nodes, tlas_order = pbrt_hip.build_general_two_level(sc)
+    assert len(tlas_order) == 5
+    bad = tlas_order.copy()
+    bad[0] = bad[1]
+    with pytest.raises(pbrt_hip.PbrtHipError, match=r"pbrt_hip_scene_create_two_level failed \(1\): tlas_order is not a permutation"):
+        pbrt_hip.Scene(hip_ctx, sc, bvh=(trees, inst, tlas_nodes, bad))
+    assert not hip_ctx.is_lost()
+    osc = oracle.OracleScene(sc)
+    gsc = pbrt_hip.Scene(hip_ctx, sc, bvh=(trees, inst, tlas_nodes, tlas_order))
+    rays = scenes.random_rays(100, 43, origin_extent=3.0)    # aimed, loosely, at the three instances and the light in turn
+    targets = np.concatenate([sc["instances"][:, 0, :3, 3], w["positions"][4:8].mean(axis=0, keepdims=True)])
+    rays["d"] = targets[np.arange(100) % 4] + 0.1 * rays["d"] - rays["o"]
+    rays["t_max"][::3] = np.float32(4.0)
+    cpu, _ = osc.intersect(rays)
+    gpu = gsc.intersect(rays)
+    _assert_hits_equal(gpu, cpu)
+    assert np.array_equal(gpu["instance_id"], cpu["instance_id"])
+    hit = cpu["prim_id"] >= 0
+    assert (np.bincount(cpu["instance_id"][hit] + 1, minlength=4) >= 10).all()    # the world triangles and every instance are hit
+    gsc.close()
+    osc.close()
+
+
 def test_context_creation_from_several_threads_keeps_each_threads_error(hip_ctx):
     """pbrt_hip_context_create may be entered from several host threads at once; a creation that fails has no context to
     carry its message, so pbrt_hip_last_error(NULL) is the CALLING thread's (it was one unlocked global). Two

@@ -46,7 +46,7 @@ def chk():
 
 
 def _tri_records(positions, indices, order):
-    """The scene's 48-B leaf-order triangle records (pbrt_hip.hip scene_create_impl): 9 vertex floats, prim, material, flags."""
+    """The scene's 48-B leaf-order triangle records (host_scene.cpp plan_scene): 9 vertex floats, prim, material, flags."""
     tri = positions[indices[order]].reshape(-1, 9).astype(np.float32)
     rec = np.zeros((len(order), 12), dtype=np.float32)
     rec[:, :9] = tri

@@ -526,6 +526,41 @@ int pbrt_hip_scene_create_with_shapes(PbrtHipContext* ctx, const float* position
                                       int32_t n_lights, const PbrtShape* shapes, int32_t n_shapes,
                                       const PbrtLinearBVHNode* nodes, int32_t n_nodes, const int32_t* prim_order,
                                       PbrtHipScene** out);
+/* Curve (src/shapes/curve.rs after pbrt-v3's Curve: DESIGN.md D98-D106): one segment [u_min, u_max] of a cubic Bezier curve
+ * with a width that varies linearly along it, seen as a flat strip that faces every ray (FLAT), as that strip shaded like
+ * a cylinder (CYLINDER) or as a ribbon whose orientation turns from n0 to n1 (RIBBON). A record holds what CurveCommon and
+ * Curve::new take: the control points, widths and normals are those of the WHOLE curve, u_min / u_max name this record's
+ * part of it (pbrt's CreateCurveShape makes 2^split_depth records per curve). to_object must be the inverse of to_world;
+ * both are affine. Curve::sample is unimplemented in pbrt-v3 and the reference, so a curve carries no area light. */
+enum PbrtCurveType { PBRT_CURVE_FLAT = 0, PBRT_CURVE_CYLINDER = 1, PBRT_CURVE_RIBBON = 2 };
+typedef struct PbrtCurve {
+    int32_t type;                /* PbrtCurveType */
+    int32_t reverse_orientation;
+    int32_t material;            /* row of `materials` */
+    float cp[4][3];              /* object space */
+    float width0, width1;        /* at u = 0 and u = 1 of the whole curve */
+    float u_min, u_max;          /* this segment, 0 <= u_min < u_max <= 1 */
+    float n0[3], n1[3];          /* ribbons: the orientation at u = 0 and u = 1 (normalised at creation); else unused */
+    float to_world[16];          /* row-major, last row (0,0,0,1) */
+    float to_object[16];         /* its inverse */
+} PbrtCurve;
+/* Shape::world_bound per curve record: object_to_world * Curve::object_bound (curve.rs:285-294: the box of the segment's
+ * four control points, expanded by half the larger of its two end widths). bounds: n x {min.xyz, max.xyz}. Host only. */
+int pbrt_hip_curve_world_bounds(const PbrtCurve* curves, int32_t n, float* bounds);
+/* As pbrt_hip_scene_create_with_shapes with curve records behind the shapes: curve j is primitive n_tris + n_shapes + j in
+ * prim_order. A hit record on a curve carries (u, v, 0) in (b0, b1, b2), u along the whole curve and v across its width;
+ * inside one curve the hit with the smallest t is reported (ties to the smaller u). With n_curves == 0 the call is
+ * pbrt_hip_scene_create_with_shapes. PBRT_HIP_ERR_INVALID (pbrt_hip_last_error says why) for whatever that call refuses and
+ * for a curve of unknown type, control points that are not finite, a width that is negative or not finite, two widths
+ * that are both zero, u_min >= u_max or a range outside [0, 1], a ribbon with a zero normal or with n0 == -n1, a transform
+ * that is not affine, a material out of range, and a light whose `prim` names a curve. The limits are those of scenes with
+ * shapes: one level, binary-record traversal, no lobe rows, no per-vertex shading data. */
+int pbrt_hip_scene_create_with_curves(PbrtHipContext* ctx, const float* positions, int32_t n_verts, const int32_t* indices,
+                                      int32_t n_tris, const int32_t* tri_material, const PbrtMaterial* materials,
+                                      int32_t n_materials, const int32_t* tri_light, const PbrtLight* lights,
+                                      int32_t n_lights, const PbrtShape* shapes, int32_t n_shapes, const PbrtCurve* curves,
+                                      int32_t n_curves, const PbrtLinearBVHNode* nodes, int32_t n_nodes,
+                                      const int32_t* prim_order, PbrtHipScene** out);
 /* Two-level scene of BASELINE config 5's shape: `n_instances` TransformedPrimitives of ONE object-space triangle
  * aggregate (pbrt_hip_scene_create_two_level with one object and no world-space triangles). blas_* = BVHAccel over the
  * triangles (object space); tlas_* = BVHAccel over the instances' world bounds, tlas_order[slot] = instance index.

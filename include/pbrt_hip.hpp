@@ -44,6 +44,7 @@ struct Point3f {
     Float x = 0, y = 0, z = 0;
 };
 using Vector3f = Point3f;
+using Normal3f = Point3f;
 struct Bounds3f {
     Point3f min, max;
 };
@@ -154,6 +155,38 @@ struct Cylinder : Shape {
     Cylinder(const double o2w[16], const double w2o[16], bool reverse_orientation, Float radius, Float z_min, Float z_max, Float phi_max,
              int32_t material = 0, int32_t area_light = -1)
         : Shape(PBRT_SHAPE_CYLINDER, o2w, w2o, reverse_orientation, radius, z_min, z_max, 0, phi_max, material, area_light) {}
+};
+// Curve (src/shapes/curve.rs after pbrt-v3; include/pbrt_hip.h: PbrtCurve): one segment [u_min, u_max] of a cubic Bezier curve.
+// CurveCommon::new's arguments (the whole curve's control points in object space, width0, width1, type, the ribbon's two normals
+// or nullptr) and Curve::new's (o2w, w2o, reverse_orientation, u_min, u_max) in one record; matrices as for Shape above.
+// Curve::segments is pbrt-v3's CreateCurveShape: the 2^split_depth records of one curve. A curve carries no area light
+// (Curve::sample is unimplemented).
+enum class CurveType { Flat = PBRT_CURVE_FLAT, Cylinder = PBRT_CURVE_CYLINDER, Ribbon = PBRT_CURVE_RIBBON };
+struct Curve {
+    PbrtCurve record;
+    Curve(const double o2w[16], const double w2o[16], bool reverse_orientation, const Point3f cp[4], Float width0, Float width1, CurveType type,
+          const Normal3f* normals, Float u_min, Float u_max, int32_t material = 0) {
+        std::memset(&record, 0, sizeof(record));
+        double inv[16];
+        if (!w2o) inverse_affine(o2w, inv);
+        for (int k = 0; k < 12; ++k) record.to_world[k] = (float)o2w[k], record.to_object[k] = (float)(w2o ? w2o[k] : inv[k]);
+        record.to_world[15] = record.to_object[15] = 1.0f;
+        record.type = (int32_t)type, record.reverse_orientation = reverse_orientation ? 1 : 0, record.material = material;
+        for (int i = 0; i < 4; ++i) record.cp[i][0] = cp[i].x, record.cp[i][1] = cp[i].y, record.cp[i][2] = cp[i].z;
+        record.width0 = width0, record.width1 = width1, record.u_min = u_min, record.u_max = u_max;
+        if (normals) {
+            record.n0[0] = normals[0].x, record.n0[1] = normals[0].y, record.n0[2] = normals[0].z;
+            record.n1[0] = normals[1].x, record.n1[1] = normals[1].y, record.n1[2] = normals[1].z;
+        }
+    }
+    static std::vector<Curve> segments(const double o2w[16], const double w2o[16], bool reverse_orientation, const Point3f cp[4], Float width0,
+                                       Float width1, CurveType type, const Normal3f* normals, int split_depth, int32_t material = 0) {
+        std::vector<Curve> out;
+        const int n = 1 << split_depth;
+        for (int i = 0; i < n; ++i)
+            out.emplace_back(o2w, w2o, reverse_orientation, cp, width0, width1, type, normals, (Float)i / (Float)n, (Float)(i + 1) / (Float)n, material);
+        return out;
+    }
 };
 struct BuildOnDevice {};  // tag: BVHAccel::new(HLBVH) built and laid out on the GPU (bvh.rs:475-568), nothing of the tree crosses PCIe
 
@@ -349,6 +382,42 @@ public:
                                                mesh.lights.data(), (int32_t)mesh.lights.size(), records.data(), (int32_t)ns, nodes, n_nodes, order, &h_);
         pbrt_hip_free(nodes), pbrt_hip_free(order);
         ctx_->check(rc, "BVHAccel::new: pbrt_hip_scene_create_with_shapes");
+    }
+    // Triangles, quadric shapes and curve segments under one BVHAccel: primitives in that order, the curves' world bounds from
+    // pbrt_hip_curve_world_bounds (Shape::world_bound over Curve::object_bound)
+    BVHAccel(std::shared_ptr<Context> ctx, const TriangleMesh& mesh, const std::vector<Shape>& shapes, const std::vector<Curve>& curves,
+             int max_prims_in_node = 4, SplitMethod split_method = SplitMethod::SAH)
+        : ctx_(std::move(ctx)) {
+        const size_t nt = (size_t)mesh.n_triangles(), ns = shapes.size(), nc = curves.size(), n = nt + ns + nc;
+        std::vector<float> lo(3 * n), hi(3 * n), box(6 * (ns + nc));
+        std::vector<PbrtShape> records(ns);
+        std::vector<PbrtCurve> curve_records(nc);
+        for (size_t t = 0; t < nt; ++t)
+            for (int k = 0; k < 3; ++k) {
+                const float a = mesh.p[3 * (size_t)mesh.vertex_indices[3 * t] + k], b = mesh.p[3 * (size_t)mesh.vertex_indices[3 * t + 1] + k],
+                            c = mesh.p[3 * (size_t)mesh.vertex_indices[3 * t + 2] + k];
+                lo[3 * t + k] = std::fmin(a, std::fmin(b, c)), hi[3 * t + k] = std::fmax(a, std::fmax(b, c));
+            }
+        for (size_t i = 0; i < ns; ++i) records[i] = shapes[i].record;
+        for (size_t i = 0; i < nc; ++i) curve_records[i] = curves[i].record;
+        int rc = pbrt_hip_shape_world_bounds(records.data(), (int32_t)ns, box.data());
+        if (rc != PBRT_HIP_OK) throw Error("BVHAccel::new: pbrt_hip_shape_world_bounds failed", rc);
+        rc = pbrt_hip_curve_world_bounds(curve_records.data(), (int32_t)nc, box.data() + 6 * ns);
+        if (rc != PBRT_HIP_OK) throw Error("BVHAccel::new: pbrt_hip_curve_world_bounds failed", rc);
+        for (size_t i = 0; i < ns + nc; ++i)
+            for (int k = 0; k < 3; ++k) lo[3 * (nt + i) + k] = box[6 * i + k], hi[3 * (nt + i) + k] = box[6 * i + 3 + k];
+        PbrtLinearBVHNode* nodes = nullptr;
+        int32_t n_nodes = 0, *order = nullptr;
+        rc = pbrt_hip_bvh_build_boxes(lo.data(), hi.data(), (int32_t)n, max_prims_in_node, (int)split_method, &nodes, &n_nodes, &order);
+        if (rc != PBRT_HIP_OK) throw Error("BVHAccel::new: pbrt_hip_bvh_build_boxes failed", rc);
+        for (int k = 0; k < 3; ++k) (&bound_.min.x)[k] = nodes[0].bounds_min[k], (&bound_.max.x)[k] = nodes[0].bounds_max[k];
+        n_nodes_ = n_nodes;
+        rc = pbrt_hip_scene_create_with_curves(ctx_->handle(), mesh.p.data(), mesh.n_vertices(), mesh.vertex_indices.data(), mesh.n_triangles(),
+                                               mesh.material.data(), mesh.materials.data(), (int32_t)mesh.materials.size(), mesh.area_light.data(),
+                                               mesh.lights.data(), (int32_t)mesh.lights.size(), records.data(), (int32_t)ns, curve_records.data(),
+                                               (int32_t)nc, nodes, n_nodes, order, &h_);
+        pbrt_hip_free(nodes), pbrt_hip_free(order);
+        ctx_->check(rc, "BVHAccel::new: pbrt_hip_scene_create_with_curves");
     }
     // The top-level aggregate of a scene of TransformedPrimitives (primitive.rs:105-159): BVHAccel::new over the object's
     // triangles (object space), TransformedPrimitive::new(object, to_world) per instance, BVHAccel::new over their world bounds.

@@ -16,6 +16,12 @@
 #include <stdint.h>
 
 #define PB_DEV __device__ __forceinline__
+// The kernels that are no templates are defined in the wavefront headers and so belong to the one translation unit that includes
+// them, render.hip. A second unit that needs the headers for its own instantiations (curve_kernels.hip) defines this as
+// `static __global__` before it includes them: its copies are then local, unused and dropped, and nothing is defined twice.
+#ifndef PB_PLAIN_KERNEL
+#define PB_PLAIN_KERNEL __global__
+#endif
 
 namespace pb {
 

@@ -640,4 +640,49 @@ extern "C" int pbrt_hip_shape_world_bounds(const PbrtShape* shapes, int32_t n, f
 }
 PB_ABI_CATCH
 
+// Shape::world_bound of a curve segment: Curve::object_bound (curve.rs:285-294) — the box of the segment's four control points
+// (blossoms of the whole curve's at u_min / u_max, curve.rs:121-128), expanded by half the larger of the two end widths —
+// through object_to_world
+extern "C" int pbrt_hip_curve_world_bounds(const PbrtCurve* curves, int32_t n, float* bounds) try {
+    if (n < 0 || (n > 0 && (!curves || !bounds))) return PBRT_HIP_ERR_INVALID;
+    for (int32_t i = 0; i < n; ++i) {
+        const PbrtCurve& c = curves[i];
+        if (c.type < PBRT_CURVE_FLAT || c.type > PBRT_CURVE_RIBBON) return PBRT_HIP_ERR_INVALID;
+        auto lerp = [](float t, float a, float b) { return (1.0f - t) * a + t * b; };
+        const float us[4][3] = {{c.u_min, c.u_min, c.u_min}, {c.u_min, c.u_min, c.u_max}, {c.u_min, c.u_max, c.u_max}, {c.u_max, c.u_max, c.u_max}};
+        float omin[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, omax[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+        for (int p = 0; p < 4; ++p)
+            for (int k = 0; k < 3; ++k) {
+                const float a0 = lerp(us[p][0], c.cp[0][k], c.cp[1][k]), a1 = lerp(us[p][0], c.cp[1][k], c.cp[2][k]),
+                            a2 = lerp(us[p][0], c.cp[2][k], c.cp[3][k]);
+                const float b0 = lerp(us[p][1], a0, a1), b1 = lerp(us[p][1], a1, a2);
+                const float v = lerp(us[p][2], b0, b1);
+                omin[k] = v < omin[k] ? v : omin[k];
+                omax[k] = v > omax[k] ? v : omax[k];
+            }
+        const float wa = lerp(c.u_min, c.width0, c.width1), wb = lerp(c.u_max, c.width0, c.width1);
+        const float grow = (wa > wb ? wa : wb) * 0.5f;
+        for (int k = 0; k < 3; ++k) {
+            omin[k] -= grow;
+            omax[k] += grow;
+        }
+        const float* m = c.to_world;
+        float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
+        for (int corner = 0; corner < 8; ++corner) {
+            float x = (corner & 1) ? omax[0] : omin[0];
+            float y = (corner & 2) ? omax[1] : omin[1];
+            float z = (corner & 4) ? omax[2] : omin[2];
+            for (int k = 0; k < 3; ++k) {
+                float p = m[4 * k] * x + m[4 * k + 1] * y + m[4 * k + 2] * z + m[4 * k + 3];
+                mn[k] = p < mn[k] ? p : mn[k];
+                mx[k] = p > mx[k] ? p : mx[k];
+            }
+        }
+        std::memcpy(bounds + 6 * (size_t)i, mn, 12);
+        std::memcpy(bounds + 6 * (size_t)i + 3, mx, 12);
+    }
+    return PBRT_HIP_OK;
+}
+PB_ABI_CATCH
+
 extern "C" void pbrt_hip_free(void* p) { std::free(p); }

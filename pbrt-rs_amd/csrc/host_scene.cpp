@@ -238,6 +238,71 @@ static DevShape shape_row(const PbrtShape& sh) {
     return d;
 }
 
+// ---- PbrtCurve (curve.rs:29-80: CurveCommon::new, Curve::new) ----
+static const char* curve_invalid(const PbrtCurve& c, int32_t n_materials) {
+    if (c.type < PBRT_CURVE_FLAT || c.type > PBRT_CURVE_RIBBON) return "unknown curve type";
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(c.cp[k / 3][k % 3])) return "curve control points must be finite";
+    if (!(c.width0 >= 0.0f) || !(c.width1 >= 0.0f) || !std::isfinite(c.width0) || !std::isfinite(c.width1))
+        return "curve widths must be finite and not negative";
+    if (c.width0 == 0.0f && c.width1 == 0.0f) return "curve widths must not both be zero";
+    if (!(c.u_min >= 0.0f && c.u_max <= 1.0f && c.u_min < c.u_max)) return "curve u range must satisfy 0 <= u_min < u_max <= 1";
+    if (c.type == PBRT_CURVE_RIBBON) {
+        double l0 = 0.0, l1 = 0.0, d = 0.0, cr[3];
+        for (int k = 0; k < 3; ++k) {
+            if (!std::isfinite(c.n0[k]) || !std::isfinite(c.n1[k])) return "ribbon normals must be finite";
+            l0 += (double)c.n0[k] * c.n0[k];
+            l1 += (double)c.n1[k] * c.n1[k];
+            d += (double)c.n0[k] * c.n1[k];
+        }
+        if (l0 == 0.0 || l1 == 0.0) return "ribbon normals must not be zero";
+        for (int k = 0; k < 3; ++k) cr[k] = (double)c.n0[(k + 1) % 3] * c.n1[(k + 2) % 3] - (double)c.n0[(k + 2) % 3] * c.n1[(k + 1) % 3];
+        if (d < 0.0 && cr[0] == 0.0 && cr[1] == 0.0 && cr[2] == 0.0) return "ribbon normals must not be opposite (n0 == -n1)";
+    }
+    for (int k = 0; k < 12; ++k)
+        if (!std::isfinite(c.to_world[k]) || !std::isfinite(c.to_object[k])) return "curve transforms must be finite";
+    if (c.to_world[12] != 0.0f || c.to_world[13] != 0.0f || c.to_world[14] != 0.0f || c.to_world[15] != 1.0f ||
+        c.to_object[12] != 0.0f || c.to_object[13] != 0.0f || c.to_object[14] != 0.0f || c.to_object[15] != 1.0f)
+        return "curve transforms must be affine (last row 0 0 0 1)";
+    if (c.material < 0 || c.material >= n_materials) return "curve material out of range";
+    return nullptr;
+}
+static DevCurve curve_row(const PbrtCurve& c) {
+    DevCurve d;
+    std::memcpy(d.w2o, c.to_object, 48);
+    std::memcpy(d.o2w, c.to_world, 48);
+    std::memcpy(d.cp, c.cp, 48);
+    d.width0 = c.width0;
+    d.width1 = c.width1;
+    d.u_min = c.u_min;
+    d.u_max = c.u_max;
+    for (int k = 0; k < 3; ++k) d.n0[k] = d.n1[k] = 0.0f;
+    d.normal_angle = d.inv_sin_normal_angle = 0.0f;
+    if (c.type == PBRT_CURVE_RIBBON) {
+        // CurveCommon::new after pbrt-v3: the normals normalised, normal_angle = acos(clamp(n0 . n1, 0, 1)) (D103)
+        double l0 = 0.0, l1 = 0.0, dt = 0.0;
+        for (int k = 0; k < 3; ++k) {
+            l0 += (double)c.n0[k] * c.n0[k];
+            l1 += (double)c.n1[k] * c.n1[k];
+        }
+        for (int k = 0; k < 3; ++k) {
+            d.n0[k] = (float)(c.n0[k] / std::sqrt(l0));
+            d.n1[k] = (float)(c.n1[k] / std::sqrt(l1));
+            dt += (double)d.n0[k] * d.n1[k];
+        }
+        const double angle = std::acos(dt < 0.0 ? 0.0 : (dt > 1.0 ? 1.0 : dt));
+        const bool same = d.n0[0] == d.n1[0] && d.n0[1] == d.n1[1] && d.n0[2] == d.n1[2];
+        if (!same && (float)angle != 0.0f) {
+            d.normal_angle = (float)angle;
+            d.inv_sin_normal_angle = (float)(1.0 / std::sin(angle));
+        }
+    }
+    const float* m = c.to_world;
+    const float det = m[0] * (m[5] * m[10] - m[6] * m[9]) - m[1] * (m[4] * m[10] - m[6] * m[8]) + m[2] * (m[4] * m[9] - m[5] * m[8]);
+    d.flags = c.type | (((c.reverse_orientation != 0) != (det < 0.0f)) ? kCurveFlipNormal : 0);
+    return d;
+}
+
 static bool is_permutation(const int32_t* order, int32_t n) {  // of entries already known to lie in [0, n)
     std::vector<char> seen(n, 0);
     for (int32_t i = 0; i < n; ++i) {
@@ -334,6 +399,10 @@ std::string scene_invalid(const SceneDesc& desc) {
     for (int32_t i = 0; i < sa.n_shapes; ++i) {
         if (const char* why = shape_invalid(sa.shapes[i], n_materials, n_lights)) return why;
     }
+    if (desc.n_curves < 0 || (desc.n_curves > 0 && (!desc.curves || sa.n > 0 || dt || ia.n_instances > 0))) return "bad curve arguments";
+    for (int32_t i = 0; i < desc.n_curves; ++i) {
+        if (const char* why = curve_invalid(desc.curves[i], n_materials)) return why;
+    }
     for (int32_t i = 0; i < n_prims && !dt; ++i)
         if (desc.prim_order[i] < 0 || desc.prim_order[i] >= n_prims) return "prim_order entry out of range";
     for (int32_t i = 0; i < n_tris; ++i) {
@@ -357,6 +426,8 @@ std::string scene_invalid(const SceneDesc& desc) {
         if (lights[i].type == PBRT_LIGHT_DIFFUSE_AREA &&
             (lights[i].prim < 0 || lights[i].prim >= (ia.n_instances > 0 ? ia.n_world_tris : n_prims)))
             return "area light primitive out of range";
+        if (lights[i].type == PBRT_LIGHT_DIFFUSE_AREA && desc.n_curves > 0 && lights[i].prim >= n_prims - desc.n_curves)
+            return "a curve cannot carry an area light (Curve::sample is unimplemented)";
     }
     // ---- the tree(s): single level, one tree over the primitives; two levels (instancing), the top-level tree over the
     // instances and the world-space triangles, then the object-level trees over the triangles ----
@@ -383,6 +454,14 @@ static void plan_prim_records(const SceneDesc& desc, ScenePlan* plan) {
     for (int32_t slot = 0; slot < n_prims; ++slot) {
         int32_t prim = desc.prim_order[slot];
         plan->prim_slot[prim] = slot;
+        if (prim >= n_tris + sa.n_shapes && desc.n_curves > 0) {  // curve record: - | - | (~row of DevSceneData::curves, prim, material, kPrimSphere)
+            const int32_t row = prim - n_tris - sa.n_shapes;
+            float* t = &tris[(size_t)slot * 12];
+            for (int k = 0; k < 8; ++k) t[k] = 0.0f;
+            int32_t meta[4] = {~row, prim, desc.curves[row].material, kPrimSphere};
+            std::memcpy(t + 8, meta, 16);
+            continue;
+        }
         if (prim >= n_tris && sa.n_shapes > 0) {  // shape record: - | - | (row of DevBVH::shapes, prim, material, kPrimSphere)
             const PbrtShape& sh = sa.shapes[prim - n_tris];
             float* t = &tris[(size_t)slot * 12];
@@ -637,7 +716,11 @@ void plan_scene(const SceneDesc& desc, ScenePlan* plan) {
     d.bvh.root_ref = top.root_ref;
     d.bvh.count_bits = top.count_bits;
     d.bvh.n_slots = desc.n_prims();
-    d.bvh.has_spheres = desc.sa.n_shapes > 0 ? 2 : (desc.sa.n > 0 ? 1 : 0);
+    // (a scene with curves is a scene with shapes, whether it holds a quadric or not: its builds are theirs with the curve added)
+    d.bvh.has_spheres = (desc.sa.n_shapes > 0 || desc.n_curves > 0) ? 2 : (desc.sa.n > 0 ? 1 : 0);
+    plan->curves.resize(desc.n_curves);
+    for (int32_t i = 0; i < desc.n_curves; ++i) plan->curves[i] = curve_row(desc.curves[i]);
+    d.n_curves = desc.n_curves;
     plan->shapes.resize(desc.sa.n_shapes);
     for (int32_t i = 0; i < desc.sa.n_shapes; ++i) plan->shapes[i] = shape_row(desc.sa.shapes[i]);
     d.bvh.instanced = desc.instanced() ? 1 : 0;

@@ -61,8 +61,11 @@ struct SceneDesc {
     // prim_order are unused. dt is null while the checks run before the build and names the built tree afterwards.
     bool device_tree = false;
     DeviceTree* dt = nullptr;
+    // curve segments behind the shapes (pbrt_hip_scene_create_with_curves): primitive ids n_tris + n_shapes .. + n_curves - 1
+    const PbrtCurve* curves = nullptr;
+    int32_t n_curves = 0;
 
-    int32_t n_prims() const { return n_tris + sa.n + sa.n_shapes; }
+    int32_t n_prims() const { return n_tris + sa.n + sa.n_shapes + n_curves; }
     bool instanced() const { return ia.n_instances > 0; }
     int32_t n_top() const { return ia.n_instances + ia.n_world_tris; }  // primitives of the top-level aggregate
 };
@@ -99,6 +102,7 @@ struct ScenePlan {
     std::vector<float> tris;         // 48-B triangle / sphere / shape records in leaf order
     std::vector<int32_t> prim_slot;  // primitive -> leaf slot
     std::vector<DevShape> shapes;    // theta_min / theta_max are k_shape_angles'
+    std::vector<DevCurve> curves;    // one row per curve record
     std::vector<DevLight> lights;    // max(1, n_lights) rows
     std::vector<int> infinite_ids;
     std::vector<DevMaterial> materials;

@@ -17,7 +17,8 @@ namespace pb {
 // ---- traversal ----
 // Moving: a two-level scene with moving instances (trace_persistent's MOV builds over the binary records; never wide —
 // the scene carries no wide records — and never stackless, which refuses every two-level scene)
-enum class TraceKind { Stackless, Wide, Shapes, Spheres, Binary, Moving };
+// Curves: a one-level scene with curve segments (trace_persistent's CRV builds: the shapes' with the curve test beside them)
+enum class TraceKind { Stackless, Wide, Shapes, Spheres, Binary, Moving, Curves };
 struct TraceChoice {
     TraceKind kind;
     int inst;    // trace_persistent.h: INST (0 single level, 1 instances of one aggregate, 2 general top level)
@@ -36,6 +37,7 @@ inline TraceChoice choose_trace(const PbrtHipScene* s) {
         c.count = ctx->count_traversal == 2;
     } else if (s->d.bvh.has_spheres) {  // single-level scenes only (checked at creation); 2: general quadric shapes
         c.kind = s->d.bvh.has_spheres == 2 ? TraceKind::Shapes : TraceKind::Spheres;
+        if (s->d.curves) c.kind = TraceKind::Curves;  // has_spheres == 2 there, with or without shapes
     } else if (s->moving) {
         c.kind = TraceKind::Moving;
     }
@@ -92,6 +94,7 @@ inline void dispatch(const TraceChoice& c, F&& f) {
             else
                 with_count(TraceKindC<TraceKind::Moving>{}, std::integral_constant<int, 1>{});
             break;
+        case TraceKind::Curves: with_count(TraceKindC<TraceKind::Curves>{}, std::integral_constant<int, 0>{}); break;
     }
 }
 
@@ -106,16 +109,21 @@ struct SceneNeeds {
     bool lobes;       // a row of pbrt_hip_scene_set_lobe_material: the lobe-list builds (never with shapes or light_maps: the setter refuses)
     bool moving;      // moving instances: the builds that interpolate the instance at the path's time (never with shapes, light_maps
                       // or lobes: creation and the setters refuse)
+    bool curves;      // curve segments (DevSceneData::curves): the builds that rebuild a curve's surface from the ray (with shapes set:
+                      // they are the builds for shapes with that added)
     int column() const { return shapes ? 0 : light_maps ? 1 : 5 - level; }  // of the tables below: in that precedence, most general first
 };
 inline SceneNeeds scene_needs(const PbrtHipScene* s) {
-    return SceneNeeds{s->d.bvh.has_spheres == 2, s->light_maps, s->disney ? 3 : s->bxdfs ? 2 : s->glossy ? 1 : 0, s->lobes, s->moving};
+    return SceneNeeds{s->d.bvh.has_spheres == 2, s->light_maps, s->disney ? 3 : s->bxdfs ? 2 : s->glossy ? 1 : 0, s->lobes, s->moving, s->d.curves != nullptr};
 }
 
 #ifdef PB_SELECT_SHADING_KERNELS
 using DirectKernel = void (*)(ShadeConsts, PathState, DirectState, Queues, Queues, PassParams, TileList, uint32_t);
 using PathKernel = void (*)(ShadeConsts, PathState, Queues, Queues, PassParams, TileList, uint32_t, const uint32_t*);
 using SpatialKernel = void (*)(ShadeConsts, float*);
+}  // namespace pb
+#include "curve_kernels.h"
+namespace pb {
 // The tables list every instantiation the library holds, once. Their initialisers are also where the compiler first meets each
 // instantiation, and the code it generates for some of the kernels depends on that order (profiles/r11_render_driver.txt): the
 // rows and columns below keep the order the kernels have always been named in.
@@ -126,6 +134,12 @@ inline PathKernel lobe_path_kernel(bool bin);
 // ... and behind them those of the builds for moving instances
 inline DirectKernel moving_direct_kernel(int integrator);
 inline PathKernel moving_path_kernel(bool bin);
+// ... and the builds for curves — k_shade_direct<MODE, 3 + kDirectCurves>, the AO build, k_shade_curves<BIN> and k_trace_curves<COUNT> —
+// are instantiated in a translation unit of their own (curve_kernels.hip). That goes one step further than a table at the end of
+// this file: the unit that holds every older kernel meets none of them, so it compiles, and its code object is laid out, as before
+// curves existed (profiles/curve_resource_usage.txt, profiles/curve_bench.txt). (The SpatialLightDistribution tables sample lights
+// only, and a curve carries none: the build for shapes serves.)
+// curve_direct_kernel, curve_path_kernel, launch_trace_curves: curve_kernels.h
 
 // the build of the SpatialLightDistribution tables (wf_lights.h)
 inline SpatialKernel spatial_tables_kernel(const SceneNeeds& n) {
@@ -143,6 +157,7 @@ inline DirectKernel direct_kernel(const SceneNeeds& n, int integrator) {
                                                {k_shade_direct<D, 1>, k_shade_direct<W, 1>},
                                                {k_shade_direct<D, 0>, k_shade_direct<W, 0>}};
     static constexpr DirectKernel ao[2] = {k_shade_direct<AO, kDirectShapes>, k_shade_direct<AO, 0>};
+    if (n.curves) return curve_direct_kernel(integrator);
     if (n.moving) return moving_direct_kernel(integrator);
     if (n.lobes && (integrator == D || integrator == W)) return lobe_direct_kernel(integrator == W);
     if (integrator == D || integrator == W) return lit[n.column()][integrator == W];
@@ -154,6 +169,7 @@ inline PathKernel path_kernel(const SceneNeeds& n, bool bin) {
     static constexpr PathKernel table[2][6] = {
         {k_shade_shapes<true>, k_shade_maps<true>, k_shade<true, 3>, k_shade<true, 2>, k_shade<true, 1>, k_shade<true, 0>},
         {k_shade_shapes<false>, k_shade_maps<false>, k_shade<false, 3>, k_shade<false, 2>, k_shade<false, 1>, k_shade<false, 0>}};
+    if (n.curves) return curve_path_kernel(bin);
     if (n.moving) return moving_path_kernel(bin);
     if (n.lobes) return lobe_path_kernel(bin);
     return table[bin ? 0 : 1][n.column()];
@@ -198,6 +214,7 @@ inline GenerateCameraKernel generate_camera_kernel(int key) {
     static constexpr GenerateCameraKernel table[2] = {k_generate_moving_camera, k_generate_moving_camera};
     return table[key & 1];
 }
+
 #endif  // PB_SELECT_SHADING_KERNELS
 
 }  // namespace pb

@@ -307,6 +307,7 @@ static void upload_tables(PbrtHipScene* s, const SceneDesc& desc, ScenePlan& pla
         }
         d.bvh.shapes = d_rows;
     }
+    if (!plan.curves.empty()) d.curves = dev_upload(s, plan.curves.data(), plan.curves.size(), ok);
     if (desc.instanced()) {
         d.bvh.objects = (const float4*)dev_upload(s, plan.objects.data(), plan.objects.size(), ok);
         d.bvh.instances = (const float4*)dev_upload(s, plan.top_slot_records.data(), plan.top_slot_records.size(), ok);
@@ -425,6 +426,8 @@ static bool obtain_wide(PbrtHipScene* s, const SceneDesc& desc, const ScenePlan&
     bool ok = true;
     if (ctx->wide_build == PBRT_WIDE_BUILD_NONE) {
         built.reason = "disabled by PBRT_WIDE_BUILD_NONE";
+    } else if (desc.n_curves > 0) {
+        built.reason = "scene with curves";
     } else if (desc.sa.n_shapes > 0) {
         built.reason = "scene with shapes";
     } else if (desc.sa.n > 0) {
@@ -603,6 +606,22 @@ extern "C" int pbrt_hip_scene_create_with_shapes(PbrtHipContext* ctx, const floa
     SceneDesc desc{positions, n_verts, indices, n_tris, tri_material, materials, n_materials, tri_light, lights, n_lights, nodes, n_nodes, prim_order};
     desc.sa.shapes = shapes;
     desc.sa.n_shapes = n_shapes;
+    return create_scene(ctx, desc, out);
+}
+PB_ABI_CATCH
+
+extern "C" int pbrt_hip_scene_create_with_curves(PbrtHipContext* ctx, const float* positions, int32_t n_verts,
+                                                 const int32_t* indices, int32_t n_tris, const int32_t* tri_material,
+                                                 const PbrtMaterial* materials, int32_t n_materials, const int32_t* tri_light,
+                                                 const PbrtLight* lights, int32_t n_lights, const PbrtShape* shapes,
+                                                 int32_t n_shapes, const PbrtCurve* curves, int32_t n_curves,
+                                                 const PbrtLinearBVHNode* nodes, int32_t n_nodes, const int32_t* prim_order,
+                                                 PbrtHipScene** out) try {
+    SceneDesc desc{positions, n_verts, indices, n_tris, tri_material, materials, n_materials, tri_light, lights, n_lights, nodes, n_nodes, prim_order};
+    desc.sa.shapes = shapes;
+    desc.sa.n_shapes = n_shapes;
+    desc.curves = curves;
+    desc.n_curves = n_curves;
     return create_scene(ctx, desc, out);
 }
 PB_ABI_CATCH
@@ -1294,6 +1313,19 @@ __global__ void __launch_bounds__(kTraceBlock, PB_MOVING_WAVES)
                                                                        blockIdx.x * kTraceBlock + threadIdx.x, counters, motions);
 }
 
+// scenes with curves (shapes_curve.h): the build for shapes with the curve test beside the quadrics'. Behind every older kernel, as above.
+#ifndef PB_CURVE_WAVES
+#define PB_CURVE_WAVES 3  // profiles/curve_resource_usage.txt
+#endif
+template <bool ANY, bool COUNT>
+__global__ void __launch_bounds__(kTraceBlock, PB_CURVE_WAVES)
+    k_intersect_batch_curves(DevBVH bvh, const DevCurve* __restrict__ curves, BatchRayIO<ANY> io, unsigned int* work_counter,
+                             unsigned long long* counters) {
+    __shared__ uint2 lds_stack[kStackLds * kTraceBlock];
+    trace_persistent<BatchRayIO<ANY>, COUNT, 0, false, true, false, true>(bvh, io, work_counter, lds_stack + threadIdx.x,
+                                                                          blockIdx.x * kTraceBlock + threadIdx.x, counters, nullptr, curves);
+}
+
 template <bool ANY>
 static int launch_batch(PbrtHipScene* s, const PbrtRay* d_rays, int64_t n, PbrtHit* d_hits, uint8_t* d_flags) {
     PbrtHipContext* ctx = s->ctx;
@@ -1336,6 +1368,9 @@ static int launch_batch(PbrtHipScene* s, const PbrtRay* d_rays, int64_t n, PbrtH
         } else if constexpr (K == TraceKind::Moving) {
             hipLaunchKernelGGL((k_intersect_batch_moving<ANY, COUNT, INST>), dim3(persistent_grid(s, PB_MOVING_WAVES)), block, 0, ctx->stream,
                                s->d.bvh, s->d_motions, io, ctx->d_work_counter, ctx->d_counters);
+        } else if constexpr (K == TraceKind::Curves) {
+            hipLaunchKernelGGL((k_intersect_batch_curves<ANY, COUNT>), dim3(persistent_grid(s, PB_CURVE_WAVES)), block, 0, ctx->stream, s->d.bvh,
+                               s->d.curves, io, ctx->d_work_counter, ctx->d_counters);
         } else {
             hipLaunchKernelGGL((k_intersect_batch<ANY, COUNT, INST, K == TraceKind::Spheres>), grid, block, 0, ctx->stream, s->d.bvh, io,
                                ctx->d_work_counter, ctx->d_counters);

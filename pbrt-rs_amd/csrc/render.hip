@@ -434,6 +434,7 @@ static void scene_shade_consts(const PbrtHipScene* s, ShadeConsts* out) {
     sc.light_maps = s->d.light_maps;
     sc.lobe_rows = s->d.lobe_rows;
     sc.motions = s->d_motions;
+    if (s->d.curves) sc.curves = s->d.curves;  // the same slot: a scene with curves has one level and no motions (wf_surface.h)
 }
 
 // Light::sample_li (light.rs:35-42) of one light of the scene from bare interactions at the world points p (normal and error
@@ -1328,6 +1329,9 @@ void RenderJob::trace_wavefront(const RenderEvents& ev, const Queues& qcur, uint
         } else if constexpr (K == TraceKind::Moving) {
             hipLaunchKernelGGL((k_trace_moving<COUNT, INST>), dim3(persistent_grid(s, PB_MOVING_TRACE_WAVES)), block, 0, st, s->d.bvh, s->d_motions, ps,
                                trace_queue, n_trace, ctx->d_work_counter, ctx->d_counters, segments);
+        } else if constexpr (K == TraceKind::Curves) {
+            launch_trace_curves(COUNT, dim3(persistent_grid(s, PB_CURVE_TRACE_WAVES)), st, s->d.bvh, s->d.curves, ps, trace_queue, n_trace,
+                                ctx->d_work_counter, ctx->d_counters, segments);
         } else {
             hipLaunchKernelGGL((k_trace<COUNT, INST, K == TraceKind::Spheres>), grid, block, 0, st, s->d.bvh, ps, trace_queue, n_trace,
                                ctx->d_work_counter, ctx->d_counters, segments);

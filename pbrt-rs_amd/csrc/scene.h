@@ -195,6 +195,8 @@ struct DevSceneData {
     const DevDisney* disney;    // [n_materials]: the blocks of the kMatDisney rows
     const DevLightMap* light_maps;  // [n_lights] when the scene holds a projection or goniometric light, else null
     const DevLobeRow* lobe_rows;    // [n_materials]: the lists of the kMatLobes rows
+    const DevCurve* curves;         // [n_curves]: the rows of the curve segments (shapes_curve.h), null in a scene without curves
+    int n_curves;
 };
 
 }  // namespace pb

@@ -367,3 +367,4 @@ PB_DEV void count_flush(unsigned long long* counters, uint32_t n_node, uint32_t 
 }  // namespace pb
 
 #include "shapes_quadric.h"
+#include "shapes_curve.h"

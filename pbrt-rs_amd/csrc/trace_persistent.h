@@ -18,6 +18,8 @@
 // SPH = true: leaf slots may hold spheres (kPrimSphere; BASELINE config 1).
 // SHP = true: leaf slots may hold general quadric shapes (kPrimSphere in a scene whose DevBVH::has_spheres is 2: a row of
 // DevBVH::shapes, shapes_quadric.h); never together with SPH.
+// CRV = true (with SHP): leaf slots may also hold curve segments (a kPrimSphere slot whose row is negative: row ~j of `curves`,
+// shapes_curve.h); a curve's hit record carries (u, v, 0).
 // COUNT = true is the instrumented variant: it also counts the box tests (bvh.rs:841-842),
 // triangle tests (triangle.rs:74) and instance entries (primitive.rs:136) that the REFERENCE's
 // loops perform for the same rays. The reference pushes the far child untested and tests it when
@@ -111,11 +113,12 @@ PB_DEV bool root_box_test(const LaneState& s, const float* mn, const float* mx) 
 // MOV = true (INST only): the scene has moving instances. `motions` holds one DevMotion per top-level leaf slot, IO::load
 // hands over the ray's time, and a slot whose row is animated is entered through the rows AnimatedTransform::interpolate
 // gives at that time (motion.h) instead of the slot's own; every other slot runs the code and the rows of the static build.
-template <class IO, bool COUNT, int INST, bool SPH = false, bool SHP = false, bool MOV = false>
+template <class IO, bool COUNT, int INST, bool SPH = false, bool SHP = false, bool MOV = false, bool CRV = false>
 PB_DEV void trace_persistent(const DevBVH& bvh, const IO& io, unsigned int* __restrict__ work_counter,
                              uint2* lds_stack, int spill_lane, unsigned long long* counters,
-                             const DevMotion* __restrict__ motions = nullptr) {
+                             const DevMotion* __restrict__ motions = nullptr, const DevCurve* __restrict__ curves = nullptr) {
     static_assert(!MOV || INST != 0, "moving instances need a two-level scene");
+    static_assert(!CRV || (SHP && INST == 0), "curves live in one-level scenes, beside the general shapes");
     const uint32_t n = io.n();
     const int lane = threadIdx.x & 63;
     const int count_mask = (1 << bvh.count_bits) - 1;
@@ -469,6 +472,14 @@ PB_DEV void trace_persistent(const DevBVH& bvh, const IO& io, unsigned int* __re
                         b0 = ph.x;  // a sphere's hit record carries the refined object-space hit point
                         b1 = ph.y;
                         b2 = ph.z;
+                    } else if (CRV && (flags & kPrimSphere) && __float_as_int(p2.z) < 0) {
+                        // Curve::intersect / intersect_p (shapes_curve.h)
+                        CurveHit ch;
+                        hit = curve_test(curves[~__float_as_int(p2.z)], s.r, s.tmax, s.any, &ch, nullptr);
+                        t = ch.t;
+                        b0 = ch.u;
+                        b1 = ch.v;
+                        b2 = 0.0f;
                     } else if (SHP && (flags & kPrimSphere)) {
                         // Sphere / Disk / Cylinder::intersect_test under the shape's own transform (shapes_quadric.h)
                         V3 ph;

@@ -8,7 +8,7 @@ namespace pb {
 // generated for some of the older kernels depends on the order in which the instantiations are met.
 // One build serves static and moving scenes alike: it always writes the ray's time, which the static scenes' kernels never read.
 // The camera's DevMotion row (host_motion.cpp: camera_motion_row) rides in the arguments.
-__global__ void k_generate_moving_camera(PathState ps, Queues q, PassParams pp, DevCamera cam, DevMotion cmo, TileList tiles) {
+PB_PLAIN_KERNEL void k_generate_moving_camera(PathState ps, Queues q, PassParams pp, DevCamera cam, DevMotion cmo, TileList tiles) {
     generate_camera_rays<true, true>(ps, q, pp, cam, tiles, &cmo);
 }
 

@@ -38,12 +38,15 @@ struct DirectState {
 // Both run one wave per SIMD: at two the Whitted build spills 104 bytes (profiles/r12_lobe_materials.txt).
 // + 32 in the builds for scenes with moving instances (MOV as shade_bounce's): <DIRECT, 35>, <WHITTED, 35> and <AO, 32>. The path's
 // time is read from its continuation ray at entry and written back to it, and to every ray the launch emitted, at the end.
-constexpr int kDirectShapes = 4, kDirectMapLights = 8, kDirectLobes = 16, kDirectMoving = 32;
+// + 64 in the builds for scenes with curve segments (CRV as shade_bounce's; they are the builds for shapes with the curve's surface
+// added): <DIRECT, 67>, <WHITTED, 67> and <AO, 64>, one wave per SIMD (profiles/curve_resource_usage.txt).
+constexpr int kDirectShapes = 4, kDirectMapLights = 8, kDirectLobes = 16, kDirectMoving = 32, kDirectCurves = 64;
 template <int MODE, int LEVEL_SHP>
-__global__ void __launch_bounds__(256, (((LEVEL_SHP & 3) >= 1 && MODE == PBRT_INTEGRATOR_DIRECT) || (LEVEL_SHP & (16 | 32))) ? 1 : PB_DIRECT_WAVES) k_shade_direct(ShadeConsts sc, PathState ps, DirectState ds, Queues qin,
+__global__ void __launch_bounds__(256, (((LEVEL_SHP & 3) >= 1 && MODE == PBRT_INTEGRATOR_DIRECT) || (LEVEL_SHP & (16 | 32 | 64))) ? 1 : PB_DIRECT_WAVES) k_shade_direct(ShadeConsts sc, PathState ps, DirectState ds, Queues qin,
                                                         Queues qout, PassParams pp, TileList tiles, uint32_t n_in) {
     constexpr int LEVEL = LEVEL_SHP & 3;
-    constexpr bool SHP = (LEVEL_SHP & kDirectShapes) != 0;
+    constexpr bool CRV = (LEVEL_SHP & kDirectCurves) != 0;
+    constexpr bool SHP = CRV || (LEVEL_SHP & kDirectShapes) != 0;
     constexpr bool ML = SHP || (LEVEL_SHP & kDirectMapLights) != 0;
     constexpr bool LOBES = (LEVEL_SHP & kDirectLobes) != 0;
     constexpr bool MOV = (LEVEL_SHP & kDirectMoving) != 0;
@@ -129,7 +132,9 @@ __global__ void __launch_bounds__(256, (((LEVEL_SHP & 3) >= 1 && MODE == PBRT_IN
             rd = V3{r0.w, r1.x, r1.y};
             float4 h0 = ps.hit[hbase];
             int hslot = __float_as_int(h0.x);
-            if constexpr (MOV)
+            if constexpr (CRV)
+                sf = surface_from_hit_curves(sc.bvh, sc.curves, hslot, h0.y, h0.z, h0.w, V3{r0.x, r0.y, r0.z}, rd);
+            else if constexpr (MOV)
                 sf = surface_from_hit_moving(sc.bvh, sc.motions, time, hslot, hit_instance(ps, hbase), h0.y, h0.z, h0.w, rd);
             else
                 sf = surface_from_hit<SHP>(sc.bvh, hslot, hit_instance(ps, hbase), h0.y, h0.z, h0.w, rd);

@@ -12,7 +12,7 @@ PB_DEV V3 clamp_sample_luminance(V3 L, float max_lum) {
 }
 
 // ---- film: FilmTile::add_sample (film.rs:252-295) with the 0.5 box filter, samples summed in order ----
-__global__ void k_film_accumulate(PathState ps, PassParams pp, TileList tiles, float4* accum, float* d_film) {
+PB_PLAIN_KERNEL void k_film_accumulate(PathState ps, PassParams pp, TileList tiles, float4* accum, float* d_film) {
     uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= (uint32_t)pp.n_pix) return;
     int tile = pix >> 8, within = pix & 255;
@@ -78,7 +78,7 @@ __global__ void k_film_accumulate(PathState ps, PassParams pp, TileList tiles, f
 // load instruction, as line-efficient as the sample-major layout was for k_film_accumulate); every lane forms its own sample's
 // contribution, then the sixteen are added to the pixel IN SAMPLE ORDER — lane after lane through the row — because float addition
 // is not associative and the reference's loop (and the oracle's) adds them one after the other.
-__global__ void k_film_accumulate_rows(PathState ps, PassParams pp, TileList tiles, float4* accum, float* d_film) {
+PB_PLAIN_KERNEL void k_film_accumulate_rows(PathState ps, PassParams pp, TileList tiles, float4* accum, float* d_film) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t pix = t >> 4, k = t & 15u;
     if (pix >= (uint32_t)pp.n_pix) return;  // (whole rows of sixteen lanes leave together)
@@ -132,7 +132,7 @@ __global__ void k_film_accumulate_rows(PathState ps, PassParams pp, TileList til
 // L * weight * filter and the filter weight to every pixel of its footprint with float atomics (the
 // footprints of neighbouring samples, tiles and GPUs overlap); XYZ conversion is linear, so it is applied
 // per contribution instead of per tile (film.rs:111-123).
-__global__ void k_film_splat(PathState ps, PassParams pp, TileList tiles, float* d_film) {
+PB_PLAIN_KERNEL void k_film_splat(PathState ps, PassParams pp, TileList tiles, float* d_film) {
     uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= (uint32_t)pp.n_pix * pp.n_samples) return;
     if (!(__float_as_int(ps.beta[p].w) & PF_VALID)) return;
@@ -166,7 +166,7 @@ __global__ void k_film_splat(PathState ps, PassParams pp, TileList tiles, float*
 }
 
 // Film::merge_film_tile (film.rs:111-123): contrib_sum -> XYZ, accumulated into the film
-__global__ void k_film_merge(PassParams pp, TileList tiles, const float4* accum, float* d_film) {
+PB_PLAIN_KERNEL void k_film_merge(PassParams pp, TileList tiles, const float4* accum, float* d_film) {
     uint32_t pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= (uint32_t)pp.n_pix) return;
     int tile = pix >> 8, within = pix & 255;

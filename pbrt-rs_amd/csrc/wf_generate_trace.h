@@ -133,14 +133,14 @@ PB_DEV void generate_camera_rays(const PathState& ps, const Queues& q, const Pas
     q.trace[p] = p * 4u + RS_CONT;
     q.shade[p] = p;
 }
-__global__ void k_generate(PathState ps, Queues q, PassParams pp, DevCamera cam, TileList tiles) {
+PB_PLAIN_KERNEL void k_generate(PathState ps, Queues q, PassParams pp, DevCamera cam, TileList tiles) {
     generate_camera_rays<false>(ps, q, pp, cam, tiles);
 }
 
 // ---- pbrt_hip_li: a batch of Integrator::li calls (integrator.rs:29-42). The caller made the rays (its own Camera) and
 // names the random stream of each (its own Sampler's RNG::set_sequence argument, rng.rs:21-35); `skip` values were
 // already drawn from that stream before li (SamplerIntegrator::render draws the 5 of the CameraSample, integrator.rs:430). ----
-__global__ void k_li_generate(PathState ps, Queues q, const PbrtRay* __restrict__ rays, const uint64_t* __restrict__ keys, uint32_t n,
+PB_PLAIN_KERNEL void k_li_generate(PathState ps, Queues q, const PbrtRay* __restrict__ rays, const uint64_t* __restrict__ keys, uint32_t n,
                               uint32_t n_padded, int skip) {
     uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n_padded) return;
@@ -165,7 +165,7 @@ __global__ void k_li_generate(PathState ps, Queues q, const PbrtRay* __restrict_
     q.trace[p] = p * 4u + RS_CONT;
     q.shade[p] = p;
 }
-__global__ void k_li_output(PathState ps, uint32_t n, float* __restrict__ rgb) {
+PB_PLAIN_KERNEL void k_li_output(PathState ps, uint32_t n, float* __restrict__ rgb) {
     uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= n) return;
     float4 L = ps.L[p];  // what li returns; the NaN / negative-luminance guard is render's (integrator.rs:455), not li's
@@ -174,7 +174,7 @@ __global__ void k_li_output(PathState ps, uint32_t n, float* __restrict__ rgb) {
     rgb[3 * (size_t)p + 2] = L.z;
 }
 // pbrt_hip_camera_rays: what k_generate made, in the caller's record types (path order)
-__global__ void k_camera_rays_out(PathState ps, PassParams pp, TileList tiles, PbrtRay* __restrict__ rays, uint64_t* __restrict__ keys,
+PB_PLAIN_KERNEL void k_camera_rays_out(PathState ps, PassParams pp, TileList tiles, PbrtRay* __restrict__ rays, uint64_t* __restrict__ keys,
                                   float* __restrict__ pfilm, int32_t* __restrict__ pixel_sample) {
     uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t n = (uint32_t)pp.n_pix * pp.n_samples;
@@ -275,7 +275,7 @@ __global__ void __launch_bounds__(kTraceBlock, 4)
 }
 
 // the binary records without a stack (trace_stackless.h; PBRT_TRAVERSAL_STACKLESS)
-__global__ void __launch_bounds__(kTraceBlock, PB_STACKLESS_WAVES)
+PB_PLAIN_KERNEL void __launch_bounds__(kTraceBlock, PB_STACKLESS_WAVES)
     k_trace_stackless(DevBVH bvh, PathState ps, const uint32_t* __restrict__ queue, uint32_t n, unsigned int* work_counter, int segments) {
     WavefrontRayIO<false> io{ps, queue, n, segments};
     trace_stackless<WavefrontRayIO<false>>(bvh, io, work_counter);
@@ -310,7 +310,7 @@ __global__ void __launch_bounds__(kTraceBlock, INST ? PB_INST_WAVES : PB_TRACE_W
 
 // ---- scenes with moving instances: named after every older kernel (kernel_select.h: the code generated for some kernels
 // depends on the order in which the instantiations are met) ----
-__global__ void k_generate_moving(PathState ps, Queues q, PassParams pp, DevCamera cam, TileList tiles) {
+PB_PLAIN_KERNEL void k_generate_moving(PathState ps, Queues q, PassParams pp, DevCamera cam, TileList tiles) {
     generate_camera_rays<true>(ps, q, pp, cam, tiles);
 }
 #ifndef PB_MOVING_TRACE_WAVES
@@ -324,6 +324,21 @@ __global__ void __launch_bounds__(kTraceBlock, PB_MOVING_TRACE_WAVES)
     WavefrontRayIO<true> io{ps, queue, n, segments};
     trace_persistent<WavefrontRayIO<true>, COUNT, INST, false, false, true>(bvh, io, work_counter, lds_stack + threadIdx.x,
                                                                             blockIdx.x * kTraceBlock + threadIdx.x, counters, motions);
+}
+
+// ---- scenes with curves (shapes_curve.h; DevSceneData::curves): the build for shapes with the curve test beside the quadrics';
+// named after every older kernel, as above ----
+#ifndef PB_CURVE_TRACE_WAVES
+#define PB_CURVE_TRACE_WAVES 3  // profiles/curve_resource_usage.txt
+#endif
+template <bool COUNT>
+__global__ void __launch_bounds__(kTraceBlock, PB_CURVE_TRACE_WAVES)
+    k_trace_curves(DevBVH bvh, const DevCurve* __restrict__ curves, PathState ps, const uint32_t* __restrict__ queue, uint32_t n,
+                   unsigned int* work_counter, unsigned long long* counters, int segments) {
+    __shared__ uint2 lds_stack[kStackLds * kTraceBlock];
+    WavefrontRayIO<false> io{ps, queue, n, segments};
+    trace_persistent<WavefrontRayIO<false>, COUNT, 0, false, true, false, true>(bvh, io, work_counter, lds_stack + threadIdx.x,
+                                                                                blockIdx.x * kTraceBlock + threadIdx.x, counters, nullptr, curves);
 }
 
 }  // namespace pb

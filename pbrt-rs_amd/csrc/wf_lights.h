@@ -452,10 +452,10 @@ PB_DEV void spatial_light_tables(const ShadeConsts& sc, float* __restrict__ tabl
     }
     func[2 * n + 1] = func_int;
 }
-__global__ void k_spatial_light_tables(ShadeConsts sc, float* __restrict__ table) { spatial_light_tables<false>(sc, table); }
-__global__ void k_spatial_light_tables_shapes(ShadeConsts sc, float* __restrict__ table) { spatial_light_tables<true, true>(sc, table); }
+PB_PLAIN_KERNEL void k_spatial_light_tables(ShadeConsts sc, float* __restrict__ table) { spatial_light_tables<false>(sc, table); }
+PB_PLAIN_KERNEL void k_spatial_light_tables_shapes(ShadeConsts sc, float* __restrict__ table) { spatial_light_tables<true, true>(sc, table); }
 // a scene with a projection or goniometric light
-__global__ void k_spatial_light_tables_maps(ShadeConsts sc, float* __restrict__ table) { spatial_light_tables<false, true>(sc, table); }
+PB_PLAIN_KERNEL void k_spatial_light_tables_maps(ShadeConsts sc, float* __restrict__ table) { spatial_light_tables<false, true>(sc, table); }
 
 // estimate_direct (integrator.rs:136-266), first part: sample the light, evaluate the BSDF, sample the
 // BSDF, evaluate the light pdf. Writes the shadow ray (slot 2), the MIS ray (slot 1) and the pending
@@ -605,6 +605,8 @@ PB_DEV V3 estimate_direct_resolve(const ShadeConsts& sc, const PathState& ps, ui
                 float4 r0 = ps.ray[ray_index(ps, rec, RS_MIS)], r1 = ps.ray[ray_index(ps, rec, RS_MIS) + 1];
                 V3 wi = V3{r0.w, r1.x, r1.y};
                 float4 hb = ps.hit[hit_index(ps, rec, RS_MIS)];
+                // (never a curve's slot, in the curve builds either: a curve carries no area light (creation refuses one), so its
+                // hl is -1 and this branch is not taken. tri_interaction_normal<true> would read a curve's negative row as a shape's.)
                 V3 n = tri_interaction_normal<SHP>(sc.bvh, hslot, hb.y, hb.z, hb.w);
                 if (lt.two_sided || dot(n, -wi) > 0.0f) li = V3{lt.L[0], lt.L[1], lt.L[2]};
             }

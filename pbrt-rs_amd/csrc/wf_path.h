@@ -33,7 +33,7 @@ PB_DEV uint32_t shade_key(const ShadeConsts& sc, const PathState& ps, uint32_t p
     }
     return key;
 }
-__global__ void k_shade_sort_keys(ShadeConsts sc, PathState ps, const uint32_t* __restrict__ shade_queue, uint32_t n, int max_depth,
+PB_PLAIN_KERNEL void k_shade_sort_keys(ShadeConsts sc, PathState ps, const uint32_t* __restrict__ shade_queue, uint32_t n, int max_depth,
                                   uint32_t* __restrict__ keys, uint32_t* __restrict__ positions) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -70,8 +70,9 @@ struct ShadeBins {
 // kernels of every other scene compile as they did without it. ML: it may hold a projection or goniometric light (light_sample_li);
 // k_shade_maps below is that build, and k_shade_shapes takes it too. MOV: it holds moving instances (sc.motions): the surface is
 // rebuilt through the instance's rows at the path's time, which rides in the fourth component of the ray's second float4 and is
-// copied to every ray the path emits (spawn_ray keeps the time); k_shade_moving below is that build.
-template <bool BIN, int LEVEL, bool SHP, bool ML = false, bool MOV = false>
+// copied to every ray the path emits (spawn_ray keeps the time); k_shade_moving below is that build. CRV (with SHP): it holds curve
+// segments (sc.curves): a curve's surface is rebuilt from the continuation ray (make_surface_curve); k_shade_curves below.
+template <bool BIN, int LEVEL, bool SHP, bool ML = false, bool MOV = false, bool CRV = false>
 PB_DEV void shade_bounce(const ShadeConsts& sc, const PathState& ps, const Queues& qin, const Queues& qout, const PassParams& pp,
                          const TileList& tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
     constexpr bool GLOSSY = LEVEL >= 1;
@@ -144,7 +145,9 @@ PB_DEV void shade_bounce(const ShadeConsts& sc, const PathState& ps, const Queue
             Surf sf;
             if (MOV) time = r1.w;
             if (found) {
-                if constexpr (MOV)
+                if constexpr (CRV)
+                    sf = surface_from_hit_curves(sc.bvh, sc.curves, hslot, h0.y, h0.z, h0.w, V3{r0.x, r0.y, r0.z}, rd);
+                else if constexpr (MOV)
                     sf = surface_from_hit_moving(sc.bvh, sc.motions, time, hslot, hit_instance(ps, hbase), h0.y, h0.z, h0.w, rd);
                 else
                     sf = surface_from_hit<SHP>(sc.bvh, hslot, hit_instance(ps, hbase), h0.y, h0.z, h0.w, rd);
@@ -327,6 +330,12 @@ template <bool BIN>
 __global__ void __launch_bounds__(256, 2) k_shade_moving(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
                                                         TileList tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
     shade_bounce<BIN, 3, false, false, true>(sc, ps, qin, qout, pp, tiles, n_in, order);
+}
+// scenes with curve segments: the build for shapes with the curve's surface added (profiles/curve_resource_usage.txt)
+template <bool BIN>
+__global__ void __launch_bounds__(256, 2) k_shade_curves(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
+                                                        TileList tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
+    shade_bounce<BIN, 3, true, true, false, true>(sc, ps, qin, qout, pp, tiles, n_in, order);
 }
 
 }  // namespace pb

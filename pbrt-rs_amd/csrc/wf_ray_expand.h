@@ -18,6 +18,9 @@
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #define PB_XHD __host__ __device__ __forceinline__
+#ifndef PB_PLAIN_KERNEL  // dev_math.h
+#define PB_PLAIN_KERNEL __global__
+#endif
 #else
 #define PB_XHD inline
 #endif
@@ -73,7 +76,7 @@ __device__ __forceinline__ uint32_t expand_counts(uint4 v) {
 }
 
 // block_counts[b] = closest tokens of tile b | any-hit tokens << 32; block_counts[gridDim.x] = 0 (the scan's totals slot)
-__global__ void __launch_bounds__(kExpandBlock) k_ray_expand_count(const uint32_t* __restrict__ entries, uint32_t n,
+PB_PLAIN_KERNEL void __launch_bounds__(kExpandBlock) k_ray_expand_count(const uint32_t* __restrict__ entries, uint32_t n,
                                                                    unsigned long long* __restrict__ block_counts) {
     __shared__ uint32_t wave_sum[kExpandBlock / 64];
     uint32_t s = expand_counts(expand_load(entries, n, blockIdx.x * kExpandTile + threadIdx.x * kExpandItems));
@@ -91,7 +94,7 @@ __global__ void __launch_bounds__(kExpandBlock) k_ray_expand_count(const uint32_
 // block_offsets: the exclusive scan of block_counts over gridDim.x + 1 elements. Tokens are ranked inside the tile (threads in
 // entry order), staged in LDS and copied out in whole lines. n_tokens = the queue's length as the host knows it; the sections
 // add up to it, and nothing is written past it whatever the entries hold.
-__global__ void __launch_bounds__(kExpandBlock) k_ray_expand_scatter(const uint32_t* __restrict__ entries, uint32_t n,
+PB_PLAIN_KERNEL void __launch_bounds__(kExpandBlock) k_ray_expand_scatter(const uint32_t* __restrict__ entries, uint32_t n,
                                                                      const unsigned long long* __restrict__ block_offsets,
                                                                      uint32_t* __restrict__ tokens, uint32_t n_tokens) {
     __shared__ uint32_t wave_sum[kExpandBlock / 64];

@@ -162,7 +162,7 @@ PB_DEV void table_gray_code(const PixelColumn& c, int off, int n_per, int n_pixe
     for (int i = 0; i < n_pixel_samples; ++i) table_shuffle(c, off + i * n_per * width, n_per, 1, width, rng);
     table_shuffle(c, off, n_pixel_samples, n_per, width, rng);
 }
-__global__ void k_sampler_tables(PassParams pp, TileList tiles) {
+PB_PLAIN_KERNEL void k_sampler_tables(PassParams pp, TileList tiles) {
     int pix = blockIdx.x * blockDim.x + threadIdx.x;
     if (pix >= pp.n_pix) return;
     int2 org = tiles.origin[pix >> 8];

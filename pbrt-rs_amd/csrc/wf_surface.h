@@ -332,6 +332,101 @@ PB_DEV Surf surface_from_hit_moving(const DevBVH& bvh, const DevMotion* __restri
     instance_to_world_moving(bvh, o, w, inst_slot, &s);
     return s;
 }
+// Curve::intersect past the hit test (curve.rs:243-276) for row `row` of the curve table. A curve's hit record carries (u, v, 0)
+// and no t, so the surface is rebuilt from the ray: the hit test runs again on this one curve with an unbounded ray and gives
+// the hit the traversal kernel recorded (the nearest inside the curve: a t_max only ever prunes it), and with it t, hit_width
+// and the ray's frame. p = ray(t) with p_error = 2 hit_width on each axis, dpdu from the whole curve at u, dpdv across the
+// ray (flat), rotated about dpdu by lerp(v, -90, 90) degrees (cylinder) or n_hit x dpdu (ribbon); n = normalize(dpdu x dpdv),
+// flipped by reverse_orientation ^ swaps_handedness; shading geometry = geometric. Then Transform(SurfaceInteraction) through
+// the curve's matrices as make_surface_shape does it.
+PB_DEV Surf make_surface_curve(const DevBVH& bvh, const DevCurve* __restrict__ curves, int slot, int row, V3 ro, V3 rd) {
+    float4 c4 = bvh.tris[3 * (size_t)slot + 2];
+    const DevCurve& c = curves[row];
+    Surf s;
+    s.material = __float_as_int(c4.z);
+    s.light = -1;
+    CurveHit h;
+    CurveFrame f;
+    h.t = h.u = h.width = 0.0f;
+    h.v = 0.5f;
+    f.n_hit = V3{0.0f, 0.0f, 1.0f};
+    // Invariant: this call finds the hit. It evaluates the expressions the traversal kernel evaluated, on the same inputs, in
+    // the same order and without contraction; the only difference is t_max = inf, which can only let more through. Should it
+    // miss all the same (another compiler, another build of one of the two), the end of this function replaces what was
+    // computed from the empty hit by a finite surface, so that no NaN reaches the film.
+    f.o = ro;
+    f.d = rd;
+    f.right = V3{1.0f, 0.0f, 0.0f};
+    f.up = V3{0.0f, 1.0f, 0.0f};
+    f.dir = V3{0.0f, 0.0f, 1.0f};
+    f.ray_length = 1.0f;
+    const bool found = curve_test(c, TravRay{ro.x, ro.y, ro.z, rd.x, rd.y, rd.z, kInf}, kInf, false, &h, &f);
+    const int type = c.flags & kCurveTypeMask;
+    V3 dpdu, dpdv;
+    (void)curve_eval(V3{c.cp[0], c.cp[1], c.cp[2]}, V3{c.cp[3], c.cp[4], c.cp[5]}, V3{c.cp[6], c.cp[7], c.cp[8]}, V3{c.cp[9], c.cp[10], c.cp[11]},
+                     h.u, &dpdu);
+    if (type == kCurveRibbon) {
+        dpdv = normalize(cross(f.n_hit, dpdu)) * h.width;
+    } else {
+        // object_to_ray and back are rotations by (right, up, dir)
+        const V3 du = V3{dot(f.right, dpdu), dot(f.up, dpdu), dot(f.dir, dpdu)};
+        V3 dv = normalize(V3{-du.y, du.x, 0.0f}) * h.width;
+        if (type == kCurveCylinder) {
+            // Rotate(-theta, dpdu_plane) (transform.rs): v cos + (a x v) sin + a (a . v) (1 - cos) about the unit axis a
+            const float theta = curve_lerp(h.v, -90.0f, 90.0f);
+            float sn, cs;
+            det_sincos(-theta * (kPi / 180.0f), &sn, &cs);
+            const V3 a = normalize(du);
+            dv = dv * cs + cross(a, dv) * sn + a * (dot(a, dv) * (1.0f - cs));
+        }
+        dpdv = f.right * dv.x + f.up * dv.y + f.dir * dv.z;
+    }
+    V3 n = normalize(cross(dpdu, dpdv));  // SurfaceInteraction::new (interaction.rs:248-300)
+    if (c.flags & kCurveFlipNormal) n = -n;
+    const V3 ph = f.o + f.d * h.t;
+    const float pe = 2.0f * h.width;
+    const float* w = c.o2w;
+    const float* o = c.w2o;
+    const float g3 = kGamma3;
+    const float x = ph.x, y = ph.y, z = ph.z;
+    s.p = V3{w[0] * x + w[1] * y + w[2] * z + w[3], w[4] * x + w[5] * y + w[6] * z + w[7], w[8] * x + w[9] * y + w[10] * z + w[11]};
+    s.p_error.x = (g3 + 1.0f) * (__builtin_fabsf(w[0] * pe) + __builtin_fabsf(w[1] * pe) + __builtin_fabsf(w[2] * pe)) +
+                  g3 * (__builtin_fabsf(w[0] * x) + __builtin_fabsf(w[1] * y) + __builtin_fabsf(w[2] * z) + __builtin_fabsf(w[3]));
+    s.p_error.y = (g3 + 1.0f) * (__builtin_fabsf(w[4] * pe) + __builtin_fabsf(w[5] * pe) + __builtin_fabsf(w[6] * pe)) +
+                  g3 * (__builtin_fabsf(w[4] * x) + __builtin_fabsf(w[5] * y) + __builtin_fabsf(w[6] * z) + __builtin_fabsf(w[7]));
+    s.p_error.z = (g3 + 1.0f) * (__builtin_fabsf(w[8] * pe) + __builtin_fabsf(w[9] * pe) + __builtin_fabsf(w[10] * pe)) +
+                  g3 * (__builtin_fabsf(w[8] * x) + __builtin_fabsf(w[9] * y) + __builtin_fabsf(w[10] * z) + __builtin_fabsf(w[11]));
+    auto vec = [](const float* m, V3 v) {  // Transform * Vector3: the upper 3x3
+        return V3{m[0] * v.x + m[1] * v.y + m[2] * v.z, m[4] * v.x + m[5] * v.y + m[6] * v.z, m[8] * v.x + m[9] * v.y + m[10] * v.z};
+    };
+    auto nrm = [o](V3 v) {  // Transform * Normal3: the transpose of the inverse's upper 3x3
+        return V3{o[0] * v.x + o[4] * v.y + o[8] * v.z, o[1] * v.x + o[5] * v.y + o[9] * v.z, o[2] * v.x + o[6] * v.y + o[10] * v.z};
+    };
+    s.n = normalize(nrm(n));
+    s.wo = normalize(vec(w, -f.d));
+    s.dpdu = vec(w, dpdu);
+    if (!found) {  // (see the invariant above) the curve's material at the ray's origin, facing the ray
+        s.p = ro;
+        s.p_error = V3{0.0f, 0.0f, 0.0f};
+        s.n = s.wo = normalize(-rd);
+        V3 other;
+        coordinate_system(s.n, &s.dpdu, &other);
+    }
+    s.ns = s.n;
+    s.sdpdu = s.dpdu;
+    return s;
+}
+// Hit record -> world-space surface in a scene with curves: `ro` / `rd` the world-space ray; everything but a curve as in the
+// build for shapes
+PB_DEV Surf surface_from_hit_curves(const DevBVH& bvh, const DevCurve* __restrict__ curves, int slot, float b0, float b1, float b2, V3 ro, V3 rd) {
+    const float4 c4 = bvh.tris[3 * (size_t)slot + 2];
+    Surf s;
+    if ((__float_as_int(c4.w) & kPrimSphere) && __float_as_int(c4.x) < 0)
+        s = make_surface_curve(bvh, curves, slot, ~__float_as_int(c4.x), ro, rd);
+    else
+        s = surface_from_hit<true>(bvh, slot, -1, b0, b1, b2, rd);
+    return s;
+}
 // SurfaceInteraction::n of a hit at barycentrics (b0, b1, b2): the geometric normal, on the shading normal's side
 template <bool SHP = false>
 PB_DEV V3 tri_interaction_normal(const DevBVH& bvh, int slot, float b0, float b1, float b2) {
@@ -461,7 +556,13 @@ struct ShadeConsts {
     const DevDisney* disney;  // [n_materials]: the blocks of the kMatDisney rows (wf_disney.h)
     const DevLightMap* light_maps;  // side table of the projection / goniometric lights (DevLight::slot), null when there are none
     const DevLobeRow* lobe_rows;  // [n_materials]: the lobe lists of the kMatLobes rows (wf_lobes.h)
-    const DevMotion* motions;     // [top-level leaf slots]: the side table of a scene with moving instances (motion.h), else null
+    // One side table, by the kind of scene: a scene has two levels and may move, or has one level and may hold curves, never both
+    // (creation refuses it). One slot for both keeps the argument block of every shading kernel the size and layout it had before
+    // curves, and with it the text of the 38 kernels that read nothing else new (profiles/curve_resource_usage.txt).
+    union {
+        const DevMotion* motions;  // [top-level leaf slots]: the side table of a scene with moving instances (motion.h), else null
+        const DevCurve* curves;    // the rows of a one-level scene's curve segments (shapes_curve.h), else null
+    };
 };
 
 // ---- InfiniteAreaLight with an image map (DevEnvMap): one lookup and one Distribution2D for le, sample_li and pdf_li ----

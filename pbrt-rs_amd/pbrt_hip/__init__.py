@@ -50,6 +50,7 @@ EXPORTS = [
     "pbrt_hip_instance_motion_bounds", "pbrt_hip_scene_create_two_level_moving",
     "pbrt_hip_render_moving_camera", "pbrt_hip_render_device_moving_camera", "pbrt_hip_camera_rays_moving_camera",
     "pbrt_hip_camera_motion_interpolate",
+    "pbrt_hip_curve_world_bounds", "pbrt_hip_scene_create_with_curves",
 ]
 MAT_NONE, MAT_MATTE, MAT_MIRROR, MAT_GLASS, MAT_PLASTIC, MAT_METAL = (scenes.MAT_NONE, scenes.MAT_MATTE, scenes.MAT_MIRROR,
                                                                       scenes.MAT_GLASS, scenes.MAT_PLASTIC, scenes.MAT_METAL)
@@ -158,6 +159,9 @@ def lib():
                                                          ctypes.POINTER(vp)]
         L.pbrt_hip_shape_world_bounds.argtypes = [vp, i32, vp]
         L.pbrt_hip_scene_create_with_shapes.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, i32, vp,
+                                                        ctypes.POINTER(vp)]
+        L.pbrt_hip_curve_world_bounds.argtypes = [vp, i32, vp]
+        L.pbrt_hip_scene_create_with_curves.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, vp, vp, i32, vp, i32, vp, i32, vp, i32, vp,
                                                         ctypes.POINTER(vp)]
         L.pbrt_hip_free.argtypes = [vp]
         L.pbrt_hip_free.restype = None
@@ -480,6 +484,16 @@ def shape_world_bounds(shapes):
     return np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3:])
 
 
+def curve_world_bounds(curves):
+    """Shape::world_bound per PbrtCurve record (scenes.CURVE_DTYPE): (n, 3) mins and (n, 3) maxs. Host only."""
+    curves = np.ascontiguousarray(curves, dtype=scenes.CURVE_DTYPE).reshape(-1)
+    out = np.zeros((len(curves), 6), dtype=np.float32)
+    rc = lib().pbrt_hip_curve_world_bounds(_p(curves) if len(curves) else None, len(curves), _p(out) if len(curves) else None)
+    if rc != 0:
+        raise PbrtHipError(f"pbrt_hip_curve_world_bounds failed ({rc})")
+    return np.ascontiguousarray(out[:, :3]), np.ascontiguousarray(out[:, 3:])
+
+
 def build_general_two_level(scene, max_prims_in_node=4, split_method=SPLIT_SAH):
     """Host BVH builds for scenes.two_level_scene-style scenes: one tree per object, the top-level tree over the instances'
     world bounds followed by the world triangles' bounds. Returns (object trees [(nodes, order)], instances, tlas_nodes, tlas_order)."""
@@ -542,6 +556,9 @@ class Scene:
 
     def _create(self, ctx, scene, max_prims_in_node, split_method, bvh, device_build):
         self.ctx = ctx
+        has_curves = scene.get("curves") is not None and len(scene["curves"]) > 0
+        if has_curves and ("objects" in scene or "instances" in scene or device_build):
+            raise PbrtHipError('"curves" live in one-level scenes over a host-built tree: not with "objects", "instances" or device_build')
         if "objects" in scene:
             self._init_two_level(scene, max_prims_in_node, split_method, bvh)
             return
@@ -566,6 +583,13 @@ class Scene:
         tri_light = np.ascontiguousarray(scene["tri_light"], dtype=np.int32)
         lights = np.ascontiguousarray(scene["lights"], dtype=LIGHT_DTYPE)
         spheres, shapes = scene.get("spheres"), scene.get("shapes")
+        # (with shapes an empty "curves" array goes the same way: n_curves == 0 is pbrt_hip_scene_create_with_shapes by another name;
+        # without shapes it is no key at all, and the scene takes the paths below with its per-vertex shading data)
+        if has_curves or (scene.get("curves") is not None and shapes is not None and len(shapes)):
+            if spheres is not None and len(spheres):
+                raise PbrtHipError('a scene with "curves" holds "shapes", not "spheres" (a Sphere is a shape: scenes.sphere_shape)')
+            self._init_with_curves(scene, tri_material, materials, tri_light, lights, max_prims_in_node, split_method, bvh)
+            return
         if shapes is not None and len(shapes):
             if spheres is not None and len(spheres):
                 raise PbrtHipError('a scene holds either "spheres" or "shapes", not both (a Sphere is a shape: scenes.sphere_shape)')
@@ -624,6 +648,36 @@ class Scene:
             _p(materials), len(materials), _p(tri_light), _p(lights) if len(lights) else None, len(lights), _p(shapes),
             len(shapes), _p(self.nodes), len(self.nodes), _p(self.prim_order), ctypes.byref(h))
         self.ctx.check(rc, "pbrt_hip_scene_create_with_shapes")
+        self.h = h
+        self.ctx._scenes.add(self)
+
+    def _init_with_curves(self, scene, tri_material, materials, tri_light, lights, max_prims_in_node, split_method, bvh):
+        """scene["curves"]: scenes.CURVE_DTYPE records (scenes.curve / curves) behind the optional scene["shapes"]; curve j is
+        primitive n_tris + n_shapes + j. The tree is built over the primitives' world bounds. A record whose bounds cannot be
+        formed (an unknown type) or are not finite (a NaN control point) gets an empty box at the origin instead of an error here:
+        such a record never makes a scene, and the creation call that refuses it names the reason, which the bounds call cannot."""
+        shapes = scene.get("shapes")
+        shapes = np.ascontiguousarray(shapes if shapes is not None else np.zeros(0, scenes.SHAPE_DTYPE), dtype=scenes.SHAPE_DTYPE).reshape(-1)
+        curves = np.ascontiguousarray(scene["curves"], dtype=scenes.CURVE_DTYPE).reshape(-1)
+        if bvh is None:
+            tri = self.positions[self.indices]                       # Triangle::world_bound (triangle.rs:175-180)
+            slo, shi = shape_world_bounds(shapes)                    # Shape::world_bound = object_to_world * object_bound()
+            try:
+                clo, chi = curve_world_bounds(curves)
+            except PbrtHipError:                                     # (a record the bounds cannot take: the creation call
+                clo = chi = np.zeros((len(curves), 3), np.float32)   # below refuses it and says why; so for a box that is
+            bad = ~(np.isfinite(clo).all(axis=1) & np.isfinite(chi).all(axis=1))   # not finite)
+            clo, chi = np.where(bad[:, None], 0, clo).astype(np.float32), np.where(bad[:, None], 0, chi).astype(np.float32)
+            bvh = bvh_build_boxes(np.concatenate([tri.min(axis=1), slo, clo]), np.concatenate([tri.max(axis=1), shi, chi]),
+                                  max_prims_in_node, split_method)
+        self.nodes, self.prim_order = bvh
+        h = ctypes.c_void_p()
+        rc = lib().pbrt_hip_scene_create_with_curves(
+            self.ctx.h, _p(self.positions), self.positions.shape[0], _p(self.indices), self.indices.shape[0], _p(tri_material),
+            _p(materials), len(materials), _p(tri_light), _p(lights) if len(lights) else None, len(lights),
+            _p(shapes) if len(shapes) else None, len(shapes), _p(curves) if len(curves) else None, len(curves),
+            _p(self.nodes), len(self.nodes), _p(self.prim_order), ctypes.byref(h))
+        self.ctx.check(rc, "pbrt_hip_scene_create_with_curves")
         self.h = h
         self.ctx._scenes.add(self)
 

@@ -30,6 +30,13 @@ SHAPE_DTYPE = np.dtype([("type", "<i4"), ("reverse_orientation", "<i4"), ("mater
                         ("z_min", "<f4"), ("z_max", "<f4"), ("inner_radius", "<f4"), ("phi_max", "<f4"), ("pad", "<f4", 3),
                         ("to_world", "<f4", 16), ("to_object", "<f4", 16)])
 SHAPE_SPHERE, SHAPE_DISK, SHAPE_CYLINDER = 0, 1, 2
+# PbrtCurve (pbrt_hip_scene_create_with_curves): scene["curves"] is an array of these, curve j is primitive n_tris + n_shapes + j
+CURVE_DTYPE = np.dtype([("type", "<i4"), ("reverse_orientation", "<i4"), ("material", "<i4"), ("cp", "<f4", (4, 3)),
+                        ("width0", "<f4"), ("width1", "<f4"), ("u_min", "<f4"), ("u_max", "<f4"), ("n0", "<f4", 3), ("n1", "<f4", 3),
+                        ("to_world", "<f4", 16), ("to_object", "<f4", 16)])
+CURVE_FLAT, CURVE_CYLINDER, CURVE_RIBBON = 0, 1, 2
+CURVE_TYPES = {"flat": CURVE_FLAT, "cylinder": CURVE_CYLINDER, "ribbon": CURVE_RIBBON}
+assert CURVE_DTYPE.itemsize == 228
 NODE_DTYPE = np.dtype([("bmin", "<f4", 3), ("bmax", "<f4", 3), ("offset", "<i4"), ("n_primitives", "<u2"),
                        ("axis", "u1"), ("pad", "u1")])
 assert MATERIAL_DTYPE.itemsize == 32 and LIGHT_DTYPE.itemsize == 96
@@ -280,6 +287,35 @@ def cylinder(radius, z_min, z_max, phi_max=360.0, to_world=None, material=0, lig
 def shapes(*records):
     """The records of sphere_shape / disk / cylinder as one scene["shapes"] array."""
     return np.concatenate(records) if records else np.zeros(0, dtype=SHAPE_DTYPE)
+
+
+def curve(cp, width0, width1, type="flat", normals=None, to_world=None, material=0, split_depth=3, reverse_orientation=False):
+    """CreateCurveShape of pbrt-v3: the 2**split_depth PbrtCurve records of one cubic Bezier curve, segment i spanning
+    [i, i + 1] / 2**split_depth of the whole curve. cp: (4, 3) object-space control points; width0 / width1: the width at u = 0
+    and u = 1; type: "flat", "cylinder" or "ribbon" (a CURVE_* value is taken as it is); normals: (2, 3), ribbons only;
+    to_world: 4x4 affine (None = identity), the inverse is formed in float64 and rounded once."""
+    kind = CURVE_TYPES[type] if isinstance(type, str) else int(type)
+    m = np.eye(4) if to_world is None else np.asarray(to_world, dtype=np.float32).astype(np.float64).reshape(4, 4)
+    n_seg = 1 << int(split_depth)
+    rec = np.zeros(n_seg, dtype=CURVE_DTYPE)
+    rec["type"], rec["reverse_orientation"], rec["material"] = kind, int(bool(reverse_orientation)), material
+    rec["cp"] = np.asarray(cp, dtype=np.float32).reshape(4, 3)
+    rec["width0"], rec["width1"] = width0, width1
+    rec["u_min"] = np.arange(n_seg, dtype=np.float64) / n_seg
+    rec["u_max"] = np.arange(1, n_seg + 1, dtype=np.float64) / n_seg
+    if normals is not None:
+        nn = np.asarray(normals, dtype=np.float32).reshape(2, 3)
+        rec["n0"], rec["n1"] = nn[0], nn[1]
+    rec["to_world"] = m.astype(np.float32).reshape(16)
+    inv = np.linalg.inv(m)
+    inv[3] = (0.0, 0.0, 0.0, 1.0)
+    rec["to_object"] = inv.astype(np.float32).reshape(16)
+    return rec
+
+
+def curves(*records):
+    """The records of curve(...) calls as one scene["curves"] array."""
+    return np.concatenate(records) if records else np.zeros(0, dtype=CURVE_DTYPE)
 
 
 def _quad(a, b, c, d):

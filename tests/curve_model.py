@@ -8,7 +8,9 @@ ancestors' boxes pass the culling tests, the leaf test of curve.rs:196-243, and 
 which moves t by about 1e-7 of the origin's distance.
 
 intersect() returns a dict of arrays: hit, t, u, v, width (hit_width), p / n / dpdu / dpdv (world space), p_error (2 hit_width),
-depth (max_depth of the ray) and margin: how far the ray is from the nearest decision of the algorithm that would change the
+depth (max_depth of the ray), side (the sine of the angle between the curve's tangent and the offset of the curve point from the
+ray, both across the ray: the sign of it picks v's half of the strip, so that where |side| |v - 0.5| is within the rounding of the
+position, in widths, v may come out as 1 - v) and margin: how far the ray is from the nearest decision of the algorithm that would change the
 answer (an edge test, the width test, the z range, the depth's threshold), in units of hit_width; a ray with a small margin is
 one where float32 and float64 may legitimately disagree about hit or miss.
 """
@@ -127,7 +129,7 @@ def intersect(rec, o, d, t_max=np.inf, dtype=np.float64):
         k = np.round(np.log(np.maximum(arg.astype(np.float64), 1e-30) / 3.0) / np.log(4.0))
         depth_margin = np.abs(arg.astype(np.float64) / (3.0 * 4.0 ** np.clip(k, 0, 10)) - 1.0)
 
-    out = dict(hit=np.zeros(R, bool), t=np.full(R, np.inf, f), u=np.zeros(R, f), v=np.zeros(R, f), width=np.zeros(R, f),
+    out = dict(hit=np.zeros(R, bool), t=np.full(R, np.inf, f), u=np.zeros(R, f), v=np.zeros(R, f), width=np.zeros(R, f), side=np.zeros(R, f),
                n_hit=np.zeros((R, 3), f), depth=depth.astype(np.int32), margin=np.full(R, np.inf))
     out["margin"] = np.where(depth_margin < 1e-4, 0.0, np.inf)
     if kind == 2:
@@ -150,7 +152,7 @@ def intersect(rec, o, d, t_max=np.inf, dtype=np.float64):
 
         best_t = np.full(len(idx), np.inf, f)
         got = np.zeros(len(idx), bool)
-        res = {k: np.zeros(len(idx), f) for k in ("u", "v", "width")}
+        res = {k: np.zeros(len(idx), f) for k in ("u", "v", "width", "side")}
         res_n = np.zeros((len(idx), 3), f)
         margin = np.full(len(idx), np.inf)
         for i in range(n_leaf):
@@ -186,6 +188,7 @@ def intersect(rec, o, d, t_max=np.inf, dtype=np.float64):
                 t = pc[:, 2] / rl
                 edge_func = dpcdw[:, 0] * -pc[:, 1] + pc[:, 0] * dpcdw[:, 1]
                 v = np.where(edge_func > 0, f(0.5) + dist / hw, f(0.5) - dist / hw)
+                side = edge_func / np.sqrt((dpcdw[:, 0] ** 2 + dpcdw[:, 1] ** 2) * dist2)
                 # signed margins of the leaf's tests in units of hit_width (positive: passes)
                 l_ab = np.sqrt((b[:, 0] - a[:, 0]) ** 2 + (b[:, 1] - a[:, 1]) ** 2)
                 l_ce = np.sqrt((c[:, 0] - e[:, 0]) ** 2 + (c[:, 1] - e[:, 1]) ** 2)
@@ -197,7 +200,7 @@ def intersect(rec, o, d, t_max=np.inf, dtype=np.float64):
             better = ok & (t < best_t)
             best_t = np.where(better, t, best_t)
             got |= better
-            for key, val in (("u", u), ("v", v), ("width", hw)):
+            for key, val in (("u", u), ("v", v), ("width", hw), ("side", np.where(np.isfinite(side), side, 0))):
                 res[key] = np.where(better, val, res[key])
             res_n = np.where(better[:, None], n_hit, res_n)
         out["hit"][idx] = got
@@ -238,15 +241,16 @@ def intersect(rec, o, d, t_max=np.inf, dtype=np.float64):
 
 def intersect_many(recs, o, d, t_max=np.inf, dtype=np.float64):
     """The brute-force aggregate: every record against every ray; the nearest hit, ties to the lower record index.
-    Returns (hit, t, record index, u, v, margin)."""
+    Returns (hit, t, record index, u, v, side, margin)."""
     recs = np.asarray(recs).reshape(-1)
     R = len(np.asarray(o).reshape(-1, 3))
-    best = dict(hit=np.zeros(R, bool), t=np.full(R, np.inf), prim=np.full(R, -1), u=np.zeros(R), v=np.zeros(R), margin=np.full(R, np.inf))
+    best = dict(hit=np.zeros(R, bool), t=np.full(R, np.inf), prim=np.full(R, -1), u=np.zeros(R), v=np.zeros(R), side=np.zeros(R),
+                margin=np.full(R, np.inf))
     for j, rec in enumerate(recs):
         r = intersect(rec, o, d, t_max, dtype)
         better = r["hit"] & (r["t"] < best["t"])
         best["hit"] |= better
-        for key in ("t", "u", "v"):
+        for key in ("t", "u", "v", "side"):
             best[key] = np.where(better, r[key], best[key])
         best["prim"] = np.where(better, j, best["prim"])
         best["margin"] = np.minimum(best["margin"], r["margin"])

@@ -1,5 +1,7 @@
 """The Curve shape on the CPU: the float64 model (tests/curve_model.py) against closed forms, the shared cases' exclusion cap and
-float32 spread (tests/curve_cases.py), and the host surface of the feature (record layout, symbols, pbrt_hip_curve_world_bounds)."""
+float32 spread (tests/curve_cases.py), the edge cases' margins, caps, hit shares and depths, how far a reversed normal or a turned
+frame moves what test_gpu_curve_shading.py expects, and the host surface of the feature (record layout, symbols,
+pbrt_hip_curve_world_bounds)."""
 import ctypes
 import os
 import subprocess
@@ -181,6 +183,83 @@ def test_cases_leave_out_few_rays_and_hit_often(case):
     np.testing.assert_array_equal(m32["hit"][keep], m64["hit"][keep])
     sp = cc.case_spread(*case)
     assert sp["t"] < 1e-4 and sp["u"] < 1e-4 and sp["v"] < 1e-2, sp
+
+
+@pytest.mark.parametrize("case", cc.EDGE_CASES, ids=lambda c: "-".join(c))
+def test_edge_cases_are_decided_by_the_model(case):
+    """what test_gpu_curve_edges.py relies on: a margin among EDGE_MARGINS at which the float32 run gives the float64 run's
+    verdict on every kept ray, few rays left out, hits and misses both present (but where the case is built to have one of
+    them only), the refinement depth the case is there for, finite records, and each case's own property"""
+    name, kind = case
+    curves, (o, d, t_max), m64, m32, margin = cc.edge_model(*case)
+    _, depth_wanted, _ = cc.EDGE_NAMES[name]
+    assert margin in cc.EDGE_MARGINS, "no margin decides the case"
+    by_margin = m64["margin"] >= margin
+    np.testing.assert_array_equal(m32["hit"][by_margin], m64["hit"][by_margin])
+    keep, dt = cc.edge_keep(*case)   # the device's origin push takes out a few more
+    print("-".join(case), "origin push dt up to %.2e, takes out %.4f of the rays" % (dt.max(), (by_margin & ~keep).mean()))
+    depth = max(int(cm.intersect(rec, o, d, t_max)["depth"].max()) for rec in curves)
+    sp = cc.edge_spread(*case)
+    print("-".join(case), "margin %g left out %.4f hits %.3f depth %d spread t %.2e u %.2e v %.2e" % (
+        margin, 1 - keep.mean(), m64["hit"].mean(), depth, sp["t"], sp["u"], sp["v"]))
+    assert 1 - keep.mean() <= cc.EDGE_MAX_LEFT_OUT[margin]
+    for k in ("t", "u", "v"):
+        assert np.isfinite(m64[k][m64["hit"]]).all() and np.isfinite(m32[k][m32["hit"]]).all() and np.isfinite(sp[k])
+    if depth_wanted is not None:
+        assert depth == depth_wanted
+    if name == "parallel_exact":
+        assert not m64["hit"].any() and not m32["hit"].any()
+    elif name in ("loop", "loop_tmax"):   # chords of the curve: all but the edge-on ribbon's hit
+        assert m64["hit"].mean() > 0.5
+    else:
+        assert 0.1 < m64["hit"].mean() < 0.9
+    if name == "taper":   # rays aimed past the tip of zero width (u > 1 by up to 0.05) are there, and hits end before it
+        assert m64["u"][m64["hit"]].max() < 1.0
+    if name == "loop":
+        crossings = sum((cm.intersect(rec, o, d)["hit"]).astype(int) for rec in curves)
+        share = (crossings[keep] >= 2).mean()
+        print("  rays hit on two or more of the %d records: %.3f" % (len(curves), share))
+        assert len(curves) == 8 and share >= 0.5
+    if name == "loop_tmax":   # the finite t_max lies past the first crossing: the same hit as without it
+        stopped = np.isfinite(t_max)
+        free = cm.intersect_many(curves, o, d)
+        assert stopped.mean() > 0.5
+        np.testing.assert_array_equal(m64["hit"][stopped & keep], free["hit"][stopped & keep])
+        np.testing.assert_array_equal(m64["t"][stopped & keep], free["t"][stopped & keep])
+    if name == "parallel_chord":   # d along the chord to float32's rounding: the float64 model finds a residue, never zero
+        cp = curves[0]["cp"].astype(np.float64)
+        dx = np.linalg.norm(np.cross(d.astype(np.float64), cp[3] - cp[0]), axis=1)
+        assert (dx > 0).all() and (dx < 1e-6 * np.linalg.norm(d, axis=1) * np.linalg.norm(cp[3] - cp[0])).all()
+
+
+@pytest.mark.parametrize("kind", cc.TYPES)
+def test_the_orientation_test_can_fail(kind):
+    """test_gpu_curve_shading.py holds kCurveFlipNormal with a rough-glass row under a point light. Here: with the normal
+    reversed, the value that test expects moves by more than ten times its tolerance on at least half of the rays it keeps, for
+    every orientation and both lights; and with the tangents turned by 90 degrees the anisotropic metal row's does likewise."""
+    import bxdf_model as bm
+    import microfacet_model as mm
+    glass = bm.rough_glass(cc.GLASS["kr"], cc.GLASS["kt"], cc.GLASS["eta"], cc.GLASS["roughness"])
+    metal = mm.Material.metal(cc.METAL["eta"], cc.METAL["k"], cc.METAL["u_roughness"], cc.METAL["v_roughness"])
+    for xform, reverse in cc.ORIENTATIONS:
+        _, (_, d), _, surf, lights = cc.orient_case(kind, xform, reverse)
+        for light in lights:
+            keep, clear = cc.orient_kept(kind, xform, reverse, light)
+            assert len(keep) >= 128 and clear.mean() > 0.9
+            f = lambda wo, wi: bm.bsdf_f(glass, wo, wi)
+            want = cc.point_light_radiance(surf, keep, d, lights[light], cc.ORIENT_INTENSITY, f)
+            flipped = cc.point_light_radiance(surf, keep, d, lights[light], cc.ORIENT_INTENSITY, f, flip=True)
+            moved = (np.abs(flipped - want) > 10 * cc.GLOSSY_RTOL * np.abs(want)).any(-1)
+            print(f"{kind} {xform} reverse {int(reverse)} light {light}: kept {len(keep)}, moved by a reversed normal {moved.mean():.3f}")
+            assert moved.mean() >= 0.5
+        if xform == "scaled":
+            keep, _ = cc.orient_kept(kind, xform, reverse, "front")
+            g = lambda wo, wi: mm.bsdf_f(metal, wo, wi)
+            want = cc.point_light_radiance(surf, keep, d, lights["front"], cc.ORIENT_INTENSITY, g)
+            turned = cc.point_light_radiance(surf, keep, d, lights["front"], cc.ORIENT_INTENSITY, g, turn=True)
+            moved = (np.abs(turned - want) > 10 * cc.GLOSSY_RTOL * np.abs(want)).any(-1)
+            print(f"{kind} {xform} metal: moved by a frame turned by 90 degrees {moved.mean():.3f}")
+            assert moved.mean() >= 0.5
 
 
 def test_record_layout_and_symbols(tmp_path):

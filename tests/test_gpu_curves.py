@@ -6,7 +6,11 @@ entry point, plastic and Disney rows on a curve, the refusals, and examples/rend
 Tolerance of t, u and v against the model: four times the spread of the model's own float32 run against its float64 run over the
 same cases (curve_cases.case_spread, the largest over the 18 cases), as measured on the CPU by this file at import:
     spread  t 3.04e-06  u 1.70e-06  v 3.11e-04      tolerance  t 1.21e-05  u 6.79e-06  v 1.25e-03
-(test_tolerances_are_the_measured_spread prints the figures of the run at hand)."""
+(test_tolerances_are_the_measured_spread prints the figures of the run at hand).
+
+test_gpu_curve_edges.py holds the hit test at the inputs these cases do not reach (each with a margin and a tolerance of its own)
+and curves among other primitives; test_gpu_curve_shading.py holds the surface on every case, the orientation flag, and the
+integrators and lights beyond point and distant ones."""
 import re
 import subprocess
 

@@ -1,6 +1,7 @@
 // host_envmap.h — InfiniteAreaLight's image map on the host: MIPMap::new (src/core/mipmap.rs:76-183, ImageWrap::Repeat,
 // no trilinear flag) over the texels x L, and the 2W x 2H sin-weighted Distribution2D (src/lights/infinite.rs:59-73,
 // src/core/sampling.rs:62-215) as the device reads it (scene.h: DevEnvMap). Intended semantics: DESIGN.md, D33 / D40 / D48 / D59-D62.
+// What an edit makes of the tables (the light's transform and power, the texels, the power distribution): host_edit.h.
 #pragma once
 #include <cstdint>
 #include <vector>

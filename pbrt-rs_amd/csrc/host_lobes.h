@@ -1,6 +1,6 @@
 // host_lobes.h — the lobe list (the reference's BSDF, reflection.rs:207-449) of any material row description, on the host.
-// One function per description, all ending in the same LobeList; pbrt_hip_scene_set_lobe_material and the context-free
-// pbrt_hip_material_lobes (include/pbrt_hip.h) call them. The rules that turn a PbrtMaterial / PbrtMaterialDesc into a
+// One function per description, all ending in the same LobeList; host_edit.cpp's lobe_row_of_desc (the host half of
+// pbrt_hip_scene_set_lobe_material) and the context-free pbrt_hip_material_lobes (include/pbrt_hip.h) call them. The rules that turn a PbrtMaterial / PbrtMaterialDesc into a
 // DevMaterial row live here as well, so that the scene and the listing cannot disagree. No device code.
 #pragma once
 #include <algorithm>

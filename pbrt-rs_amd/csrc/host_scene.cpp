@@ -377,6 +377,66 @@ static std::string instancing_invalid(const SceneDesc& desc, int* depth) {
     return std::string();
 }
 
+const char* combine_two_level(const TwoLevelArgs& a, CombinedMesh* out) {
+    const int32_t n_objects = a.n_objects, n_world_tris = a.n_world_tris, n_world_verts = a.n_world_verts;
+    if (!a.objects || n_objects <= 0 || !a.instances || a.n_instances <= 0 || !a.tlas_nodes || a.n_tlas_nodes <= 0 || !a.tlas_order)
+        return "two-level scene needs objects, instances and a top-level node array";
+    if (n_world_tris < 0 || n_world_verts < 0 || (n_world_tris > 0 && (!a.world_positions || !a.world_indices || n_world_verts <= 0)))
+        return "bad world-space triangle arguments";
+    // ---- the combined mesh: object after object, then the world-space triangles ----
+    InstancingArgs& ia = out->ia;
+    ia = InstancingArgs{a.instances, a.n_instances, a.tlas_nodes, a.n_tlas_nodes, a.tlas_order, a.objects, n_objects, a.instance_object, a.motions,
+                        std::vector<int32_t>(n_objects + 1, 0), n_world_tris, 0};
+    int64_t n_verts = 0, n_tris = 0, n_nodes = 0;
+    for (int32_t k = 0; k < n_objects; ++k) {
+        const PbrtObject& o = a.objects[k];
+        if (!o.positions || !o.indices || !o.nodes || !o.prim_order || o.n_verts <= 0 || o.n_tris <= 0 || o.n_nodes <= 0)
+            return "object aggregate with a null pointer or an empty mesh / tree";
+        if (!mesh_indices_in_range(o.indices, o.n_tris, o.n_verts)) return "object vertex index out of range";
+        for (int32_t i = 0; i < o.n_tris; ++i)
+            if (o.prim_order[i] < 0 || o.prim_order[i] >= o.n_tris) return "object prim_order entry out of range";
+        n_verts += o.n_verts;
+        n_tris += o.n_tris;
+        n_nodes += o.n_nodes;
+        ia.obj_tri_offset[k + 1] = (int32_t)n_tris;
+    }
+    ia.world_tri_offset = (int32_t)n_tris;
+    if (!mesh_indices_in_range(a.world_indices, n_world_tris, n_world_verts)) return "world triangle vertex index out of range";
+    n_verts += n_world_verts;
+    n_tris += n_world_tris;
+    if (n_tris >= (1ll << 30) || n_verts >= (1ll << 31)) return "two-level scene too large";
+    for (int32_t i = 0; i < a.n_instances; ++i)
+        if (a.instance_object && (a.instance_object[i] < 0 || a.instance_object[i] >= n_objects)) return "instance_object out of range";
+    for (int32_t i = 0; i < a.n_lights; ++i)
+        if (a.lights[i].type == PBRT_LIGHT_DIFFUSE_AREA && (a.lights[i].prim < 0 || a.lights[i].prim >= n_world_tris))
+            return "area lights sit on world-space triangles (instanced primitives cannot be area lights): prim out of range";
+    out->n_nodes = (int32_t)n_nodes;
+    std::vector<float>& pos = out->pos;
+    std::vector<int32_t>&idx = out->idx, &mat = out->mat, &lgt = out->lgt, &order = out->order;
+    pos.assign((size_t)n_verts * 3, 0.0f);
+    idx.assign((size_t)n_tris * 3, 0);
+    mat.assign((size_t)n_tris, 0);
+    lgt.assign((size_t)n_tris, -1);
+    order.assign((size_t)n_tris, 0);
+    // the world-space triangles are one more mesh, in caller order, and the only one whose triangles can be lights
+    const PbrtObject world{a.world_positions, n_world_verts, a.world_indices, n_world_tris, a.world_tri_material, nullptr, 0, nullptr};
+    int64_t v0 = 0, t0 = 0;
+    for (int32_t k = 0; k <= n_objects; ++k) {
+        const PbrtObject& o = k < n_objects ? a.objects[k] : world;
+        if (o.n_tris <= 0) continue;
+        std::memcpy(&pos[(size_t)v0 * 3], o.positions, (size_t)o.n_verts * 12);
+        for (int64_t i = 0; i < 3 * (int64_t)o.n_tris; ++i) idx[(size_t)t0 * 3 + i] = o.indices[i] + (int32_t)v0;
+        for (int32_t i = 0; i < o.n_tris; ++i) {
+            mat[(size_t)t0 + i] = o.tri_material ? o.tri_material[i] : 0;
+            if (k == n_objects && a.world_tri_light) lgt[(size_t)t0 + i] = a.world_tri_light[i];
+            order[(size_t)t0 + i] = (o.prim_order ? o.prim_order[i] : i) + (int32_t)t0;
+        }
+        v0 += o.n_verts;
+        t0 += o.n_tris;
+    }
+    return nullptr;
+}
+
 std::string scene_invalid(const SceneDesc& desc) {
     const SphereArgs& sa = desc.sa;
     const InstancingArgs& ia = desc.ia;

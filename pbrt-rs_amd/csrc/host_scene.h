@@ -74,6 +74,37 @@ struct SceneDesc {
 // pbrt_hip_last_error, empty when the description is fine.
 std::string scene_invalid(const SceneDesc& desc);
 
+// What pbrt_hip_scene_create_two_level_moving is called with, in its order (the other two-level entry points leave out a part)
+struct TwoLevelArgs {
+    const PbrtObject* objects;
+    int32_t n_objects;
+    const PbrtInstance* instances;
+    const PbrtInstanceMotion* motions;
+    const int32_t* instance_object;
+    int32_t n_instances;
+    const float* world_positions;
+    int32_t n_world_verts;
+    const int32_t* world_indices;
+    int32_t n_world_tris;
+    const int32_t *world_tri_material, *world_tri_light;
+    const PbrtMaterial* materials;
+    int32_t n_materials;
+    const PbrtLight* lights;
+    int32_t n_lights;
+    const PbrtLinearBVHNode* tlas_nodes;
+    int32_t n_tlas_nodes;
+    const int32_t* tlas_order;
+};
+// The combined mesh of a two-level scene (InstancingArgs above), owned: what the SceneDesc of such a scene points at
+struct CombinedMesh {
+    std::vector<float> pos;
+    std::vector<int32_t> idx, mat, lgt, order;  // lgt: -1 on object triangles; order: the combined leaf order
+    int32_t n_nodes = 0;                        // the objects' total
+    InstancingArgs ia;
+};
+// Checks the arguments that become subscripts here and concatenates the meshes; nullptr, or the refusal (*out unspecified then)
+const char* combine_two_level(const TwoLevelArgs& a, CombinedMesh* out);
+
 // Validates one reference-order LinearBVHNode array (nullptr, or the refusal) ...
 // force_count_bits >= 0: the width of (n_primitives - 1) in the leaf references (several object trees share one width);
 // n_slots_total >= 0: the leaf slots of the whole scene, where the tree is one of several.

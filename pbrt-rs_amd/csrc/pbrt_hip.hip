@@ -14,8 +14,7 @@
 #include <string>
 #include <vector>
 
-#include "host_envmap.h"
-#include "host_lobes.h"
+#include "host_edit.h"
 #include "host_motion.h"
 #include "host_scene.h"
 #include "host_wide.h"
@@ -327,10 +326,8 @@ static void upload_tables(PbrtHipScene* s, const SceneDesc& desc, ScenePlan& pla
         d.lobe_rows = dev_upload(s, s->h_lobe_rows.data(), s->h_lobe_rows.size(), ok);
     }
     d.lights = dev_upload(s, plan.lights.data(), plan.lights.size(), ok);
-    if (plan.light_maps) {
-        d.light_maps = dev_upload(s, plan.light_map_rows.data(), plan.light_map_rows.size(), ok);
-        s->light_map_allocs.assign(n_lights, nullptr);
-    }
+    if (plan.light_maps) d.light_maps = dev_upload(s, plan.light_map_rows.data(), plan.light_map_rows.size(), ok);
+    s->light_allocs.assign(n_lights, {});
     d.infinite_ids = dev_upload(s, plan.infinite_ids.data(), plan.infinite_ids.size(), ok);
     if (n_lights > 0) {
         d.light_distrib_uniform.func = dev_upload(s, plan.uniform_func.data(), plan.uniform_func.size(), ok);
@@ -626,86 +623,18 @@ extern "C" int pbrt_hip_scene_create_with_curves(PbrtHipContext* ctx, const floa
 }
 PB_ABI_CATCH
 
-// pbrt_hip_scene_create_two_level and, with `motions`, pbrt_hip_scene_create_two_level_moving
-static int create_two_level(PbrtHipContext* ctx, const PbrtObject* objects, int32_t n_objects, const PbrtInstance* instances,
-                            const PbrtInstanceMotion* motions, const int32_t* instance_object, int32_t n_instances,
-                            const float* world_positions, int32_t n_world_verts, const int32_t* world_indices, int32_t n_world_tris,
-                            const int32_t* world_tri_material, const int32_t* world_tri_light, const PbrtMaterial* materials,
-                            int32_t n_materials, const PbrtLight* lights, int32_t n_lights, const PbrtLinearBVHNode* tlas_nodes,
-                            int32_t n_tlas_nodes, const int32_t* tlas_order, PbrtHipScene** out) {
+// pbrt_hip_scene_create_two_level(_moving): the combined mesh (host_scene.cpp), then the three phases. A refusal of the
+// arguments is reported before the context is entered.
+static int create_two_level(PbrtHipContext* ctx, const TwoLevelArgs& a, PbrtHipScene** out) {
     if (!ctx || !out) return PBRT_HIP_ERR_INVALID;
-    auto fail = [&](const char* msg) {
-        ctx->last_error = msg;
+    CombinedMesh m;
+    if (const char* why = combine_two_level(a, &m)) {
+        ctx->last_error = why;
         return PBRT_HIP_ERR_INVALID;
-    };
-    if (!objects || n_objects <= 0 || !instances || n_instances <= 0 || !tlas_nodes || n_tlas_nodes <= 0 || !tlas_order)
-        return fail("two-level scene needs objects, instances and a top-level node array");
-    if (n_world_tris < 0 || n_world_verts < 0 || (n_world_tris > 0 && (!world_positions || !world_indices || n_world_verts <= 0)))
-        return fail("bad world-space triangle arguments");
-    // ---- the combined mesh: object after object, then the world-space triangles ----
-    InstancingArgs ia;
-    ia.instances = instances;
-    ia.n_instances = n_instances;
-    ia.tlas_nodes = tlas_nodes;
-    ia.n_tlas_nodes = n_tlas_nodes;
-    ia.tlas_order = tlas_order;
-    ia.objects = objects;
-    ia.n_objects = n_objects;
-    ia.instance_object = instance_object;
-    ia.motions = motions;
-    ia.n_world_tris = n_world_tris;
-    int64_t n_verts = 0, n_tris = 0, n_nodes = 0;
-    ia.obj_tri_offset.assign(n_objects + 1, 0);
-    for (int32_t k = 0; k < n_objects; ++k) {
-        const PbrtObject& o = objects[k];
-        if (!o.positions || !o.indices || !o.nodes || !o.prim_order || o.n_verts <= 0 || o.n_tris <= 0 || o.n_nodes <= 0)
-            return fail("object aggregate with a null pointer or an empty mesh / tree");
-        for (int64_t i = 0; i < 3 * (int64_t)o.n_tris; ++i)
-            if (o.indices[i] < 0 || o.indices[i] >= o.n_verts) return fail("object vertex index out of range");
-        for (int32_t i = 0; i < o.n_tris; ++i)
-            if (o.prim_order[i] < 0 || o.prim_order[i] >= o.n_tris) return fail("object prim_order entry out of range");
-        n_verts += o.n_verts;
-        n_tris += o.n_tris;
-        n_nodes += o.n_nodes;
-        ia.obj_tri_offset[k + 1] = (int32_t)n_tris;
-    }
-    ia.world_tri_offset = (int32_t)n_tris;
-    for (int64_t i = 0; i < 3 * (int64_t)n_world_tris; ++i)
-        if (world_indices[i] < 0 || world_indices[i] >= n_world_verts) return fail("world triangle vertex index out of range");
-    n_verts += n_world_verts;
-    n_tris += n_world_tris;
-    if (n_tris >= (1ll << 30) || n_verts >= (1ll << 31)) return fail("two-level scene too large");
-    for (int32_t i = 0; i < n_instances; ++i)
-        if (instance_object && (instance_object[i] < 0 || instance_object[i] >= n_objects)) return fail("instance_object out of range");
-    for (int32_t i = 0; i < n_lights; ++i)
-        if (lights[i].type == PBRT_LIGHT_DIFFUSE_AREA && (lights[i].prim < 0 || lights[i].prim >= n_world_tris))
-            return fail("area lights sit on world-space triangles (instanced primitives cannot be area lights): prim out of range");
-    std::vector<float> pos((size_t)n_verts * 3);
-    std::vector<int32_t> idx((size_t)n_tris * 3), mat((size_t)n_tris, 0), lgt((size_t)n_tris, -1), order((size_t)n_tris);
-    int64_t v0 = 0, t0 = 0;
-    for (int32_t k = 0; k < n_objects; ++k) {
-        const PbrtObject& o = objects[k];
-        std::memcpy(&pos[(size_t)v0 * 3], o.positions, (size_t)o.n_verts * 12);
-        for (int64_t i = 0; i < 3 * (int64_t)o.n_tris; ++i) idx[(size_t)t0 * 3 + i] = o.indices[i] + (int32_t)v0;
-        for (int32_t i = 0; i < o.n_tris; ++i) {
-            mat[(size_t)t0 + i] = o.tri_material ? o.tri_material[i] : 0;
-            order[(size_t)t0 + i] = o.prim_order[i] + (int32_t)t0;
-        }
-        v0 += o.n_verts;
-        t0 += o.n_tris;
-    }
-    if (n_world_tris > 0) {
-        std::memcpy(&pos[(size_t)v0 * 3], world_positions, (size_t)n_world_verts * 12);
-        for (int64_t i = 0; i < 3 * (int64_t)n_world_tris; ++i) idx[(size_t)t0 * 3 + i] = world_indices[i] + (int32_t)v0;
-        for (int32_t i = 0; i < n_world_tris; ++i) {
-            mat[(size_t)t0 + i] = world_tri_material ? world_tri_material[i] : 0;
-            lgt[(size_t)t0 + i] = world_tri_light ? world_tri_light[i] : -1;
-            order[(size_t)t0 + i] = (int32_t)t0 + i;
-        }
     }
     // (no one node array: the trees are the objects' and the top-level one; n_nodes is the objects' total)
-    SceneDesc desc{pos.data(), (int32_t)n_verts, idx.data(), (int32_t)n_tris, mat.data(), materials, n_materials, lgt.data(), lights, n_lights,
-                   nullptr, (int32_t)n_nodes, order.data(), SphereArgs(), std::move(ia)};
+    SceneDesc desc{m.pos.data(), (int32_t)m.pos.size() / 3, m.idx.data(), (int32_t)m.mat.size(), m.mat.data(), a.materials, a.n_materials,
+                   m.lgt.data(), a.lights, a.n_lights, nullptr, m.n_nodes, m.order.data(), SphereArgs(), std::move(m.ia)};
     return create_scene(ctx, desc, out);
 }
 
@@ -716,9 +645,9 @@ extern "C" int pbrt_hip_scene_create_two_level(PbrtHipContext* ctx, const PbrtOb
                                                const int32_t* world_tri_light, const PbrtMaterial* materials, int32_t n_materials,
                                                const PbrtLight* lights, int32_t n_lights, const PbrtLinearBVHNode* tlas_nodes,
                                                int32_t n_tlas_nodes, const int32_t* tlas_order, PbrtHipScene** out) try {
-    return create_two_level(ctx, objects, n_objects, instances, nullptr, instance_object, n_instances, world_positions, n_world_verts,
-                            world_indices, n_world_tris, world_tri_material, world_tri_light, materials, n_materials, lights, n_lights,
-                            tlas_nodes, n_tlas_nodes, tlas_order, out);
+    return create_two_level(ctx, {objects, n_objects, instances, nullptr, instance_object, n_instances, world_positions, n_world_verts,
+                                  world_indices, n_world_tris, world_tri_material, world_tri_light, materials, n_materials, lights, n_lights,
+                                  tlas_nodes, n_tlas_nodes, tlas_order}, out);
 }
 PB_ABI_CATCH
 
@@ -734,9 +663,9 @@ extern "C" int pbrt_hip_scene_create_two_level_moving(PbrtHipContext* ctx, const
     // a scene in which nothing moves is pbrt_hip_scene_create_two_level's scene: same records, same kernels
     bool any = false;
     for (int32_t i = 0; motions && i < n_instances; ++i) any = any || motions[i].animated != 0;
-    return create_two_level(ctx, objects, n_objects, instances, any ? motions : nullptr, instance_object, n_instances, world_positions,
-                            n_world_verts, world_indices, n_world_tris, world_tri_material, world_tri_light, materials, n_materials,
-                            lights, n_lights, tlas_nodes, n_tlas_nodes, tlas_order, out);
+    return create_two_level(ctx, {objects, n_objects, instances, any ? motions : nullptr, instance_object, n_instances, world_positions,
+                                  n_world_verts, world_indices, n_world_tris, world_tri_material, world_tri_light, materials, n_materials,
+                                  lights, n_lights, tlas_nodes, n_tlas_nodes, tlas_order}, out);
 }
 PB_ABI_CATCH
 
@@ -748,18 +677,9 @@ extern "C" int pbrt_hip_scene_create_instanced(PbrtHipContext* ctx, const float*
                                                const int32_t* blas_order, const PbrtInstance* instances,
                                                int32_t n_instances, const PbrtLinearBVHNode* tlas_nodes,
                                                int32_t n_tlas_nodes, const int32_t* tlas_order, PbrtHipScene** out) try {
-    if (!ctx || !out) return PBRT_HIP_ERR_INVALID;
-    PbrtObject obj;
-    obj.positions = positions;
-    obj.n_verts = n_verts;
-    obj.indices = indices;
-    obj.n_tris = n_tris;
-    obj.tri_material = tri_material;
-    obj.nodes = blas_nodes;
-    obj.n_nodes = n_blas_nodes;
-    obj.prim_order = blas_order;
-    return pbrt_hip_scene_create_two_level(ctx, &obj, 1, instances, nullptr, n_instances, nullptr, 0, nullptr, 0, nullptr, nullptr,
-                                           materials, n_materials, lights, n_lights, tlas_nodes, n_tlas_nodes, tlas_order, out);
+    const PbrtObject obj{positions, n_verts, indices, n_tris, tri_material, blas_nodes, n_blas_nodes, blas_order};
+    return create_two_level(ctx, {&obj, 1, instances, nullptr, nullptr, n_instances, nullptr, 0, nullptr, 0, nullptr, nullptr, materials, n_materials,
+                                  lights, n_lights, tlas_nodes, n_tlas_nodes, tlas_order}, out);
 }
 PB_ABI_CATCH
 
@@ -796,49 +716,118 @@ extern "C" void pbrt_hip_scene_destroy(PbrtHipScene* s) {
     if (!s->ctx->lost) {  // a lost context: an abandoned kernel may still read the scene, and waiting for it may never end
         (void)hipStreamSynchronize(s->ctx->stream);
         for (void* p : s->allocs) (void)hipFree(p);
-        for (auto& a : s->env_allocs)
+        for (auto& a : s->light_allocs)
             for (void* p : a) (void)hipFree(p);
-        for (void* p : s->light_map_allocs)
-            if (p) (void)hipFree(p);
     }
     delete s;
 }
 
-// TrowbridgeReitzDistribution::new(alpha_u, alpha_v, true) of a plastic / metal material with pbrt-v3's remaproughness switch
-// (plastic.cpp / metal.cpp): the alphas of material `material` are replaced in the device table and its host copy.
-extern "C" int pbrt_hip_scene_set_material_roughness(PbrtHipScene* s, int32_t material, float u_roughness, float v_roughness,
-                                                     int32_t remap) try {
-    if (!s) return PBRT_HIP_ERR_INVALID;
-    PbrtHipContext* ctx = s->ctx;
-    PB_ENTER(ctx);
-    auto invalid = [&](const std::string& why) {
-        ctx->last_error = "pbrt_hip_scene_set_material_roughness: " + why;
-        return PBRT_HIP_ERR_INVALID;
-    };
-    if (material < 0 || material >= (int32_t)s->h_materials.size()) return invalid("material index out of range");
-    DevMaterial m = s->h_materials[material];
-    if (m.type != PBRT_MAT_PLASTIC && m.type != PBRT_MAT_METAL) return invalid("material is not PBRT_MAT_PLASTIC or PBRT_MAT_METAL");
-    if (const char* why = roughness_invalid(u_roughness, v_roughness, remap != 0)) return invalid(why);
-    if (m.type == PBRT_MAT_PLASTIC && u_roughness != v_roughness) return invalid("plastic is isotropic: u_roughness must equal v_roughness");
-    m.alpha_u = remap ? roughness_to_alpha(u_roughness) : u_roughness;
-    m.alpha_v = remap ? roughness_to_alpha(v_roughness) : v_roughness;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy((void*)(s->d.materials + material), &m, sizeof(DevMaterial), hipMemcpyHostToDevice));
-    s->h_materials[material] = m;
-    return PBRT_HIP_OK;
-}
-PB_ABI_CATCH
+// ---- scene edits. Every pbrt_hip_scene_set_* entry point enters through PB_EDIT (a null scene is refused, the context is
+// entered, invalid(why) refuses the call under its own name), has host_edit.cpp check the call and compute what it writes (no
+// device call there), lists the writes in a SceneEdit, applies them and commits the scene's host copies. ----
+#define PB_EDIT(s, name)                                \
+    if (!(s)) return PBRT_HIP_ERR_INVALID;              \
+    PbrtHipContext* ctx = (s)->ctx;                     \
+    PB_ENTER(ctx);                                      \
+    auto invalid = [ctx](const std::string& why) {      \
+        ctx->last_error = std::string(name ": ") + why; \
+        return PBRT_HIP_ERR_INVALID;                    \
+    }
 
-// which shading-kernel level the table needs beyond plastic / metal, after a row was replaced
-static void refresh_material_levels(PbrtHipScene* s) {
+namespace {
+// One edit of the scene's device tables: the writes it makes (host_edit.h: apply_writes) and the device arrays it brings. They
+// are freed with the edit unless a light takes them over (write_light) or a failed rollback leaves them to the scene.
+struct SceneEdit {
+    PbrtHipScene* s;
+    std::vector<DeviceWrite> writes;
+    std::vector<void*> fresh;
+    bool uploaded = true;  // every upload() so far arrived
+    ~SceneEdit() {
+        for (void* p : fresh) (void)hipFree(p);
+    }
+    // nothing reads the tables while they change
+    int begin() {
+        PbrtHipContext* ctx = s->ctx;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        return PBRT_HIP_OK;
+    }
+    template <class T>
+    const T* upload(const std::vector<T>& v) {
+        T* p = uploaded ? dev_copy(s->ctx, v.data(), v.size(), &uploaded) : nullptr;
+        if (p) fresh.push_back(p);
+        return p;
+    }
+    int apply() {
+        PbrtHipContext* ctx = s->ctx;
+        auto copy = [ctx](void* dst, const void* src, size_t bytes) {
+            return hip_ok(ctx, hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice), "hipMemcpy");
+        };
+        const Applied a = apply_writes(writes, copy, &ctx->last_error);
+        if (a == Applied::kTorn) {  // the device may still name the fresh arrays: they stay allocated until the scene is destroyed
+            s->allocs.insert(s->allocs.end(), fresh.begin(), fresh.end());
+            fresh.clear();
+        }
+        return a == Applied::kDone ? PBRT_HIP_OK : PBRT_HIP_ERR_DEVICE;
+    }
+};
+}  // namespace
+
+// Row `material` of the material table, written after the block of its kind that it names (DevDisney, DevLobeRow), and the host
+// copies: the row, who wrote it, and which shading-kernel level the table needs beyond plastic / metal.
+static int write_material(PbrtHipScene* s, int32_t material, const DevMaterial& m, int origin, const DeviceWrite* block = nullptr) {
+    SceneEdit edit{s};
+    if (int rc = edit.begin()) return rc;
+    if (block) edit.writes.push_back(*block);
+    edit.writes.push_back({(void*)(s->d.materials + material), &m, &s->h_materials[material], sizeof(DevMaterial)});
+    if (int rc = edit.apply()) return rc;
+    s->h_materials[material] = m;
+    s->h_lobe_origin[material] = origin;
     s->bxdfs = s->disney = s->lobes = false;
     for (const DevMaterial& row : s->h_materials) {
         s->lobes = s->lobes || row.type == kMatLobes;
         s->bxdfs = s->bxdfs || (row.type >= kMatOrenNayar && row.type <= kMatSubstrate);
         s->disney = s->disney || row.type == kMatDisney;
     }
+    return PBRT_HIP_OK;
 }
+
+// Light `light` changed: its descriptor, its row and the power distribution go to the device from one consistent host state.
+// Then the arrays of a map set before on this light are freed and the edit's take their place, the host copies follow, and a
+// spatial light table already built is dropped (the next render with that strategy builds it again).
+static int write_light(SceneEdit& edit, int light, const DevLight& lt, const DeviceWrite& descriptor) {
+    PbrtHipScene* s = edit.s;
+    const size_t n = (size_t)s->d.n_lights;
+    const PowerEdit p = power_edit(s->h_lights, (int)n, light, lt.power_y);
+    edit.writes = {descriptor,
+                   {(void*)(s->d.lights + light), &lt, &s->h_lights[light], sizeof(DevLight)},
+                   {(void*)s->d.light_distrib_power.func, p.func.data(), p.old_func.data(), n * sizeof(float)},
+                   {(void*)s->d.light_distrib_power.cdf, p.cdf.data(), p.old_cdf.data(), (n + 1) * sizeof(float)}};
+    if (int rc = edit.apply()) return rc;
+    s->d.light_distrib_power.func_int = p.func_int;
+    for (void* q : s->light_allocs[light]) (void)hipFree(q);
+    s->light_allocs[light] = std::move(edit.fresh);
+    edit.fresh.clear();
+    s->h_lights[light] = lt;
+    if (s->d_spatial) {
+        (void)hipFree(s->d_spatial);
+        s->allocs.erase(std::remove(s->allocs.begin(), s->allocs.end(), (void*)s->d_spatial), s->allocs.end());
+        s->d_spatial = nullptr;
+    }
+    return PBRT_HIP_OK;
+}
+
+// TrowbridgeReitzDistribution::new(alpha_u, alpha_v, true) of a plastic / metal material with pbrt-v3's remaproughness switch
+// (plastic.cpp / metal.cpp): the alphas of material `material` are replaced in the device table and its host copy.
+extern "C" int pbrt_hip_scene_set_material_roughness(PbrtHipScene* s, int32_t material, float u_roughness, float v_roughness,
+                                                     int32_t remap) try {
+    PB_EDIT(s, "pbrt_hip_scene_set_material_roughness");
+    if (material < 0 || material >= (int32_t)s->h_materials.size()) return invalid("material index out of range");
+    DevMaterial m;
+    if (const char* why = roughness_row(s->h_materials[material], u_roughness, v_roughness, remap != 0, &m)) return invalid(why);
+    return write_material(s, material, m, 0);
+}
+PB_ABI_CATCH
 
 // pbrt-v3's MatteMaterial (sigma), GlassMaterial (roughness) and SubstrateMaterial on the reference's OrenNayar,
 // MicrofacetReflection / MicrofacetTransmission and FresnelBlend (reflection.rs:917-975, 977-1192, 1194-1280): row `material`
@@ -846,113 +835,28 @@ static void refresh_material_levels(PbrtHipScene* s) {
 // PbrtMaterialType expresses becomes that row; the others become a kMatOrenNayar / kMatRoughGlass / kMatSubstrate row
 // (scene.h), which the shading kernels' level-2 instantiations shade (wf_bxdfs.h).
 extern "C" int pbrt_hip_scene_set_material(PbrtHipScene* s, int32_t material, const PbrtMaterialDesc* desc) try {
-    if (!s) return PBRT_HIP_ERR_INVALID;
-    PbrtHipContext* ctx = s->ctx;
-    PB_ENTER(ctx);
-    auto invalid = [&](const std::string& why) {
-        ctx->last_error = "pbrt_hip_scene_set_material: " + why;
-        return PBRT_HIP_ERR_INVALID;
-    };
+    PB_EDIT(s, "pbrt_hip_scene_set_material");
     if (!desc) return invalid("null desc");
     if (material < 0 || material >= (int32_t)s->h_materials.size()) return invalid("material index out of range");
     DevMaterial m{};
     if (const char* why = row_of_desc(*desc, &m)) return invalid(why);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy((void*)(s->d.materials + material), &m, sizeof(DevMaterial), hipMemcpyHostToDevice));
-    s->h_materials[material] = m;
-    s->h_lobe_origin[material] = 0;
-    refresh_material_levels(s);
-    return PBRT_HIP_OK;
+    return write_material(s, material, m, 0);
 }
 PB_ABI_CATCH
 
 // pbrt-v3's DisneyMaterial without subsurface (include/pbrt_hip.h): row `material` becomes a kMatDisney row
-// and its DevDisney block (scene.h) gets the lobes' constants, computed here in double and rounded once. The shading kernels'
-// level-3 instantiations shade it (wf_disney.h).
+// and its DevDisney block (scene.h) gets the lobes' constants (host_edit.cpp). The shading kernels' level-3 instantiations
+// shade it (wf_disney.h). The block has no host copy: a kMatDisney row is what names it, and the row is written after it.
 extern "C" int pbrt_hip_scene_set_disney_material(PbrtHipScene* s, int32_t material, const PbrtDisneyDesc* desc) try {
-    if (!s) return PBRT_HIP_ERR_INVALID;
-    PbrtHipContext* ctx = s->ctx;
-    PB_ENTER(ctx);
-    auto invalid = [&](const std::string& why) {
-        ctx->last_error = "pbrt_hip_scene_set_disney_material: " + why;
-        return PBRT_HIP_ERR_INVALID;
-    };
+    PB_EDIT(s, "pbrt_hip_scene_set_disney_material");
     if (!desc) return invalid("null desc");
     if (material < 0 || material >= (int32_t)s->h_materials.size()) return invalid("material index out of range");
-    const PbrtDisneyDesc& p = *desc;
-    for (int k = 0; k < 3; ++k)
-        if (!std::isfinite(p.color[k]) || p.color[k] < 0.0f) return invalid("color must be finite and >= 0");
-    const struct {
-        const char* name;
-        float v, max;
-    } scalars[] = {{"metallic", p.metallic, 1.0f}, {"eta", p.eta, INFINITY}, {"roughness", p.roughness, 1.0f},
-                   {"specular_tint", p.specular_tint, 1.0f}, {"anisotropic", p.anisotropic, 1.0f}, {"sheen", p.sheen, INFINITY},
-                   {"sheen_tint", p.sheen_tint, 1.0f}, {"clearcoat", p.clearcoat, INFINITY}, {"clearcoat_gloss", p.clearcoat_gloss, 1.0f},
-                   {"spec_trans", p.spec_trans, 1.0f}, {"flatness", p.flatness, 1.0f}, {"diff_trans", p.diff_trans, 2.0f}};
-    for (const auto& sv : scalars) {
-        if (!std::isfinite(sv.v) || sv.v < 0.0f) return invalid(std::string(sv.name) + " must be finite and >= 0");
-        if (sv.v > sv.max) return invalid(std::string(sv.name) + (sv.max == 2.0f ? " must be <= 2" : " must be <= 1"));
-    }
-    if (!(p.eta > 0.0f)) return invalid("eta must be > 0");
-
-    const bool thin = p.thin != 0;
-    const double c[3] = {p.color[0], p.color[1], p.color[2]};
-    const double lum = 0.212671 * c[0] + 0.715160 * c[1] + 0.072169 * c[2];
-    const double metallic = p.metallic, eta = p.eta, rough = p.roughness, strans = p.spec_trans, flat = p.flatness;
-    const double dw = (1.0 - metallic) * (1.0 - strans), dt = p.diff_trans / 2.0;
-    const double aspect = std::sqrt(1.0 - 0.9 * p.anisotropic);
-    const double r0 = ((eta - 1.0) / (eta + 1.0)) * ((eta - 1.0) / (eta + 1.0));
-    auto lerp = [](double t, double a, double b) { return (1.0 - t) * a + t * b; };
-    DevDisney z{};
-    z.metallic = p.metallic;
-    z.eta = p.eta;
-    z.roughness = p.roughness;
-    z.ax = (float)std::max(1e-3, rough * rough / aspect);
-    z.ay = (float)std::max(1e-3, rough * rough * aspect);
-    z.tax = z.ax;
-    z.tay = z.ay;
-    z.sep_trans = thin ? 0 : 1;
-    z.lobes = kDzMicro;
-    if (dw > 0.0) z.lobes |= kDzDiffuse | kDzRetro | (thin ? kDzFakeSS : 0) | (p.sheen > 0.0f ? kDzSheen : 0);
-    if (p.clearcoat > 0.0f) z.lobes |= kDzClearcoat;
-    if (p.spec_trans > 0.0f) z.lobes |= kDzTrans;
-    if (thin) z.lobes |= kDzLambertT;
-    for (int k = 0; k < 3; ++k) {
-        const double tint = lum > 0.0 ? c[k] / lum : 1.0;
-        z.cspec0[k] = (float)lerp(metallic, r0 * lerp(p.specular_tint, 1.0, tint), c[k]);
-        if (z.lobes & kDzDiffuse) z.diffuse[k] = (float)(thin ? dw * (1.0 - flat) * (1.0 - dt) * c[k] : dw * c[k]);
-        if (z.lobes & kDzFakeSS) z.fakess[k] = (float)(dw * flat * (1.0 - dt) * c[k]);
-        if (z.lobes & kDzRetro) z.retro[k] = (float)(dw * c[k]);
-        if (z.lobes & kDzSheen) z.sheen[k] = (float)(dw * p.sheen * lerp(p.sheen_tint, 1.0, tint));
-        if (z.lobes & kDzTrans) z.trans[k] = (float)(strans * std::sqrt(c[k]));
-        if (z.lobes & kDzLambertT) z.lambert_t[k] = (float)(dt * c[k]);
-    }
-    {
-        const double g = lerp(p.clearcoat_gloss, 0.1, 0.001), a2 = g * g;
-        z.clearcoat = p.clearcoat;
-        z.cc_a2 = (float)a2;
-        z.cc_ln_a2 = (float)std::log(a2);
-        z.cc_norm = (float)((a2 - 1.0) / (3.14159265358979323846 * std::log(a2)));
-    }
-    if ((z.lobes & kDzTrans) && thin) {
-        const double rs = (0.65 * eta - 0.35) * rough;
-        z.tax = (float)std::max(1e-3, rs * rs / aspect);
-        z.tay = (float)std::max(1e-3, rs * rs * aspect);
-    }
-    z.n = __builtin_popcount((unsigned)z.lobes);
-    DevMaterial m{};
-    m.type = kMatDisney;
-    std::memcpy(m.kd, p.color, 12);
-    m.eta = p.eta;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy((void*)(s->d.disney + material), &z, sizeof(DevDisney), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy((void*)(s->d.materials + material), &m, sizeof(DevMaterial), hipMemcpyHostToDevice));
-    s->h_materials[material] = m;
-    s->h_lobe_origin[material] = 0;
-    refresh_material_levels(s);
-    return PBRT_HIP_OK;
+    DevDisney z;
+    DevMaterial m;
+    const std::string why = disney_of_desc(*desc, &z, &m);
+    if (!why.empty()) return invalid(why);
+    const DeviceWrite block{(void*)(s->d.disney + material), &z, nullptr, sizeof(DevDisney)};
+    return write_material(s, material, m, 0, &block);
 }
 PB_ABI_CATCH
 
@@ -960,191 +864,64 @@ PB_ABI_CATCH
 // kMatLobes row and its DevLobeRow (scene.h) gets the list host_lobes.cpp makes of the descriptor. The shading kernels' lobe-list
 // builds shade it (wf_lobes.h). A mix copies its operands' lists as they are now.
 extern "C" int pbrt_hip_scene_set_lobe_material(PbrtHipScene* s, int32_t material, const PbrtLobeMaterialDesc* desc) try {
-    if (!s) return PBRT_HIP_ERR_INVALID;
-    PbrtHipContext* ctx = s->ctx;
-    PB_ENTER(ctx);
-    auto invalid = [&](const std::string& why) {
-        ctx->last_error = "pbrt_hip_scene_set_lobe_material: " + why;
-        return PBRT_HIP_ERR_INVALID;
-    };
+    PB_EDIT(s, "pbrt_hip_scene_set_lobe_material");
     if (!desc) return invalid("null desc");
     if (material < 0 || material >= (int32_t)s->h_materials.size()) return invalid("material index out of range");
-    if (s->d.bvh.has_spheres == 2) return invalid("scenes with general quadric shapes take no lobe rows (their shading builds stay at level 3)");
-    if (s->light_maps) return invalid("scenes with a projection or goniometric light take no lobe rows (their shading builds stay at level 3)");
-    if (s->moving) return invalid("scenes with moving instances take no lobe rows");
-    LobeList la, lb, L;
-    if (desc->type == PBRT_LOBEMAT_MIX) {
-        const int32_t ops[2] = {desc->material_a, desc->material_b};
-        LobeList* lists[2] = {&la, &lb};
-        for (int k = 0; k < 2; ++k) {
-            const std::string name = k ? "material_b" : "material_a";
-            if (ops[k] < 0 || ops[k] >= (int32_t)s->h_materials.size()) return invalid(name + " out of range");
-            const DevMaterial& om = s->h_materials[ops[k]];
-            if (om.type == kMatLobes) {
-                if (s->h_lobe_origin[ops[k]] == PBRT_LOBEMAT_MIX) return invalid(name + " is a mix row");
-                const DevLobeRow& r = s->h_lobe_rows[ops[k]];
-                lists[k]->n = r.n;
-                lists[k]->eta = r.eta;
-                for (int i = 0; i < r.n; ++i) lists[k]->lobes[i] = r.lobes[i];
-            } else if (const char* why = lobes_of_row(om, lists[k])) {
-                return invalid(name + ": " + why);
-            }
-        }
-    }
-    if (const char* why = lobes_of_lobe_desc(*desc, &la, &lb, &L)) return invalid(why);
-    const DevLobeRow row = lobe_row_of(L);
-    DevMaterial m{};
-    m.type = kMatLobes;
-    m.eta = L.eta;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    HIP_TRY(ctx, hipMemcpy((void*)(s->d.lobe_rows + material), &row, sizeof(DevLobeRow), hipMemcpyHostToDevice));
-    HIP_TRY(ctx, hipMemcpy((void*)(s->d.materials + material), &m, sizeof(DevMaterial), hipMemcpyHostToDevice));
-    s->h_materials[material] = m;
+    DevLobeRow row;
+    DevMaterial m;
+    const std::string why = lobe_row_of_desc(*desc, {s->h_materials, s->h_lobe_rows, s->h_lobe_origin, s->d.bvh.has_spheres == 2, s->light_maps, s->moving}, &row, &m);
+    if (!why.empty()) return invalid(why);
+    const DeviceWrite block{(void*)(s->d.lobe_rows + material), &row, &s->h_lobe_rows[material], sizeof(DevLobeRow)};
+    if (int rc = write_material(s, material, m, desc->type, &block)) return rc;
     s->h_lobe_rows[material] = row;
-    s->h_lobe_origin[material] = desc->type;
-    refresh_material_levels(s);
     return PBRT_HIP_OK;
 }
 PB_ABI_CATCH
 
 // InfiniteAreaLight::new(light_to_world, L, n_samples, texmap) (lights/infinite.rs:36-82) with the texels in memory: the map's
-// tables (host_envmap.cpp) go to the device for light `light`, its power and the power distribution are recomputed, and a
-// spatial light table already built is dropped (the next render with that strategy builds it again).
+// tables (host_envmap.cpp) go to the device for light `light`, and its power and the power distribution are recomputed.
 extern "C" int pbrt_hip_scene_set_environment_map(PbrtHipScene* s, int32_t light, const float* rgb, int32_t width, int32_t height,
                                                   const float light_to_world[16]) try {
-    if (!s) return PBRT_HIP_ERR_INVALID;
-    PbrtHipContext* ctx = s->ctx;
-    PB_ENTER(ctx);
-    auto invalid = [&](const std::string& why) {
-        ctx->last_error = "pbrt_hip_scene_set_environment_map: " + why;
-        return PBRT_HIP_ERR_INVALID;
-    };
+    PB_EDIT(s, "pbrt_hip_scene_set_environment_map");
     if (light < 0 || light >= s->d.n_lights) return invalid("light index out of range");
     if (s->h_lights[light].type != PBRT_LIGHT_INFINITE) return invalid("light is not PBRT_LIGHT_INFINITE");
     if (!light_to_world) return invalid("null light_to_world");
-    const float* m = light_to_world;
-    for (int k = 0; k < 16; ++k)
-        if (!std::isfinite(m[k])) return invalid("light_to_world is not finite");
-    if (m[12] != 0.0f || m[13] != 0.0f || m[14] != 0.0f || m[15] != 1.0f) return invalid("light_to_world's last row is not (0, 0, 0, 1)");
-    // world_to_light's directions: the inverse of the upper 3x3, in double
-    double a[9];
-    for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) a[3 * r + c] = m[4 * r + c];
-    double inv[9] = {a[4] * a[8] - a[5] * a[7], a[2] * a[7] - a[1] * a[8], a[1] * a[5] - a[2] * a[4],
-                     a[5] * a[6] - a[3] * a[8], a[0] * a[8] - a[2] * a[6], a[2] * a[3] - a[0] * a[5],
-                     a[3] * a[7] - a[4] * a[6], a[1] * a[6] - a[0] * a[7], a[0] * a[4] - a[1] * a[3]};
-    double det = a[0] * inv[0] + a[1] * inv[3] + a[2] * inv[6];
     DevEnvMap e{};
-    for (int k = 0; k < 9; ++k) {
-        e.l2w[k] = (float)a[k];
-        e.w2l[k] = det != 0.0 ? (float)(inv[k] / det) : 0.0f;
-        if (det == 0.0 || !std::isfinite(e.w2l[k])) return invalid("light_to_world is singular");
-    }
+    if (const char* why = envmap_transform(light_to_world, &e)) return invalid(why);
     EnvTables t;
     if (const char* why = envmap_build(rgb, width, height, s->h_lights[light].L, &t)) return invalid(why);
 
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<void*> fresh;
-    auto release = [&]() {
-        for (void* p : fresh) (void)hipFree(p);
-    };
-    auto upload = [&](const void* src, size_t bytes) -> void* {
-        void* p = nullptr;
-        if (!hip_ok(ctx, hipMalloc(&p, bytes), "hipMalloc environment map")) return nullptr;
-        fresh.push_back(p);
-        if (!hip_ok(ctx, hipMemcpy(p, src, bytes, hipMemcpyHostToDevice), "hipMemcpy environment map")) return nullptr;
-        return p;
-    };
-    std::vector<float4> texels((size_t)t.w * t.h);
-    for (size_t i = 0; i < texels.size(); ++i) texels[i] = make_float4(t.level0[3 * i], t.level0[3 * i + 1], t.level0[3 * i + 2], 0.0f);
-    e.texels = (const float4*)upload(texels.data(), texels.size() * sizeof(float4));
-    e.func = e.texels ? (const float*)upload(t.func.data(), t.func.size() * sizeof(float)) : nullptr;
-    e.cdf = e.func ? (const float*)upload(t.cdf.data(), t.cdf.size() * sizeof(float)) : nullptr;
-    e.row_int = e.cdf ? (const float*)upload(t.row_int.data(), t.row_int.size() * sizeof(float)) : nullptr;
-    e.marg_cdf = e.row_int ? (const float*)upload(t.marg_cdf.data(), t.marg_cdf.size() * sizeof(float)) : nullptr;
-    if (!e.marg_cdf) {
-        release();
-        return PBRT_HIP_ERR_DEVICE;
-    }
+    SceneEdit edit{s};
+    if (int rc = edit.begin()) return rc;
+    e.texels = edit.upload(texels_of_rgb(t.level0));
+    e.func = edit.upload(t.func);
+    e.cdf = edit.upload(t.cdf);
+    e.row_int = edit.upload(t.row_int);
+    e.marg_cdf = edit.upload(t.marg_cdf);
     e.marg_int = t.marg_int;
     e.w = t.w;
     e.h = t.h;
     e.nu = t.nu;
     e.nv = t.nv;
-    const int n = s->d.n_lights;
-    if (!s->d.env_maps) {
-        void* p = nullptr;
-        if (!hip_ok(ctx, hipMalloc(&p, (size_t)n * sizeof(DevEnvMap)), "hipMalloc environment maps")) {
-            release();
-            return PBRT_HIP_ERR_DEVICE;
-        }
-        s->allocs.push_back(p);
-        s->d.env_maps = (const DevEnvMap*)p;
-        s->h_env.assign(n, DevEnvMap{});
-        s->env_allocs.assign(n, {});
+    if (edit.uploaded && !s->d.env_maps) {  // the scene's first map: the descriptors, one per light
+        s->h_env.assign(s->d.n_lights, DevEnvMap{});
+        s->d.env_maps = dev_upload(s, s->h_env.data(), s->h_env.size(), &edit.uploaded);
     }
-    // the light itself: its map, and InfiniteAreaLight::power (infinite.rs:131-133) for the power distribution
+    if (!edit.uploaded) return PBRT_HIP_ERR_DEVICE;
     DevLight lt = s->h_lights[light];
     lt.slot = light;
-    const float scale = kPi * s->d.world_radius * s->d.world_radius;
-    float p[3] = {t.power_rgb[0] * scale, t.power_rgb[1] * scale, t.power_rgb[2] * scale};
-    lt.power_y = 0.212671f * p[0] + 0.715160f * p[1] + 0.072169f * p[2];
-    std::vector<float> power_y(n), cdf;
-    for (int i = 0; i < n; ++i) power_y[i] = i == light ? lt.power_y : s->h_lights[i].power_y;
-    float fi;
-    make_distribution(power_y, &cdf, &fi);
-    std::vector<DevEnvMap> h_env = s->h_env;
-    h_env[light] = e;
-    std::vector<float> old_power_y(n), old_cdf;
-    for (int i = 0; i < n; ++i) old_power_y[i] = s->h_lights[i].power_y;
-    float old_fi;
-    make_distribution(old_power_y, &old_cdf, &old_fi);
-    // the device copies of the descriptors, the light and the power distribution, from one consistent host state
-    auto write_state = [&](const std::vector<DevEnvMap>& env, const DevLight& l, const std::vector<float>& py, const std::vector<float>& pc) {
-        return hip_ok(ctx, hipMemcpy((void*)s->d.env_maps, env.data(), (size_t)n * sizeof(DevEnvMap), hipMemcpyHostToDevice), "hipMemcpy") &&
-               hip_ok(ctx, hipMemcpy((void*)(s->d.lights + light), &l, sizeof(DevLight), hipMemcpyHostToDevice), "hipMemcpy") &&
-               hip_ok(ctx, hipMemcpy((void*)s->d.light_distrib_power.func, py.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy") &&
-               hip_ok(ctx, hipMemcpy((void*)s->d.light_distrib_power.cdf, pc.data(), (size_t)(n + 1) * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy");
-    };
-    if (!write_state(h_env, lt, power_y, cdf)) {
-        // put the previous state back; if that fails as well the device may still point at the new arrays: they then stay
-        // allocated until the scene is destroyed instead of being freed under a descriptor that names them
-        std::string why = ctx->last_error;
-        if (write_state(s->h_env, s->h_lights[light], old_power_y, old_cdf)) {
-            release();
-        } else {
-            s->allocs.insert(s->allocs.end(), fresh.begin(), fresh.end());
-        }
-        ctx->last_error = why;
-        return PBRT_HIP_ERR_DEVICE;
-    }
-    s->d.light_distrib_power.func_int = fi;
-    for (void* q : s->env_allocs[light]) (void)hipFree(q);  // a map set before on this light
-    s->env_allocs[light].swap(fresh);
-    s->h_env.swap(h_env);
-    s->h_lights[light] = lt;
-    if (s->d_spatial) {
-        (void)hipFree(s->d_spatial);
-        s->allocs.erase(std::remove(s->allocs.begin(), s->allocs.end(), (void*)s->d_spatial), s->allocs.end());
-        s->d_spatial = nullptr;
-    }
+    lt.power_y = envmap_power_y(t, s->d.world_radius);
+    if (int rc = write_light(edit, light, lt, {(void*)(s->d.env_maps + light), &e, &s->h_env[light], sizeof(DevEnvMap)})) return rc;
+    s->h_env[light] = e;
     return PBRT_HIP_OK;
 }
 PB_ABI_CATCH
 
 // ProjectionLight::new / GonioPhotometricLight::new (lights/projection.rs:36-88, goniometric.rs:32-63) with the texels in memory:
-// level 0 of the map's MIPMap goes to the device for light `light`, the projector's window follows the map's aspect, the light's
-// power (D89) and the power distribution are recomputed, and a spatial light table already built is dropped.
+// level 0 of the map's MIPMap goes to the device for light `light`, the projector's window follows the map's aspect, and the
+// light's power (D89) and the power distribution are recomputed.
 extern "C" int pbrt_hip_scene_set_light_map(PbrtHipScene* s, int32_t light, const float* rgb, int32_t width, int32_t height) try {
-    if (!s) return PBRT_HIP_ERR_INVALID;
-    PbrtHipContext* ctx = s->ctx;
-    PB_ENTER(ctx);
-    auto invalid = [&](const std::string& why) {
-        ctx->last_error = "pbrt_hip_scene_set_light_map: " + why;
-        return PBRT_HIP_ERR_INVALID;
-    };
+    PB_EDIT(s, "pbrt_hip_scene_set_light_map");
     if (light < 0 || light >= s->d.n_lights) return invalid("light index out of range");
     const int type = s->h_lights[light].type;
     if (type != PBRT_LIGHT_PROJECTION && type != PBRT_LIGHT_GONIOMETRIC) return invalid("light is not PBRT_LIGHT_PROJECTION or PBRT_LIGHT_GONIOMETRIC");
@@ -1152,62 +929,20 @@ extern "C" int pbrt_hip_scene_set_light_map(PbrtHipScene* s, int32_t light, cons
     LightMapTables t;
     if (const char* why = light_map_build(type, s->light_fov[light], rgb, width, height, &t)) return invalid(why);
 
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    std::vector<float4> texels((size_t)t.w * t.h);
-    for (size_t i = 0; i < texels.size(); ++i) texels[i] = make_float4(t.level0[3 * i], t.level0[3 * i + 1], t.level0[3 * i + 2], 0.0f);
-    void* fresh = nullptr;
-    if (!hip_ok(ctx, hipMalloc(&fresh, texels.size() * sizeof(float4)), "hipMalloc light map")) return PBRT_HIP_ERR_DEVICE;
-    if (!hip_ok(ctx, hipMemcpy(fresh, texels.data(), texels.size() * sizeof(float4), hipMemcpyHostToDevice), "hipMemcpy light map")) {
-        (void)hipFree(fresh);
-        return PBRT_HIP_ERR_DEVICE;
-    }
+    SceneEdit edit{s};
+    if (int rc = edit.begin()) return rc;
     DevLightMap m{};
-    m.texels = (const float4*)fresh;
+    m.texels = edit.upload(texels_of_rgb(t.level0));
+    if (!edit.uploaded) return PBRT_HIP_ERR_DEVICE;
     m.w = t.w;
     m.h = t.h;
     m.inv_tan = t.inv_tan;
     std::memcpy(m.screen_bounds, t.screen_bounds, sizeof(m.screen_bounds));
-    // the light itself: its power for the power distribution
-    const int n = s->d.n_lights;
     DevLight lt = s->h_lights[light];
     if (type == PBRT_LIGHT_PROJECTION) lt.cos_total_width = t.cos_total_width;
-    float p[3] = {lt.L[0] * t.power_rgb[0], lt.L[1] * t.power_rgb[1], lt.L[2] * t.power_rgb[2]};
-    lt.power_y = 0.212671f * p[0] + 0.715160f * p[1] + 0.072169f * p[2];
-    std::vector<float> power_y(n), cdf, old_power_y(n), old_cdf;
-    for (int i = 0; i < n; ++i) {
-        old_power_y[i] = s->h_lights[i].power_y;
-        power_y[i] = i == light ? lt.power_y : old_power_y[i];
-    }
-    float fi, old_fi;
-    make_distribution(power_y, &cdf, &fi);
-    make_distribution(old_power_y, &old_cdf, &old_fi);
-    // the device copies of the descriptor, the light and the power distribution, from one consistent host state
-    auto write_state = [&](const DevLightMap& dm, const DevLight& l, const std::vector<float>& py, const std::vector<float>& pc) {
-        return hip_ok(ctx, hipMemcpy((void*)(s->d.light_maps + light), &dm, sizeof(DevLightMap), hipMemcpyHostToDevice), "hipMemcpy") &&
-               hip_ok(ctx, hipMemcpy((void*)(s->d.lights + light), &l, sizeof(DevLight), hipMemcpyHostToDevice), "hipMemcpy") &&
-               hip_ok(ctx, hipMemcpy((void*)s->d.light_distrib_power.func, py.data(), (size_t)n * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy") &&
-               hip_ok(ctx, hipMemcpy((void*)s->d.light_distrib_power.cdf, pc.data(), (size_t)(n + 1) * sizeof(float), hipMemcpyHostToDevice), "hipMemcpy");
-    };
-    if (!write_state(m, lt, power_y, cdf)) {
-        // put the previous state back; if that fails as well the device may still point at the new texels: they then stay
-        // allocated until the scene is destroyed instead of being freed under a descriptor that names them
-        std::string why = ctx->last_error;
-        if (write_state(s->h_light_maps[light], s->h_lights[light], old_power_y, old_cdf)) (void)hipFree(fresh);
-        else s->allocs.push_back(fresh);
-        ctx->last_error = why;
-        return PBRT_HIP_ERR_DEVICE;
-    }
-    s->d.light_distrib_power.func_int = fi;
-    if (s->light_map_allocs[light]) (void)hipFree(s->light_map_allocs[light]);  // a map set before on this light
-    s->light_map_allocs[light] = fresh;
+    lt.power_y = light_map_power_y(t, lt.L);
+    if (int rc = write_light(edit, light, lt, {(void*)(s->d.light_maps + light), &m, &s->h_light_maps[light], sizeof(DevLightMap)})) return rc;
     s->h_light_maps[light] = m;
-    s->h_lights[light] = lt;
-    if (s->d_spatial) {
-        (void)hipFree(s->d_spatial);
-        s->allocs.erase(std::remove(s->allocs.begin(), s->allocs.end(), (void*)s->d_spatial), s->allocs.end());
-        s->d_spatial = nullptr;
-    }
     return PBRT_HIP_OK;
 }
 PB_ABI_CATCH

@@ -1,4 +1,5 @@
-// scene.h — context / scene objects behind the C ABI and the host->device re-layout.
+// scene.h — context / scene objects behind the C ABI and the device tables' rows. The tables are laid out on the host by
+// host_scene.cpp (creation) and host_edit.cpp (the pbrt_hip_scene_set_* edits); pbrt_hip.hip puts them on the device.
 //
 // Scene::new (src/core/scene.rs:18-34) + GeometricPrimitive (src/core/primitive.rs:33-55) +
 // BVHAccel's flat node array (src/accelerators/bvh.rs:129-135, 774-811), re-laid out for the
@@ -108,7 +109,7 @@ struct DevMaterial {
 // OrenNayar's A / B in alpha_u / alpha_v; kMatRoughGlass: kd = Kr, kt = Kt, eta, the alphas; kMatSubstrate: kd, kt = Ks, the alphas
 constexpr int kMatOrenNayar = 6, kMatRoughGlass = 7, kMatSubstrate = 8;
 // kMatDisney: a row of pbrt_hip_scene_set_disney_material (wf_disney.h). The DevMaterial row keeps the colour in kd and eta; what
-// the lobes read is the DevDisney block of the same index in DevSceneData::disney, computed on the host in double and rounded once.
+// the lobes read is the DevDisney block of the same index in DevSceneData::disney, computed on the host in double and rounded once (host_edit.cpp).
 constexpr int kMatDisney = 9;
 // DevDisney::lobes, in the order DisneyMaterial adds them (BSDF::sample_f picks a lobe by index)
 constexpr int kDzDiffuse = 1, kDzFakeSS = 2, kDzRetro = 4, kDzSheen = 8, kDzMicro = 16, kDzClearcoat = 32, kDzTrans = 64, kDzLambertT = 128;
@@ -220,12 +221,11 @@ struct PbrtHipScene {
     std::vector<int> h_lobe_origin;           // per row: the PbrtLobeMaterialType that wrote it, 0 for any other row
     bool light_maps = false;  // a projection or goniometric light in the table: the shading kernels' map-light builds run
     std::vector<pb::DevLightMap> h_light_maps;  // the device table's host copy
-    std::vector<void*> light_map_allocs;         // per light: its texels on the device (pbrt_hip_scene_set_light_map) or null
     std::vector<float> light_fov;                // per light: PbrtLight.fov (projection)
     std::vector<int> light_samples;  // max(1, n_samples) per light (light.rs:76)
-    // image maps of infinite lights (pbrt_hip_scene_set_environment_map): per light its descriptor and its device arrays
-    std::vector<pb::DevEnvMap> h_env;
-    std::vector<std::vector<void*>> env_allocs;
+    std::vector<pb::DevEnvMap> h_env;  // image maps of infinite lights (pbrt_hip_scene_set_environment_map): the descriptors' host copy
+    // per light: the device arrays of its map (an infinite light's five, a projection / goniometric light's texels), to hipFree
+    std::vector<std::vector<void*>> light_allocs;
     // SpatialLightDistribution tables (lightdistrib.rs:76-220), built on first use by a render with that strategy
     float* d_spatial = nullptr;
     int spatial_voxels[3] = {0, 0, 0};

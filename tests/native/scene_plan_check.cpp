@@ -270,7 +270,7 @@ void make_two_level(Scene* s, bool moving) {
         mo.end_time = 1.0f;
         mo.animated = 1;
     }
-    // the combined mesh, as pbrt_hip.hip's create_two_level lays it out: object after object, then the world triangles
+    // the combined mesh, as combine_two_level lays it out (scene_edit_check.cpp holds it to that): object after object, then the world triangles
     const float wpos[12] = {-1, 2, -1, 1, 2, -1, 1, 2, 1, -1, 2, 1};
     const int32_t widx[6] = {0, 1, 2, 0, 2, 3};
     pb::InstancingArgs& ia = s->desc.ia;

@@ -472,6 +472,45 @@ int pbrt_hip_material_lobes(const PbrtMaterial* row, const PbrtMaterialDesc* des
  * 16 specular); all 0 when nothing was sampled. Host buffers; any output may be NULL. n = 0 is a no-op. */
 int pbrt_hip_bsdf_query(PbrtHipScene* scene, int32_t material, int64_t n, const float* wo, const float* wi, const float* u, float* f,
                         float* pdf, float* wi_s, float* f_s, float* pdf_s, int32_t* sampled_flags);
+/* pbrt-v3's HairMaterial: the fibre BSDF of Chiang et al. (HairBSDF: lobes R, TT, TRT and a residual, pMax = 3) on the curve
+ * segments of a scene made by pbrt_hip_scene_create_with_curves. pbrt_hip_scene_set_hair_material replaces row `material`; any
+ * other setter replaces a hair row in turn. x of the shading frame runs along the fibre (normalize(shading.dpdu)) and
+ * h = -1 + 2 v of the curve's hit. Every parameter is a constant of the row; `absorption` says which of the three
+ * parametrisations is read:
+ *   PBRT_HAIR_SIGMA_A  sigma_a
+ *   PBRT_HAIR_COLOR    sigma_a = (log(color) / (5.969 - 0.215 bn + 2.532 bn^2 - 10.73 bn^3 + 5.574 bn^4 + 0.245 bn^5))^2
+ *   PBRT_HAIR_MELANIN  sigma_a = eumelanin (0.419, 0.697, 1.37) + pheomelanin (0.187, 0.4, 1.05)
+ * pbrt-v3's defaults: eumelanin 1.3, eta 1.55, beta_m = beta_n = 0.3, alpha 2 (degrees). The one lobe is glossy, reflecting and
+ * transmitting and never specular. Two of pbrt-v3's closed forms are replaced by longer ones, because with
+ * them a white fibre loses up to 0.7 % of its energy: I0 has twenty terms and log I0 three terms of its asymptotic series (D112),
+ * so values differ from pbrt-v3's by up to that much at beta_m near 0.3. beta_m = 0, beta_n = 0 and eta < 1 are accepted as
+ * pbrt-v3 accepts them and give undefined (not finite) values where pbrt-v3's formulas divide by zero (D113). PBRT_HIP_ERR_INVALID (pbrt_hip_last_error says why, the scene unchanged)
+ * for a null descriptor, a row out of range, a field that is not finite, beta_m or beta_n outside [0, 1], eta <= 0, a negative
+ * sigma_a or melanin, a colour outside (0, 1], an unknown `absorption`, a scene without curves, and a row that a triangle or a
+ * quadric shape names (a triangle has no v here). A hair row is refused as an operand of a mix, by
+ * pbrt_hip_scene_set_material_roughness and by pbrt_hip_bsdf_query (pbrt_hip_bsdf_query_hair takes the h it needs). */
+enum PbrtHairAbsorption { PBRT_HAIR_SIGMA_A = 0, PBRT_HAIR_COLOR = 1, PBRT_HAIR_MELANIN = 2 };
+typedef struct PbrtHairDesc {
+    int32_t absorption; /* PbrtHairAbsorption */
+    float sigma_a[3], color[3], eumelanin, pheomelanin, eta, beta_m, beta_n, alpha;
+} PbrtHairDesc;
+int pbrt_hip_scene_set_hair_material(PbrtHipScene* scene, int32_t material, const PbrtHairDesc* desc);
+/* What the scene's tables ask of the shading kernels right now, as the render driver reads it when it picks their builds
+ * (csrc/kernel_select.h: SceneNeeds): out[0] general quadric shapes, out[1] a projection or goniometric light, out[2] the
+ * material level (0 matte / mirror / glass, 1 plastic or metal, 2 a pbrt_hip_scene_set_material row, 3 a Disney row), out[3] a
+ * lobe row, out[4] moving instances, out[5] curve segments, out[6] a hair row (with out[5]: the hair builds run), out[7] 0. */
+int pbrt_hip_scene_shading_needs(const PbrtHipScene* scene, int32_t out[8]);
+/* The constants of a hair row as the device holds them, on the host, without a context or a GPU: computed in double and rounded
+ * once per field. v: the longitudinal variances of p = 0, 1, 2 and of the residual; s: the azimuthal logistic's scale;
+ * sin2k / cos2k: sine and cosine of alpha, 2 alpha and 4 alpha. PBRT_HIP_ERR_INVALID with *reason set (reason may be NULL) for
+ * what the setter refuses and can be seen here. */
+typedef struct PbrtHairTables {
+    float sigma_a[3], eta, v[4], s, sin2k[3], cos2k[3];
+} PbrtHairTables;
+int pbrt_hip_hair_tables(const PbrtHairDesc* desc, PbrtHairTables* out, const char** reason);
+/* pbrt_hip_bsdf_query for a hair row: h[i] in [-1, 1] is the offset across the fibre of point i, x of the frame runs along it. */
+int pbrt_hip_bsdf_query_hair(PbrtHipScene* scene, int32_t material, int64_t n, const float* h, const float* wo, const float* wi,
+                             const float* u, float* f, float* pdf, float* wi_s, float* f_s, float* pdf_s, int32_t* sampled_flags);
 /* Scene with spheres next to the triangles (src/shapes/sphere.rs:38-92, 228-284 with src/core/efloat.rs; BASELINE
  * config 1): n_spheres full spheres {centre.xyz, radius}, i.e. Sphere::new with object_to_world = translate(centre).
  * Sphere i is primitive n_tris + i in prim_order; nodes come from pbrt_hip_bvh_build_boxes over the primitives' world

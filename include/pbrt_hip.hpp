@@ -574,10 +574,37 @@ public:
         aggregate_->context()->check(pbrt_hip_scene_set_light_map(aggregate_->handle(), light, rgb.data(), width, height),
                                      "Scene::set_light_map");
     }
+    // pbrt-v3's HairMaterial on row `material` of a scene with curves (include/pbrt_hip.h: pbrt_hip_scene_set_hair_material):
+    // only curves may name the row; pbrt::hair() below gives the descriptor
+    void set_hair_material(int32_t material, const PbrtHairDesc& desc) {
+        aggregate_->context()->check(pbrt_hip_scene_set_hair_material(aggregate_->handle(), material, &desc), "Scene::set_hair_material");
+    }
 
 private:
     std::shared_ptr<BVHAccel> aggregate_;
 };
+
+// HairMaterial's parameters with pbrt-v3's defaults and its precedence among the three ways to give the absorption: sigma_a, then
+// color, then the melanin concentrations; none given: eumelanin 1.3. A null pointer or a negative concentration means "not given".
+inline PbrtHairDesc hair(const Float* sigma_a = nullptr, const Float* color = nullptr, Float eumelanin = -1, Float pheomelanin = -1,
+                         Float eta = 1.55f, Float beta_m = 0.3f, Float beta_n = 0.3f, Float alpha = 2.0f) {
+    PbrtHairDesc d{};
+    d.absorption = PBRT_HAIR_MELANIN;
+    d.eta = eta, d.beta_m = beta_m, d.beta_n = beta_n, d.alpha = alpha;
+    if (sigma_a) {
+        d.absorption = PBRT_HAIR_SIGMA_A;
+        for (int k = 0; k < 3; ++k) d.sigma_a[k] = sigma_a[k];
+    } else if (color) {
+        d.absorption = PBRT_HAIR_COLOR;
+        for (int k = 0; k < 3; ++k) d.color[k] = color[k];
+    } else if (eumelanin >= 0 || pheomelanin >= 0) {
+        d.eumelanin = eumelanin >= 0 ? eumelanin : 0;
+        d.pheomelanin = pheomelanin >= 0 ? pheomelanin : 0;
+    } else {
+        d.eumelanin = 1.3f;
+    }
+    return d;
+}
 
 struct Vector2f {
     Float x = 0, y = 0;

@@ -4,11 +4,13 @@
 
 #include <cstring>
 
+#include "abi_guard.h"
 #include "host_scene.h"
 
 namespace pb {
 
 const char* roughness_row(const DevMaterial& m, float u, float v, bool remap, DevMaterial* out) {
+    if (m.type == kMatHair) return "a hair row has no roughness: pbrt_hip_scene_set_hair_material sets beta_m and beta_n";
     if (m.type != PBRT_MAT_PLASTIC && m.type != PBRT_MAT_METAL) return "material is not PBRT_MAT_PLASTIC or PBRT_MAT_METAL";
     if (const char* why = roughness_invalid(u, v, remap)) return why;
     if (m.type == PBRT_MAT_PLASTIC && u != v) return "plastic is isotropic: u_roughness must equal v_roughness";
@@ -82,6 +84,69 @@ std::string disney_of_desc(const PbrtDisneyDesc& p, DevDisney* block, DevMateria
     DevMaterial m{};
     m.type = kMatDisney;
     std::memcpy(m.kd, p.color, 12);
+    m.eta = p.eta;
+    *block = z;
+    *row = m;
+    return "";
+}
+
+std::string hair_of_desc(const PbrtHairDesc& p, DevHair* block, DevMaterial* row) {
+    const float fields[] = {p.sigma_a[0], p.sigma_a[1], p.sigma_a[2], p.color[0], p.color[1], p.color[2], p.eumelanin, p.pheomelanin,
+                            p.eta, p.beta_m, p.beta_n, p.alpha};
+    for (float f : fields)
+        if (!std::isfinite(f)) return "every field must be finite";
+    if (p.beta_m < 0.0f || p.beta_m > 1.0f) return "beta_m must be in [0, 1]";
+    if (p.beta_n < 0.0f || p.beta_n > 1.0f) return "beta_n must be in [0, 1]";
+    if (!(p.eta > 0.0f)) return "eta must be > 0";
+    const double bm = p.beta_m, bn = p.beta_n, pi = 3.14159265358979323846;
+    double sigma_a[3];
+    if (p.absorption == PBRT_HAIR_SIGMA_A) {
+        for (int k = 0; k < 3; ++k) {
+            if (p.sigma_a[k] < 0.0f) return "sigma_a must be >= 0";
+            sigma_a[k] = p.sigma_a[k];
+        }
+    } else if (p.absorption == PBRT_HAIR_COLOR) {
+        const double d = 5.969 - 0.215 * bn + 2.532 * std::pow(bn, 2) - 10.73 * std::pow(bn, 3) + 5.574 * std::pow(bn, 4) + 0.245 * std::pow(bn, 5);
+        for (int k = 0; k < 3; ++k) {
+            if (!(p.color[k] > 0.0f && p.color[k] <= 1.0f)) return "color must be in (0, 1]";
+            const double q = std::log((double)p.color[k]) / d;
+            sigma_a[k] = q * q;
+        }
+    } else if (p.absorption == PBRT_HAIR_MELANIN) {
+        if (p.eumelanin < 0.0f || p.pheomelanin < 0.0f) return "eumelanin and pheomelanin must be >= 0";
+        const double eu[3] = {0.419, 0.697, 1.37}, ph[3] = {0.187, 0.4, 1.05};
+        for (int k = 0; k < 3; ++k) sigma_a[k] = (double)p.eumelanin * eu[k] + (double)p.pheomelanin * ph[k];
+    } else {
+        return "unknown absorption (PBRT_HAIR_SIGMA_A, PBRT_HAIR_COLOR or PBRT_HAIR_MELANIN)";
+    }
+    DevHair z{};
+    for (int k = 0; k < 3; ++k) z.sigma_a[k] = (float)sigma_a[k];
+    z.eta = p.eta;
+    const double q = 0.726 * bm + 0.812 * bm * bm + 3.7 * std::pow(bm, 20);
+    const double v0 = q * q;
+    z.v[0] = (float)v0;
+    z.v[1] = (float)(0.25 * v0);
+    z.v[2] = (float)(4.0 * v0);
+    z.v[3] = z.v[2];
+    const double s = std::sqrt(pi / 8.0) * (0.265 * bn + 1.194 * bn * bn + 5.372 * std::pow(bn, 22));
+    z.s = (float)s;
+    double sk[3], ck[3];
+    sk[0] = std::sin((double)p.alpha * (pi / 180.0));
+    ck[0] = std::sqrt(std::max(0.0, 1.0 - sk[0] * sk[0]));
+    for (int i = 1; i < 3; ++i) {
+        sk[i] = 2.0 * ck[i - 1] * sk[i - 1];
+        ck[i] = ck[i - 1] * ck[i - 1] - sk[i - 1] * sk[i - 1];
+    }
+    for (int i = 0; i < 3; ++i) {
+        z.sin2k[i] = (float)sk[i];
+        z.cos2k[i] = (float)ck[i];
+    }
+    // the trimmed logistic over [-pi, pi]: at s == 0 (beta_n == 0) the cdfs are 0 and 1
+    const double lo = s > 0.0 ? 1.0 / (1.0 + std::exp(pi / s)) : 0.0, hi = s > 0.0 ? 1.0 / (1.0 + std::exp(-pi / s)) : 1.0;
+    z.cdf_lo = (float)lo;
+    z.trim_k = (float)(hi - lo);
+    DevMaterial m{};
+    m.type = kMatHair;
     m.eta = p.eta;
     *block = z;
     *row = m;
@@ -170,3 +235,24 @@ PowerEdit power_edit(const std::vector<DevLight>& lights, int n, int light, floa
 }
 
 }  // namespace pb
+
+// the constants of a hair row without a scene (include/pbrt_hip.h)
+extern "C" int pbrt_hip_hair_tables(const PbrtHairDesc* desc, PbrtHairTables* out, const char** reason) try {
+    static thread_local std::string why;
+    if (reason) *reason = nullptr;
+    pb::DevHair z;
+    pb::DevMaterial m;
+    why = (desc && out) ? pb::hair_of_desc(*desc, &z, &m) : std::string("null pointer");
+    if (!why.empty()) {
+        if (reason) *reason = why.c_str();
+        return PBRT_HIP_ERR_INVALID;
+    }
+    std::memcpy(out->sigma_a, z.sigma_a, 12);
+    out->eta = z.eta;
+    std::memcpy(out->v, z.v, 16);
+    out->s = z.s;
+    std::memcpy(out->sin2k, z.sin2k, 12);
+    std::memcpy(out->cos2k, z.cos2k, 12);
+    return PBRT_HIP_OK;
+}
+PB_ABI_CATCH

@@ -18,6 +18,11 @@ const char* roughness_row(const DevMaterial& m, float u, float v, bool remap, De
 // field, and the kMatDisney row that names them. The refusal, or an empty string.
 std::string disney_of_desc(const PbrtDisneyDesc& p, DevDisney* block, DevMaterial* row);
 
+// pbrt-v3's HairMaterial: the absorption of the chosen parametrisation and the lobes' constants, computed in
+// double and rounded once per field, and the kMatHair row that names them. The refusal, or an empty string. (What depends on the
+// scene — it holds curves, and only curves name the row — is the setter's to check.)
+std::string hair_of_desc(const PbrtHairDesc& p, DevHair* block, DevMaterial* row);
+
 // The material tables' host copies as pbrt_hip_scene_set_lobe_material reads them: a mix copies its operands' lists as they are now
 struct LobeTables {
     const std::vector<DevMaterial>& materials;

@@ -184,6 +184,7 @@ const char* lobes_of_row(const DevMaterial& m, LobeList* out) {
             }
             break;
         case kMatDisney: return "a Disney row has no lobe list";
+        case kMatHair: return "a hair row has no lobe list";
         default: return "a lobe row is not an operand";
     }
     *out = L;

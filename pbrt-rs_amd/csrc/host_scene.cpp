@@ -781,6 +781,11 @@ void plan_scene(const SceneDesc& desc, ScenePlan* plan) {
     plan->curves.resize(desc.n_curves);
     for (int32_t i = 0; i < desc.n_curves; ++i) plan->curves[i] = curve_row(desc.curves[i]);
     d.n_curves = desc.n_curves;
+    if (desc.n_curves > 0) {  // the rows a hair material may not take: those a triangle or a quadric shape names
+        plan->row_off_curve.assign(desc.n_materials, 0);
+        for (int32_t i = 0; i < desc.n_tris; ++i) plan->row_off_curve[desc.tri_material ? desc.tri_material[i] : 0] = 1;
+        for (int32_t i = 0; i < desc.sa.n_shapes; ++i) plan->row_off_curve[desc.sa.shapes[i].material] = 1;
+    }
     plan->shapes.resize(desc.sa.n_shapes);
     for (int32_t i = 0; i < desc.sa.n_shapes; ++i) plan->shapes[i] = shape_row(desc.sa.shapes[i]);
     d.bvh.instanced = desc.instanced() ? 1 : 0;

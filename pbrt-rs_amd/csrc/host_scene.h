@@ -134,6 +134,7 @@ struct ScenePlan {
     std::vector<int32_t> prim_slot;  // primitive -> leaf slot
     std::vector<DevShape> shapes;    // theta_min / theta_max are k_shape_angles'
     std::vector<DevCurve> curves;    // one row per curve record
+    std::vector<uint8_t> row_off_curve;  // scenes with curves, per material row: a triangle or a quadric shape names it
     std::vector<DevLight> lights;    // max(1, n_lights) rows
     std::vector<int> infinite_ids;
     std::vector<DevMaterial> materials;

@@ -111,10 +111,11 @@ struct SceneNeeds {
                       // or lobes: creation and the setters refuse)
     bool curves;      // curve segments (DevSceneData::curves): the builds that rebuild a curve's surface from the ray (with shapes set:
                       // they are the builds for shapes with that added)
+    bool hair;        // a row of pbrt_hip_scene_set_hair_material (only in a scene with curves: the setter refuses): the hair builds
     int column() const { return shapes ? 0 : light_maps ? 1 : 5 - level; }  // of the tables below: in that precedence, most general first
 };
 inline SceneNeeds scene_needs(const PbrtHipScene* s) {
-    return SceneNeeds{s->d.bvh.has_spheres == 2, s->light_maps, s->disney ? 3 : s->bxdfs ? 2 : s->glossy ? 1 : 0, s->lobes, s->moving, s->d.curves != nullptr};
+    return SceneNeeds{s->d.bvh.has_spheres == 2, s->light_maps, s->disney ? 3 : s->bxdfs ? 2 : s->glossy ? 1 : 0, s->lobes, s->moving, s->d.curves != nullptr, s->hair};
 }
 
 #ifdef PB_SELECT_SHADING_KERNELS
@@ -123,6 +124,7 @@ using PathKernel = void (*)(ShadeConsts, PathState, Queues, Queues, PassParams, 
 using SpatialKernel = void (*)(ShadeConsts, float*);
 }  // namespace pb
 #include "curve_kernels.h"
+#include "hair_kernels.h"
 namespace pb {
 // The tables list every instantiation the library holds, once. Their initialisers are also where the compiler first meets each
 // instantiation, and the code it generates for some of the kernels depends on that order (profiles/r11_render_driver.txt): the
@@ -140,6 +142,9 @@ inline PathKernel moving_path_kernel(bool bin);
 // curves existed (profiles/curve_resource_usage.txt, profiles/curve_bench.txt). (The SpatialLightDistribution tables sample lights
 // only, and a curve carries none: the build for shapes serves.)
 // curve_direct_kernel, curve_path_kernel, launch_trace_curves: curve_kernels.h
+// ... and so are the builds for a curve scene whose table holds a hair row, k_shade_direct<MODE, 3 + kDirectCurves + kDirectHair> and
+// k_shade_hair<BIN>, in hair_kernels.hip (profiles/hair_resource_usage.txt). AO reads no BSDF and traversal reads no material: the
+// curve builds serve. hair_direct_kernel, hair_path_kernel: hair_kernels.h
 
 // the build of the SpatialLightDistribution tables (wf_lights.h)
 inline SpatialKernel spatial_tables_kernel(const SceneNeeds& n) {
@@ -157,6 +162,7 @@ inline DirectKernel direct_kernel(const SceneNeeds& n, int integrator) {
                                                {k_shade_direct<D, 1>, k_shade_direct<W, 1>},
                                                {k_shade_direct<D, 0>, k_shade_direct<W, 0>}};
     static constexpr DirectKernel ao[2] = {k_shade_direct<AO, kDirectShapes>, k_shade_direct<AO, 0>};
+    if (n.curves && n.hair && (integrator == D || integrator == W)) return hair_direct_kernel(integrator == W);
     if (n.curves) return curve_direct_kernel(integrator);
     if (n.moving) return moving_direct_kernel(integrator);
     if (n.lobes && (integrator == D || integrator == W)) return lobe_direct_kernel(integrator == W);
@@ -169,6 +175,7 @@ inline PathKernel path_kernel(const SceneNeeds& n, bool bin) {
     static constexpr PathKernel table[2][6] = {
         {k_shade_shapes<true>, k_shade_maps<true>, k_shade<true, 3>, k_shade<true, 2>, k_shade<true, 1>, k_shade<true, 0>},
         {k_shade_shapes<false>, k_shade_maps<false>, k_shade<false, 3>, k_shade<false, 2>, k_shade<false, 1>, k_shade<false, 0>}};
+    if (n.curves && n.hair) return hair_path_kernel(bin);
     if (n.curves) return curve_path_kernel(bin);
     if (n.moving) return moving_path_kernel(bin);
     if (n.lobes) return lobe_path_kernel(bin);

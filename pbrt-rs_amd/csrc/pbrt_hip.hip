@@ -340,6 +340,7 @@ static void upload_tables(PbrtHipScene* s, const SceneDesc& desc, ScenePlan& pla
     s->light_maps = plan.light_maps;
     s->h_lights = std::move(plan.lights);
     s->h_materials = std::move(plan.materials);
+    s->row_off_curve = std::move(plan.row_off_curve);
     s->h_light_maps = std::move(plan.light_map_rows);
     s->light_fov = std::move(plan.light_fov);
     s->light_samples = std::move(plan.light_samples);
@@ -783,8 +784,9 @@ static int write_material(PbrtHipScene* s, int32_t material, const DevMaterial& 
     if (int rc = edit.apply()) return rc;
     s->h_materials[material] = m;
     s->h_lobe_origin[material] = origin;
-    s->bxdfs = s->disney = s->lobes = false;
+    s->bxdfs = s->disney = s->lobes = s->hair = false;
     for (const DevMaterial& row : s->h_materials) {
+        s->hair = s->hair || row.type == kMatHair;
         s->lobes = s->lobes || row.type == kMatLobes;
         s->bxdfs = s->bxdfs || (row.type >= kMatOrenNayar && row.type <= kMatSubstrate);
         s->disney = s->disney || row.type == kMatDisney;
@@ -857,6 +859,35 @@ extern "C" int pbrt_hip_scene_set_disney_material(PbrtHipScene* s, int32_t mater
     if (!why.empty()) return invalid(why);
     const DeviceWrite block{(void*)(s->d.disney + material), &z, nullptr, sizeof(DevDisney)};
     return write_material(s, material, m, 0, &block);
+}
+PB_ABI_CATCH
+
+// pbrt-v3's HairMaterial (include/pbrt_hip.h): row `material` becomes a kMatHair row and its DevHair block
+// (scene.h), which lives in the row's slot of the Disney table, gets the lobes' constants (host_edit.cpp). The hair builds shade
+// it (wf_hair.h, hair_kernels.hip). As with a Disney row the block has no host copy: the row, written after it, is what names it.
+extern "C" int pbrt_hip_scene_set_hair_material(PbrtHipScene* s, int32_t material, const PbrtHairDesc* desc) try {
+    PB_EDIT(s, "pbrt_hip_scene_set_hair_material");
+    if (!desc) return invalid("null desc");
+    if (material < 0 || material >= (int32_t)s->h_materials.size()) return invalid("material index out of range");
+    DevHair z;
+    DevMaterial m;
+    const std::string why = hair_of_desc(*desc, &z, &m);
+    if (!why.empty()) return invalid(why);
+    if (!s->d.curves) return invalid("the scene holds no curves (pbrt_hip_scene_create_with_curves): a hair row needs a curve's v");
+    if (s->row_off_curve[material]) return invalid("a triangle or a quadric shape names the row: only curves carry the v a hair row reads");
+    const DeviceWrite block{(void*)(s->d.disney + material), &z, nullptr, sizeof(DevHair)};
+    return write_material(s, material, m, 0, &block);
+}
+PB_ABI_CATCH
+
+// scene_needs (kernel_select.h) as the render driver reads it, for callers and tests that want to know which builds a render runs
+extern "C" int pbrt_hip_scene_shading_needs(const PbrtHipScene* s, int32_t out[8]) try {
+    if (!s || !out) return PBRT_HIP_ERR_INVALID;
+    PB_LOCK(s->ctx);
+    const SceneNeeds n = scene_needs(s);
+    const int32_t v[8] = {n.shapes, n.light_maps, n.level, n.lobes, n.moving, n.curves, n.hair, 0};
+    std::memcpy(out, v, sizeof(v));
+    return PBRT_HIP_OK;
 }
 PB_ABI_CATCH
 

@@ -358,6 +358,7 @@ extern "C" int pbrt_hip_bsdf_query(PbrtHipScene* s, int32_t material, int64_t n,
         return PBRT_HIP_ERR_INVALID;
     };
     if (material < 0 || material >= s->d.n_materials) return invalid("material index out of range");
+    if (s->h_materials[material].type == kMatHair) return invalid("a hair row needs h per point: pbrt_hip_bsdf_query_hair");
     if (n < 0 || n > ((int64_t)1 << 31)) return invalid("n must be in [0, 2^31]");
     if (n == 0) return PBRT_HIP_OK;
     if (!wo || !wi || !u) return invalid("null wo / wi / u");
@@ -1355,7 +1356,7 @@ void RenderJob::shade_wavefront(const PassParams& pp, int cur, int nxt, uint32_t
         hipLaunchKernelGGL(k_shade_sort_keys, dim3((n_shade + 255) / 256), dim3(256), 0, st, sc, ps, q[cur].shade, n_shade, pp.max_depth,
                            ss.keys[0], shade_positions);
         size_t tb = ss.tmp_bytes;
-        if (pb::sort_pairs_u32(st, ss.tmp, &tb, ss.keys[0], ss.keys[1], shade_positions, ss.vals, n_shade, (s->bxdfs || s->disney || s->lobes) ? 4 : 3) != 0 &&
+        if (pb::sort_pairs_u32(st, ss.tmp, &tb, ss.keys[0], ss.keys[1], shade_positions, ss.vals, n_shade, (s->bxdfs || s->disney || s->lobes || s->hair) ? 4 : 3) != 0 &&
             rc == PBRT_HIP_OK) {
             ctx->last_error = "rocPRIM radix sort failed";
             rc = PBRT_HIP_ERR_DEVICE;

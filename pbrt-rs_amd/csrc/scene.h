@@ -145,6 +145,21 @@ struct DevLobeRow {
     DevLobe lobes[kMaxLobes];
 };
 
+// kMatHair: a row of pbrt_hip_scene_set_hair_material (wf_hair.h): pbrt-v3's HairBSDF on a curve. The DevMaterial row keeps eta;
+// the lobes' constants are the DevHair block, computed on the host in double and rounded once per field (host_edit.cpp). The block
+// lives in the row's slot of DevSceneData::disney (a row is a Disney row or a hair row, never both; the row's type says how the
+// slot reads), so no kernel's argument block grows.
+constexpr int kMatHair = 11;
+struct DevHair {
+    float sigma_a[3];
+    float eta;
+    float v[4];               // longitudinal variances of p = 0, 1, 2 and of the residual
+    float s;                  // the azimuthal logistic's scale
+    float sin2k[3], cos2k[3]; // sin / cos of 2^k alpha
+    float trim_k, cdf_lo;     // logistic cdf(pi, s) - cdf(-pi, s) and cdf(-pi, s): the trimmed logistic's normalisation
+};
+static_assert(sizeof(DevHair) <= sizeof(DevDisney), "a hair row's block lives in the row's slot of the Disney table");
+
 // Distribution1D (src/core/sampling.rs:62-154) flattened: func[n], cdf[n+1]
 struct DevDistribution1D {
     const float* func;
@@ -217,6 +232,8 @@ struct PbrtHipScene {
     bool bxdfs = false;   // a kMatOrenNayar / kMatRoughGlass / kMatSubstrate row in the table: their level-2 instantiations run
     bool disney = false;  // a kMatDisney row in the table: their level-3 instantiations run
     bool lobes = false;   // a kMatLobes row in the table: the shading kernels' lobe-list builds run
+    bool hair = false;    // a kMatHair row in the table: the hair builds run (hair_kernels.hip)
+    std::vector<uint8_t> row_off_curve;  // per material row: a triangle or a quadric shape names it (a hair row needs a curve's v)
     std::vector<pb::DevLobeRow> h_lobe_rows;  // the device table's host copy: a mix reads its operands' lists
     std::vector<int> h_lobe_origin;           // per row: the PbrtLobeMaterialType that wrote it, 0 for any other row
     bool light_maps = false;  // a projection or goniometric light in the table: the shading kernels' map-light builds run

@@ -40,7 +40,9 @@ struct DirectState {
 // time is read from its continuation ray at entry and written back to it, and to every ray the launch emitted, at the end.
 // + 64 in the builds for scenes with curve segments (CRV as shade_bounce's; they are the builds for shapes with the curve's surface
 // added): <DIRECT, 67>, <WHITTED, 67> and <AO, 64>, one wave per SIMD (profiles/curve_resource_usage.txt).
-constexpr int kDirectShapes = 4, kDirectMapLights = 8, kDirectLobes = 16, kDirectMoving = 32, kDirectCurves = 64;
+// + 128 on top of the curve builds when the table holds a hair row (HAIR as shade_bounce's): <DIRECT, 195> and <WHITTED, 195>,
+// instantiated in hair_kernels.hip alone. AO reads no BSDF: the curve build serves.
+constexpr int kDirectShapes = 4, kDirectMapLights = 8, kDirectLobes = 16, kDirectMoving = 32, kDirectCurves = 64, kDirectHair = 128;
 template <int MODE, int LEVEL_SHP>
 __global__ void __launch_bounds__(256, (((LEVEL_SHP & 3) >= 1 && MODE == PBRT_INTEGRATOR_DIRECT) || (LEVEL_SHP & (16 | 32 | 64))) ? 1 : PB_DIRECT_WAVES) k_shade_direct(ShadeConsts sc, PathState ps, DirectState ds, Queues qin,
                                                         Queues qout, PassParams pp, TileList tiles, uint32_t n_in) {
@@ -50,7 +52,8 @@ __global__ void __launch_bounds__(256, (((LEVEL_SHP & 3) >= 1 && MODE == PBRT_IN
     constexpr bool ML = SHP || (LEVEL_SHP & kDirectMapLights) != 0;
     constexpr bool LOBES = (LEVEL_SHP & kDirectLobes) != 0;
     constexpr bool MOV = (LEVEL_SHP & kDirectMoving) != 0;
-    constexpr int BL = LOBES ? 4 : LEVEL;  // the BSDF type: LevelBsdf<BL>
+    constexpr bool HAIR = (LEVEL_SHP & kDirectHair) != 0;
+    constexpr int BL = HAIR ? kHairBsdfLevel : LOBES ? 4 : LEVEL;  // the BSDF type: LevelBsdf<BL>
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool active = i < n_in;
     uint32_t p = active ? qin.shade[i] : 0u;
@@ -237,6 +240,7 @@ __global__ void __launch_bounds__(256, (((LEVEL_SHP & 3) >= 1 && MODE == PBRT_IN
                 if (GLOSSY) {
                     typename LevelBsdf<BL>::type nsb;
                     load_bsdf(sc, sf.material, sc.materials[sf.material], &nsb);  // read again here: keeps the alphas out of the loop's registers
+                    if constexpr (HAIR) nsb.h = -1.0f + 2.0f * ps.hit[hbase].z;   // the curve's hit record carries (u, v, 0)
                     if (nsb.n > 0) bsdf_f_pdf(nsb, fr, sf.wo, wi, &f, &spdf);  // BSDF::f, all lobes
                 } else if (mat.type == PBRT_MAT_MATTE && !is_black(kd)) {
                     matte_f_pdf(fr, kd, sf.wo, wi, &f, &spdf);  // BSDF::f, all lobes
@@ -281,6 +285,7 @@ __global__ void __launch_bounds__(256, (((LEVEL_SHP & 3) >= 1 && MODE == PBRT_IN
                 if (GLOSSY) {
                     typename LevelBsdf<BL>::type nsb;
                     load_bsdf(sc, sf.material, sc.materials[sf.material], &nsb);
+                    if constexpr (HAIR) nsb.h = -1.0f + 2.0f * ps.hit[hbase].z;
                     nee_flags = estimate_direct_emit<SHP, ML>(sc, RecordSink{ps, p}, sf, fr, nsb.n > 0, nsb, light_num, ul0, ul1, us0, us1, pick_pdf, T);
                 } else {
                     bool matte = (mat.type == PBRT_MAT_MATTE) && !is_black(kd);

@@ -72,12 +72,16 @@ struct ShadeBins {
 // rebuilt through the instance's rows at the path's time, which rides in the fourth component of the ray's second float4 and is
 // copied to every ray the path emits (spawn_ray keeps the time); k_shade_moving below is that build. CRV (with SHP): it holds curve
 // segments (sc.curves): a curve's surface is rebuilt from the continuation ray (make_surface_curve); k_shade_curves below.
-template <bool BIN, int LEVEL, bool SHP, bool ML = false, bool MOV = false, bool CRV = false>
+// HAIR (with CRV): the table holds a kMatHair row: the BSDF type is HairBsdf (wf_hair.h, which only hair_kernels.hip includes: the
+// type is named through LevelBsdf<kHairBsdfLevel>, a dependent name), h comes from the hit record's v, and the bins have a key more.
+constexpr int kHairBsdfLevel = 5;
+template <bool BIN, int LEVEL, bool SHP, bool ML = false, bool MOV = false, bool CRV = false, bool HAIR = false>
 PB_DEV void shade_bounce(const ShadeConsts& sc, const PathState& ps, const Queues& qin, const Queues& qout, const PassParams& pp,
                          const TileList& tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
     constexpr bool GLOSSY = LEVEL >= 1;
     constexpr bool LOBES = LEVEL == 4;
-    constexpr int kShadeKeys = shade_keys(LEVEL);
+    constexpr int kShadeKeys = HAIR ? 2 + kMatHair + 1 : shade_keys(LEVEL);  // HAIR: 0, 1 + type up to kMatHair, the block tail
+    constexpr int BL = HAIR ? kHairBsdfLevel : LEVEL;                        // the BSDF type: LevelBsdf<BL>
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     bool active = i < n_in;
     uint32_t rec = (active && order) ? order[i] : i;
@@ -181,9 +185,10 @@ PB_DEV void shade_bounce(const ShadeConsts& sc, const PathState& ps, const Queue
                     V3 wo = -rd;  // path.rs:122 `let wo = -ray.d` (estimate_direct uses isect.wo = sf.wo)
                     bool has_lobe;  // which BxDFs the material adds: pbrt-v3 rules (matte / mirror / glass / plastic / metal; level 2: Oren-Nayar / rough glass / substrate rows)
                     bool nonspecular;
-                    typename LevelBsdf<LEVEL>::type nsb;
+                    typename LevelBsdf<BL>::type nsb;
                     if (GLOSSY) {
                         load_bsdf(sc, sf.material, mat, &nsb);
+                        if constexpr (HAIR) nsb.h = -1.0f + 2.0f * h0.z;  // the curve's hit record carries (u, v, 0)
                         nonspecular = nsb.n > 0;
                         if (mat.type == PBRT_MAT_GLASS) has_lobe = !(is_black(kd) && is_black(kt));
                         else if (mat.type == PBRT_MAT_MIRROR) has_lobe = !is_black(kd);
@@ -336,6 +341,14 @@ template <bool BIN>
 __global__ void __launch_bounds__(256, 2) k_shade_curves(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
                                                         TileList tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
     shade_bounce<BIN, 3, true, true, false, true>(sc, ps, qin, qout, pp, tiles, n_in, order);
+}
+
+// scenes with curve segments whose table holds a hair row (wf_hair.h): the curve build with HairBsdf (profiles/hair_resource_usage.txt).
+// Instantiated in hair_kernels.hip alone.
+template <bool BIN>
+__global__ void __launch_bounds__(256, 2) k_shade_hair(ShadeConsts sc, PathState ps, Queues qin, Queues qout, PassParams pp,
+                                                      TileList tiles, uint32_t n_in, const uint32_t* __restrict__ order) {
+    shade_bounce<BIN, 3, true, true, false, true, true>(sc, ps, qin, qout, pp, tiles, n_in, order);
 }
 
 }  // namespace pb

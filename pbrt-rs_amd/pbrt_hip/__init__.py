@@ -51,6 +51,7 @@ EXPORTS = [
     "pbrt_hip_render_moving_camera", "pbrt_hip_render_device_moving_camera", "pbrt_hip_camera_rays_moving_camera",
     "pbrt_hip_camera_motion_interpolate",
     "pbrt_hip_curve_world_bounds", "pbrt_hip_scene_create_with_curves",
+    "pbrt_hip_scene_set_hair_material", "pbrt_hip_hair_tables", "pbrt_hip_bsdf_query_hair", "pbrt_hip_scene_shading_needs",
 ]
 MAT_NONE, MAT_MATTE, MAT_MIRROR, MAT_GLASS, MAT_PLASTIC, MAT_METAL = (scenes.MAT_NONE, scenes.MAT_MATTE, scenes.MAT_MIRROR,
                                                                       scenes.MAT_GLASS, scenes.MAT_PLASTIC, scenes.MAT_METAL)
@@ -96,6 +97,27 @@ class MaterialDesc(ctypes.Structure):
 class DisneyDesc(ctypes.Structure):
     """PbrtDisneyDesc (pbrt_hip_scene_set_disney_material); scenes.disney gives the keyword form"""
     _fields_ = [("color", ctypes.c_float * 3)] + [(k, ctypes.c_float) for k in scenes.DISNEY_SCALARS] + [("thin", ctypes.c_int32)]
+
+
+class HairDesc(ctypes.Structure):
+    """PbrtHairDesc (pbrt_hip_scene_set_hair_material); scenes.hair gives the keyword form"""
+    _fields_ = ([("absorption", ctypes.c_int32), ("sigma_a", ctypes.c_float * 3), ("color", ctypes.c_float * 3)] +
+                [(k, ctypes.c_float) for k in ("eumelanin", "pheomelanin", "eta", "beta_m", "beta_n", "alpha")])
+
+
+class HairTables(ctypes.Structure):
+    """PbrtHairTables (pbrt_hip_hair_tables)"""
+    _fields_ = [("sigma_a", ctypes.c_float * 3), ("eta", ctypes.c_float), ("v", ctypes.c_float * 4), ("s", ctypes.c_float),
+                ("sin2k", ctypes.c_float * 3), ("cos2k", ctypes.c_float * 3)]
+
+
+def _hair_desc(desc):
+    if desc is None or isinstance(desc, HairDesc):
+        return desc
+    d = HairDesc()
+    for k, v in desc.items():
+        setattr(d, k, (ctypes.c_float * 3)(*[float(c) for c in v]) if k in ("sigma_a", "color") else v)
+    return d
 
 
 _LOBE_COLOURS = ("kd", "ks", "kr", "kt", "opacity", "reflect", "transmit", "amount")
@@ -243,6 +265,10 @@ def lib():
         L.pbrt_hip_scene_set_lobe_material.argtypes = [vp, i32, vp]
         L.pbrt_hip_material_lobes.argtypes = [vp, vp, vp, vp, i32, ctypes.c_float, vp, i32, vp, ctypes.POINTER(i32),
                                               ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_char_p)]
+        L.pbrt_hip_scene_set_hair_material.argtypes = [vp, i32, vp]
+        L.pbrt_hip_hair_tables.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_char_p)]
+        L.pbrt_hip_bsdf_query_hair.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.pbrt_hip_scene_shading_needs.argtypes = [vp, vp]
         _lib = L
     return _lib
 
@@ -539,6 +565,7 @@ class Scene:
         scene["disney_descs"] = {row: descriptor} (optional): set_disney_material(row, descriptor) after that;
         scene["lobe_descs"] = {row: descriptor} (optional): set_lobe_material(row, descriptor) after that, in insertion order,
         so a mix's operands come first;
+        scene["hair_descs"] = {row: descriptor} (optional): set_hair_material(row, descriptor) after that (a scene with curves);
         scene["light_maps"] = {light: rgb} (optional): set_light_map(light, rgb) after that."""
         self._create(ctx, scene, max_prims_in_node, split_method, bvh, device_build)
         try:
@@ -548,6 +575,8 @@ class Scene:
                 self.set_disney_material(row, desc)
             for row, desc in (scene.get("lobe_descs") or {}).items():
                 self.set_lobe_material(row, desc)
+            for row, desc in (scene.get("hair_descs") or {}).items():
+                self.set_hair_material(row, desc)
             for light, rgb in (scene.get("light_maps") or {}).items():
                 self.set_light_map(light, rgb)
         except Exception:
@@ -966,6 +995,36 @@ class Scene:
         self.ctx.check(lib().pbrt_hip_scene_set_lobe_material(self.h, int(m), None if desc is None else ctypes.byref(desc)),
                        "pbrt_hip_scene_set_lobe_material")
 
+    def set_hair_material(self, m, desc):
+        """Replaces row m of the material table of a scene with curves by pbrt-v3's HairMaterial: scenes.hair() (a dict of
+        PbrtHairDesc's fields) or a HairDesc (pbrt_hip_scene_set_hair_material). Only curves may name the row."""
+        desc = _hair_desc(desc)
+        self.ctx.check(lib().pbrt_hip_scene_set_hair_material(self.h, int(m), None if desc is None else ctypes.byref(desc)),
+                       "pbrt_hip_scene_set_hair_material")
+
+    def shading_needs(self):
+        """What the scene's tables ask of the shading kernels right now (pbrt_hip_scene_shading_needs: kernel_select.h's SceneNeeds):
+        dict shapes, light_maps, level, lobes, moving, curves, hair. curves and hair together: the hair builds run."""
+        out = np.zeros(8, np.int32)
+        self.ctx.check(lib().pbrt_hip_scene_shading_needs(self.h, _p(out)), "pbrt_hip_scene_shading_needs")
+        keys = ("shapes", "light_maps", "level", "lobes", "moving", "curves", "hair")
+        return {k: (int(v) if k == "level" else bool(v)) for k, v in zip(keys, out)}
+
+    def bsdf_query_hair(self, material, h, wo, wi, u):
+        """bsdf_query for a hair row: h (n,) in [-1, 1] is the offset across the fibre, x of the frame runs along it."""
+        h = np.ascontiguousarray(h, dtype=np.float32).reshape(-1)
+        wo = np.ascontiguousarray(wo, dtype=np.float32).reshape(-1, 3)
+        wi = np.ascontiguousarray(wi, dtype=np.float32).reshape(-1, 3)
+        u = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, 2)
+        n = len(wo)
+        assert len(wi) == n and len(u) == n and len(h) == n
+        out = dict(f=np.zeros((n, 3), np.float32), pdf=np.zeros(n, np.float32), wi_s=np.zeros((n, 3), np.float32),
+                   f_s=np.zeros((n, 3), np.float32), pdf_s=np.zeros(n, np.float32), flags=np.zeros(n, np.int32))
+        self.ctx.check(lib().pbrt_hip_bsdf_query_hair(self.h, int(material), n, _p(h), _p(wo), _p(wi), _p(u), _p(out["f"]), _p(out["pdf"]),
+                                                      _p(out["wi_s"]), _p(out["f_s"]), _p(out["pdf_s"]), _p(out["flags"])),
+                       "pbrt_hip_bsdf_query_hair")
+        return out
+
     def bsdf_query(self, material, wo, wi, u):
         """BSDF::f / pdf / sample_f of a material on the device, in the shading frame (n = +z): wo, wi (n, 3), u (n, 2).
         Returns dict f (n, 3), pdf (n,), wi_s (n, 3), f_s (n, 3), pdf_s (n,), flags (n,) int32 BxDFType of the sampled lobe."""
@@ -1183,6 +1242,19 @@ def envmap_tables(rgb, L=(1.0, 1.0, 1.0)):
 
 
 _LOBE_FIELDS = [k for k, _ in Lobe._fields_]
+
+
+def hair_tables(desc):
+    """pbrt_hip_hair_tables: the constants of a hair row as the device holds them (float32), on the host, without a context:
+    dict sigma_a (3,), eta, v (4,), s, sin2k (3,), cos2k (3,). desc: scenes.hair() or a HairDesc."""
+    desc = _hair_desc(desc)
+    t = HairTables()
+    why = ctypes.c_char_p()
+    rc = lib().pbrt_hip_hair_tables(None if desc is None else ctypes.addressof(desc), ctypes.addressof(t), ctypes.byref(why))
+    if rc != 0:
+        raise PbrtHipError(f"pbrt_hip_hair_tables failed ({rc}): {(why.value or b'').decode()}")
+    return dict(sigma_a=np.array(t.sigma_a[:], np.float32), eta=np.float32(t.eta), v=np.array(t.v[:], np.float32), s=np.float32(t.s),
+                sin2k=np.array(t.sin2k[:], np.float32), cos2k=np.array(t.cos2k[:], np.float32))
 
 
 def material_lobes(desc, a=None, b=None):

@@ -172,6 +172,26 @@ def material_row(type, kd=(0, 0, 0), kt=(0, 0, 0), eta=0.0):
     return dict(row=True, type=int(type), kd=_rgb(kd), kt=_rgb(kt), eta=float(eta))
 
 
+HAIR_SIGMA_A, HAIR_COLOR, HAIR_MELANIN = 0, 1, 2  # PbrtHairAbsorption
+
+
+def hair(sigma_a=None, color=None, eumelanin=None, pheomelanin=None, eta=1.55, beta_m=0.3, beta_n=0.3, alpha=2.0):
+    """Descriptor (Scene.set_hair_material, scene["hair_descs"], pbrt_hip.hair_tables) of pbrt-v3's HairMaterial with its defaults.
+    Absorption by pbrt-v3's precedence when more than one is given: sigma_a, then color, then the melanin concentrations; none
+    given: eumelanin 1.3."""
+    d = dict(absorption=HAIR_MELANIN, sigma_a=(0.0, 0.0, 0.0), color=(0.0, 0.0, 0.0), eumelanin=0.0, pheomelanin=0.0, eta=float(eta),
+             beta_m=float(beta_m), beta_n=float(beta_n), alpha=float(alpha))
+    if sigma_a is not None:
+        d.update(absorption=HAIR_SIGMA_A, sigma_a=_rgb(sigma_a))
+    elif color is not None:
+        d.update(absorption=HAIR_COLOR, color=_rgb(color))
+    elif eumelanin is not None or pheomelanin is not None:
+        d.update(eumelanin=float(eumelanin or 0.0), pheomelanin=float(pheomelanin or 0.0))
+    else:
+        d.update(eumelanin=1.3)
+    return d
+
+
 def disney_invalid(desc):
     """Why pbrt_hip_scene_set_disney_material refuses the descriptor (the same rules, checked before the call), or None"""
     if desc is None:

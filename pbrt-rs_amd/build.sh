@@ -7,7 +7,7 @@ OUT=${PB_OUT:-../pbrt_hip/libpbrt_hip.so}
 FLAGS="-O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fhip-fp32-correctly-rounded-divide-sqrt --offload-arch=gfx950 -Wall -Wno-unused-function"
 OBJ=$(mktemp -d /tmp/pbrt_hip_build.XXXXXX)
 trap 'rm -rf "$OBJ"' EXIT
-SRCS="pbrt_hip.hip render.hip curve_kernels.hip hair_kernels.hip hlbvh_gpu.hip wide_gpu.hip probe.hip host_bvh.cpp host_wide.cpp host_film.cpp host_edit.cpp host_envmap.cpp host_lobes.cpp host_motion.cpp host_scene.cpp film_reduce.cpp"
+SRCS="pbrt_hip.hip render.hip curve_kernels.hip hair_kernels.hip hlbvh_gpu.hip wide_gpu.hip probe.hip host_bvh.cpp host_wide.cpp host_film.cpp host_edit.cpp host_envmap.cpp host_lobes.cpp host_motion.cpp host_render.cpp host_scene.cpp film_reduce.cpp"
 pids=()
 for f in $SRCS; do
   /opt/rocm/bin/hipcc $FLAGS $PB_DEFS -c -o "$OBJ/${f%.*}.o" "$f" &

@@ -5,10 +5,6 @@
 #include <hip/hip_runtime.h>
 #include "abi_guard.h"
 
-#include <cstring>
-#include <string>
-#include <vector>
-
 #define PB_PLAIN_KERNEL static __global__  // dev_math.h: the headers' plain kernels are render.hip's; here they are local and dropped
 #include "scene.h"
 #include "trace.h"
@@ -17,6 +13,7 @@
 
 #include "curve_kernels.h"
 #include "hair_kernels.h"
+#include "point_query.h"
 
 namespace pb {
 
@@ -38,13 +35,8 @@ __global__ void k_bsdf_query_hair(const DevHair* __restrict__ hr, int64_t n, con
                                   const float* __restrict__ wi_in, const float* __restrict__ u_in, float* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Frame fr;
-    fr.ss = V3{1.0f, 0.0f, 0.0f};
-    fr.ts = V3{0.0f, 1.0f, 0.0f};
-    fr.ns = V3{0.0f, 0.0f, 1.0f};
-    fr.ng = fr.ns;
-    const V3 wo = V3{wo_in[3 * i], wo_in[3 * i + 1], wo_in[3 * i + 2]};
-    const V3 wi = V3{wi_in[3 * i], wi_in[3 * i + 1], wi_in[3 * i + 2]};
+    const Frame fr = query_frame();
+    const V3 wo = query_v3(wo_in, i), wi = query_v3(wi_in, i);
     const float h = h_in[i];
     V3 f, wi_s = V3{0.0f, 0.0f, 0.0f}, f_s = wi_s;
     float pdf, pdf_s = 0.0f;
@@ -60,19 +52,7 @@ __global__ void k_bsdf_query_hair(const DevHair* __restrict__ hr, int64_t n, con
         pdf_s = ps;
         sampled = kBxdfGlossy | kBxdfReflection | kBxdfTransmission;
     }
-    float* o = out + 12 * i;
-    o[0] = f.x;
-    o[1] = f.y;
-    o[2] = f.z;
-    o[3] = pdf;
-    o[4] = wi_s.x;
-    o[5] = wi_s.y;
-    o[6] = wi_s.z;
-    o[7] = f_s.x;
-    o[8] = f_s.y;
-    o[9] = f_s.z;
-    o[10] = pdf_s;
-    o[11] = __int_as_float(sampled);
+    query_write(out, i, f, pdf, wi_s, f_s, pdf_s, sampled);
 }
 
 }  // namespace pb
@@ -83,52 +63,14 @@ extern "C" int pbrt_hip_bsdf_query_hair(PbrtHipScene* s, int32_t material, int64
                                         const float* u, float* f, float* pdf, float* wi_s, float* f_s, float* pdf_s,
                                         int32_t* sampled_flags) try {
     if (!s) return PBRT_HIP_ERR_INVALID;
-    PbrtHipContext* ctx = s->ctx;
-    PB_ENTER(ctx);
-    auto invalid = [&](const char* why) {
-        ctx->last_error = std::string("pbrt_hip_bsdf_query_hair: ") + why;
-        return PBRT_HIP_ERR_INVALID;
-    };
-    if (material < 0 || material >= s->d.n_materials) return invalid("material index out of range");
-    if (s->h_materials[material].type != kMatHair) return invalid("the row is not a hair row (pbrt_hip_bsdf_query serves every other row)");
-    if (n < 0 || n > ((int64_t)1 << 31)) return invalid("n must be in [0, 2^31]");
-    if (n == 0) return PBRT_HIP_OK;
-    if (!h || !wo || !wi || !u) return invalid("null h / wo / wi / u");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PB_ENTER(s->ctx);
     const size_t un = (size_t)n;
-    float *d_in = nullptr, *d_out = nullptr;
-    int rc = PBRT_HIP_OK;
-    if (!hip_ok(ctx, hipMalloc((void**)&d_in, un * 9 * sizeof(float)), "hipMalloc") ||
-        !hip_ok(ctx, hipMalloc((void**)&d_out, un * 12 * sizeof(float)), "hipMalloc"))
-        rc = PBRT_HIP_ERR_OOM;
-    if (rc == PBRT_HIP_OK && (!hip_ok(ctx, hipMemcpy(d_in, wo, un * 3 * sizeof(float), hipMemcpyHostToDevice), "H2D") ||
-                              !hip_ok(ctx, hipMemcpy(d_in + 3 * un, wi, un * 3 * sizeof(float), hipMemcpyHostToDevice), "H2D") ||
-                              !hip_ok(ctx, hipMemcpy(d_in + 6 * un, u, un * 2 * sizeof(float), hipMemcpyHostToDevice), "H2D") ||
-                              !hip_ok(ctx, hipMemcpy(d_in + 8 * un, h, un * sizeof(float), hipMemcpyHostToDevice), "H2D")))
-        rc = PBRT_HIP_ERR_DEVICE;
-    std::vector<float> res;
-    if (rc == PBRT_HIP_OK) {
-        hipLaunchKernelGGL(k_bsdf_query_hair, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                           (const DevHair*)(s->d.disney + material), n, d_in + 8 * un, d_in, d_in + 3 * un, d_in + 6 * un, d_out);
-        res.resize(un * 12);
-        if (!hip_ok(ctx, hipGetLastError(), "k_bsdf_query_hair") || !hip_ok(ctx, hipStreamSynchronize(ctx->stream), "k_bsdf_query_hair") ||
-            !hip_ok(ctx, hipMemcpy(res.data(), d_out, un * 12 * sizeof(float), hipMemcpyDeviceToHost), "D2H"))
-            rc = PBRT_HIP_ERR_DEVICE;
-    }
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    if (rc != PBRT_HIP_OK) return rc;
-    for (size_t i = 0; i < un; ++i) {
-        const float* o = &res[12 * i];
-        for (int k = 0; k < 3; ++k) {
-            if (f) f[3 * i + k] = o[k];
-            if (wi_s) wi_s[3 * i + k] = o[4 + k];
-            if (f_s) f_s[3 * i + k] = o[7 + k];
-        }
-        if (pdf) pdf[i] = o[3];
-        if (pdf_s) pdf_s[i] = o[10];
-        if (sampled_flags) std::memcpy(&sampled_flags[i], &o[11], 4);
-    }
-    return PBRT_HIP_OK;
+    return bsdf_query(
+        s, "pbrt_hip_bsdf_query_hair", true, material, n, {{wo, 3}, {wi, 3}, {u, 2}, {h, 1}}, "null h / wo / wi / u", "k_bsdf_query_hair",
+        [&](const float* d_in, float* d_out) {
+            hipLaunchKernelGGL(k_bsdf_query_hair, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s->ctx->stream,
+                               (const DevHair*)(s->d.disney + material), n, d_in + 8 * un, d_in, d_in + 3 * un, d_in + 6 * un, d_out);
+        },
+        BsdfQueryOut{f, pdf, wi_s, f_s, pdf_s, sampled_flags});
 }
 PB_ABI_CATCH

@@ -21,6 +21,7 @@
 #include "kernel_select.h"
 #include "motion.h"
 #include "scene.h"
+#include "staging.h"
 #include "trace.h"
 #include "trace_persistent.h"
 #include "trace_wide.h"
@@ -268,15 +269,6 @@ __global__ void k_shape_angles(DevShape* shapes, int n) {
 }
 }  // namespace pb
 
-namespace {
-struct ScopedDeviceBlock {  // freed on scope exit
-    void* p = nullptr;
-    ~ScopedDeviceBlock() {
-        if (p) (void)hipFree(p);
-    }
-};
-}  // namespace
-
 // The plan's tables on the device, every one but the wide records and the spill slab.
 static void upload_tables(PbrtHipScene* s, const SceneDesc& desc, ScenePlan& plan, bool* ok) {
     PbrtHipContext* ctx = s->ctx;
@@ -354,9 +346,10 @@ static void upload_tables(PbrtHipScene* s, const SceneDesc& desc, ScenePlan& pla
 // PBRT_WIDE_BUILD_HOST).
 static bool wide_on_device(PbrtHipContext* ctx, const SceneDesc& desc, const float4* d_tris, pb::WideDeviceTree* w) {
     bool up = true;
-    ScopedDeviceBlock flat;  // only the builder needs it
-    flat.p = dev_copy(ctx, desc.nodes, (size_t)desc.n_nodes, &up);
-    return up && pb::build_wide_tree_device(ctx, (const PbrtLinearBVHNode*)flat.p, desc.n_nodes, (const float*)d_tris, desc.n_prims(),
+    Staging flat(ctx);  // only the builder needs it
+    const PbrtLinearBVHNode* d_flat = dev_copy(ctx, desc.nodes, (size_t)desc.n_nodes, &up);
+    flat.adopt((void*)d_flat);
+    return up && pb::build_wide_tree_device(ctx, d_flat, desc.n_nodes, (const float*)d_tris, desc.n_prims(),
                                             desc.nodes[0], w, &w->reason);
 }
 
@@ -1176,24 +1169,16 @@ static int intersect_host(PbrtHipScene* s, const PbrtRay* rays, int64_t n, void*
     PbrtHipContext* ctx = s->ctx;
     PB_ENTER(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    PbrtRay* d_rays = nullptr;
-    void* d_out = nullptr;
-    size_t out_bytes = ANY ? (size_t)n : (size_t)n * sizeof(PbrtHit);
-    HIP_TRY(ctx, hipMalloc((void**)&d_rays, (size_t)n * sizeof(PbrtRay)));
-    if (!hip_ok(ctx, hipMalloc(&d_out, out_bytes), "hipMalloc")) {
-        (void)hipFree(d_rays);
-        return PBRT_HIP_ERR_DEVICE;
-    }
+    const size_t out_bytes = ANY ? (size_t)n : (size_t)n * sizeof(PbrtHit);
+    Staging dev(ctx);
+    PbrtRay* d_rays = dev.alloc<PbrtRay>((size_t)n);
+    char* d_out = dev.alloc<char>(out_bytes);
+    if (dev.failed) return PBRT_HIP_ERR_DEVICE;
     int rc = PBRT_HIP_OK;
-    if (!hip_ok(ctx, hipMemcpyAsync(d_rays, rays, (size_t)n * sizeof(PbrtRay), hipMemcpyHostToDevice, ctx->stream), "H2D"))
-        rc = PBRT_HIP_ERR_DEVICE;
+    if (!dev.upload(d_rays, rays, (size_t)n * sizeof(PbrtRay), true)) rc = PBRT_HIP_ERR_DEVICE;
     if (rc == PBRT_HIP_OK) rc = launch_batch<ANY>(s, d_rays, n, (PbrtHit*)d_out, (uint8_t*)d_out);
-    if (rc == PBRT_HIP_OK &&
-        !hip_ok(ctx, hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream), "D2H"))
-        rc = PBRT_HIP_ERR_DEVICE;
+    if (rc == PBRT_HIP_OK && !dev.download(out, d_out, out_bytes, true)) rc = PBRT_HIP_ERR_DEVICE;
     if (!hip_ok(ctx, hipStreamSynchronize(ctx->stream), "sync") && rc == PBRT_HIP_OK) rc = PBRT_HIP_ERR_DEVICE;
-    (void)hipFree(d_rays);
-    (void)hipFree(d_out);
     return rc;
 }
 extern "C" int pbrt_hip_intersect(PbrtHipScene* s, const PbrtRay* rays, int64_t n, PbrtHit* out) try {

@@ -1,8 +1,11 @@
-// render.hip — Integrator::render behind the C ABI: pbrt_hip_render / pbrt_hip_render_device
-// (SamplerIntegrator::render, src/core/integrator.rs:399-480) = wavefront_render, the host driver of the kernels in
-// wavefront.h, in stages (parameters, pass size, buffers, sampler, light distribution, PassParams, the wavefront loop, the
-// film); which traversal and shading kernel a launch runs comes from kernel_select.h; the per-vertex shading data of the
-// TriangleMesh (pbrt_hip_scene_set_shading_data); the host side of the HaltonSampler tables.
+// render.hip — Integrator::render behind the C ABI: pbrt_hip_render / pbrt_hip_render_device, pbrt_hip_li and pbrt_hip_camera_rays
+// (SamplerIntegrator::render, src/core/integrator.rs:399-480) = wavefront_render, the device half of a render. What a call
+// decides on the host (parameters, refusals, tiles, pass size, sort switches, sampler layout, PassParams) is host_render.cpp's
+// plan_render; RenderJob here is that plan plus the device objects that carry it out, in stages (buffers, sampler tables, light
+// distribution, the wavefront loop, the film); which traversal and shading kernel a launch runs comes from kernel_select.h. Also
+// here: the film helpers, the block cache (DevBuf), the point-query kernels of the rows this unit's shading kernels inline
+// (point_query.h holds what they share and their host driver; staging.h the scratch of every entry point that takes host
+// pointers), and the per-vertex shading data of the TriangleMesh (pbrt_hip_scene_set_shading_data).
 #include <hip/hip_runtime.h>
 #include "abi_guard.h"
 
@@ -16,11 +19,13 @@
 #include <vector>
 
 #include "host_motion.h"
+#include "host_render.h"
 #include "scene.h"
 #include "trace.h"
 #include "wavefront.h"
 #define PB_SELECT_SHADING_KERNELS  // kernel_select.h: the tables over the kernels of wavefront.h as well
 #include "kernel_select.h"
+#include "point_query.h"
 
 using namespace pb;
 
@@ -73,14 +78,12 @@ extern "C" int pbrt_hip_render_moving_camera(PbrtHipScene* s, const PbrtCamera* 
     if (int rc = camera_row(ctx, *camera, motion, &storage, &row)) return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (params->width <= 0 || params->height <= 0) return PBRT_HIP_ERR_INVALID;
-    size_t bytes = (size_t)params->width * params->height * 4 * sizeof(float);
-    float* d_film = nullptr;
-    HIP_TRY(ctx, hipMalloc((void**)&d_film, bytes));
+    const size_t n_floats = (size_t)params->width * params->height * 4;
+    Staging dev(ctx);  // after a deadline (ctx->lost) an abandoned kernel may still write the film: it stays
+    float* d_film = dev.alloc<float>(n_floats);
+    if (!d_film) return PBRT_HIP_ERR_DEVICE;
     int rc = wavefront_render(s, *camera, *params, d_film, stats, nullptr, row);
-    if (rc == PBRT_HIP_OK && !hip_ok(ctx, hipMemcpy(film_xyzw, d_film, bytes, hipMemcpyDeviceToHost), "film D2H"))
-        rc = PBRT_HIP_ERR_DEVICE;
-    // after a deadline (ctx->lost) an abandoned kernel may still write the film and hipFree waits for the device: it stays
-    if (!ctx->lost) (void)hipFree(d_film);
+    if (rc == PBRT_HIP_OK && !dev.download(film_xyzw, d_film, n_floats * sizeof(float), false, "film D2H")) rc = PBRT_HIP_ERR_DEVICE;
     return rc;
 }
 PB_ABI_CATCH
@@ -175,25 +178,15 @@ extern "C" int pbrt_hip_li(PbrtHipScene* s, const PbrtLiParams* lp, const PbrtRa
     PbrtHipContext* ctx = s->ctx;
     PB_ENTER(ctx);
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    PbrtRay* d_rays = nullptr;
-    uint64_t* d_keys = nullptr;
-    float* d_rgb = nullptr;
-    int rc = PBRT_HIP_OK;
-    if (!hip_ok(ctx, hipMalloc((void**)&d_rays, (size_t)n * sizeof(PbrtRay)), "hipMalloc") ||
-        !hip_ok(ctx, hipMalloc((void**)&d_keys, (size_t)n * sizeof(uint64_t)), "hipMalloc") ||
-        !hip_ok(ctx, hipMalloc((void**)&d_rgb, (size_t)n * 3 * sizeof(float)), "hipMalloc"))
-        rc = PBRT_HIP_ERR_OOM;
-    if (rc == PBRT_HIP_OK && (!hip_ok(ctx, hipMemcpy(d_rays, rays, (size_t)n * sizeof(PbrtRay), hipMemcpyHostToDevice), "H2D") ||
-                              !hip_ok(ctx, hipMemcpy(d_keys, stream_keys, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice), "H2D")))
-        rc = PBRT_HIP_ERR_DEVICE;
-    if (rc == PBRT_HIP_OK) rc = pbrt_hip_li_device(s, lp, d_rays, d_keys, n, d_rgb, stats);
-    if (rc == PBRT_HIP_OK && !hip_ok(ctx, hipMemcpy(rgb, d_rgb, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost), "D2H"))
-        rc = PBRT_HIP_ERR_DEVICE;
-    if (!ctx->lost) {  // as pbrt_hip_render: what an abandoned kernel may still touch is never freed
-        (void)hipFree(d_rays);
-        (void)hipFree(d_keys);
-        (void)hipFree(d_rgb);
-    }
+    Staging dev(ctx);  // as pbrt_hip_render: what an abandoned kernel may still touch is never freed
+    PbrtRay* d_rays = dev.alloc<PbrtRay>((size_t)n);
+    uint64_t* d_keys = dev.alloc<uint64_t>((size_t)n);
+    float* d_rgb = dev.alloc<float>((size_t)n * 3);
+    if (dev.failed) return PBRT_HIP_ERR_OOM;
+    if (!dev.upload(d_rays, rays, (size_t)n * sizeof(PbrtRay)) || !dev.upload(d_keys, stream_keys, (size_t)n * sizeof(uint64_t)))
+        return PBRT_HIP_ERR_DEVICE;
+    int rc = pbrt_hip_li_device(s, lp, d_rays, d_keys, n, d_rgb, stats);
+    if (rc == PBRT_HIP_OK && !dev.download(rgb, d_rgb, (size_t)n * 3 * sizeof(float))) rc = PBRT_HIP_ERR_DEVICE;
     return rc;
 }
 PB_ABI_CATCH
@@ -206,13 +199,8 @@ __global__ void k_bsdf_query(const DevMaterial* __restrict__ materials, int mate
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const DevMaterial mat = materials[material];
-    Frame fr;
-    fr.ss = V3{1.0f, 0.0f, 0.0f};
-    fr.ts = V3{0.0f, 1.0f, 0.0f};
-    fr.ns = V3{0.0f, 0.0f, 1.0f};
-    fr.ng = fr.ns;
-    const V3 wo = V3{wo_in[3 * i], wo_in[3 * i + 1], wo_in[3 * i + 2]};
-    const V3 wi = V3{wi_in[3 * i], wi_in[3 * i + 1], wi_in[3 * i + 2]};
+    const Frame fr = query_frame();
+    const V3 wo = query_v3(wo_in, i), wi = query_v3(wi_in, i);
     const float u0 = u_in[2 * i], u1 = u_in[2 * i + 1];
     V3 f = V3{0.0f, 0.0f, 0.0f}, wi_s = f, f_s = f;
     float pdf = 0.0f, pdf_s = 0.0f;
@@ -248,19 +236,7 @@ __global__ void k_bsdf_query(const DevMaterial* __restrict__ materials, int mate
             }
         }
     }
-    float* o = out + 12 * i;
-    o[0] = f.x;
-    o[1] = f.y;
-    o[2] = f.z;
-    o[3] = pdf;
-    o[4] = wi_s.x;
-    o[5] = wi_s.y;
-    o[6] = wi_s.z;
-    o[7] = f_s.x;
-    o[8] = f_s.y;
-    o[9] = f_s.z;
-    o[10] = pdf_s;
-    o[11] = __int_as_float(sampled);
+    query_write(out, i, f, pdf, wi_s, f_s, pdf_s, sampled);
 }
 
 // the same for a Disney row (wf_disney.h): `d` is the row's block
@@ -268,13 +244,8 @@ __global__ void k_bsdf_query_disney(const DevDisney* __restrict__ d, int64_t n, 
                                     const float* __restrict__ u_in, float* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Frame fr;
-    fr.ss = V3{1.0f, 0.0f, 0.0f};
-    fr.ts = V3{0.0f, 1.0f, 0.0f};
-    fr.ns = V3{0.0f, 0.0f, 1.0f};
-    fr.ng = fr.ns;
-    const V3 wo = V3{wo_in[3 * i], wo_in[3 * i + 1], wo_in[3 * i + 2]};
-    const V3 wi = V3{wi_in[3 * i], wi_in[3 * i + 1], wi_in[3 * i + 2]};
+    const Frame fr = query_frame();
+    const V3 wo = query_v3(wo_in, i), wi = query_v3(wi_in, i);
     V3 f, wi_s = V3{0.0f, 0.0f, 0.0f}, f_s = wi_s;
     float pdf, pdf_s = 0.0f;
     int sampled = 0;
@@ -290,19 +261,7 @@ __global__ void k_bsdf_query_disney(const DevDisney* __restrict__ d, int64_t n, 
     } else {
         sampled = 0;
     }
-    float* o = out + 12 * i;
-    o[0] = f.x;
-    o[1] = f.y;
-    o[2] = f.z;
-    o[3] = pdf;
-    o[4] = wi_s.x;
-    o[5] = wi_s.y;
-    o[6] = wi_s.z;
-    o[7] = f_s.x;
-    o[8] = f_s.y;
-    o[9] = f_s.z;
-    o[10] = pdf_s;
-    o[11] = __int_as_float(sampled);
+    query_write(out, i, f, pdf, wi_s, f_s, pdf_s, sampled);
 }
 
 // the same for a lobe row (wf_lobes.h): BSDF::f and pdf under BSDF_ALL, sample_f under BSDF_ALL, so a specular lobe can be the
@@ -311,13 +270,8 @@ __global__ void k_bsdf_query_lobes(const DevLobeRow* __restrict__ row, int64_t n
                                    const float* __restrict__ u_in, float* __restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Frame fr;
-    fr.ss = V3{1.0f, 0.0f, 0.0f};
-    fr.ts = V3{0.0f, 1.0f, 0.0f};
-    fr.ns = V3{0.0f, 0.0f, 1.0f};
-    fr.ng = fr.ns;
-    const V3 wo = V3{wo_in[3 * i], wo_in[3 * i + 1], wo_in[3 * i + 2]};
-    const V3 wi = V3{wi_in[3 * i], wi_in[3 * i + 1], wi_in[3 * i + 2]};
+    const Frame fr = query_frame();
+    const V3 wo = query_v3(wo_in, i), wi = query_v3(wi_in, i);
     V3 f, wi_s = V3{0.0f, 0.0f, 0.0f}, f_s = wi_s;
     float pdf, pdf_s = 0.0f;
     int sampled = 0;
@@ -333,77 +287,27 @@ __global__ void k_bsdf_query_lobes(const DevLobeRow* __restrict__ row, int64_t n
     } else {
         sampled = 0;
     }
-    float* o = out + 12 * i;
-    o[0] = f.x;
-    o[1] = f.y;
-    o[2] = f.z;
-    o[3] = pdf;
-    o[4] = wi_s.x;
-    o[5] = wi_s.y;
-    o[6] = wi_s.z;
-    o[7] = f_s.x;
-    o[8] = f_s.y;
-    o[9] = f_s.z;
-    o[10] = pdf_s;
-    o[11] = __int_as_float(sampled);
+    query_write(out, i, f, pdf, wi_s, f_s, pdf_s, sampled);
 }
 
 extern "C" int pbrt_hip_bsdf_query(PbrtHipScene* s, int32_t material, int64_t n, const float* wo, const float* wi, const float* u, float* f,
                                    float* pdf, float* wi_s, float* f_s, float* pdf_s, int32_t* sampled_flags) try {
     if (!s) return PBRT_HIP_ERR_INVALID;
-    PbrtHipContext* ctx = s->ctx;
-    PB_ENTER(ctx);
-    auto invalid = [&](const char* why) {
-        ctx->last_error = std::string("pbrt_hip_bsdf_query: ") + why;
-        return PBRT_HIP_ERR_INVALID;
-    };
-    if (material < 0 || material >= s->d.n_materials) return invalid("material index out of range");
-    if (s->h_materials[material].type == kMatHair) return invalid("a hair row needs h per point: pbrt_hip_bsdf_query_hair");
-    if (n < 0 || n > ((int64_t)1 << 31)) return invalid("n must be in [0, 2^31]");
-    if (n == 0) return PBRT_HIP_OK;
-    if (!wo || !wi || !u) return invalid("null wo / wi / u");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    PB_ENTER(s->ctx);
     const size_t un = (size_t)n;
-    float *d_in = nullptr, *d_out = nullptr;
-    int rc = PBRT_HIP_OK;
-    if (!hip_ok(ctx, hipMalloc((void**)&d_in, un * 8 * sizeof(float)), "hipMalloc") ||
-        !hip_ok(ctx, hipMalloc((void**)&d_out, un * 12 * sizeof(float)), "hipMalloc"))
-        rc = PBRT_HIP_ERR_OOM;
-    if (rc == PBRT_HIP_OK && (!hip_ok(ctx, hipMemcpy(d_in, wo, un * 3 * sizeof(float), hipMemcpyHostToDevice), "H2D") ||
-                              !hip_ok(ctx, hipMemcpy(d_in + 3 * un, wi, un * 3 * sizeof(float), hipMemcpyHostToDevice), "H2D") ||
-                              !hip_ok(ctx, hipMemcpy(d_in + 6 * un, u, un * 2 * sizeof(float), hipMemcpyHostToDevice), "H2D")))
-        rc = PBRT_HIP_ERR_DEVICE;
-    std::vector<float> h;
-    if (rc == PBRT_HIP_OK) {
-        if (s->h_materials[material].type == kMatLobes)
-            hipLaunchKernelGGL(k_bsdf_query_lobes, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, s->d.lobe_rows + material, n,
-                               d_in, d_in + 3 * un, d_in + 6 * un, d_out);
-        else if (s->h_materials[material].type == kMatDisney)
-            hipLaunchKernelGGL(k_bsdf_query_disney, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, s->d.disney + material, n,
-                               d_in, d_in + 3 * un, d_in + 6 * un, d_out);
-        else
-            hipLaunchKernelGGL(k_bsdf_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, s->d.materials, material, n, d_in,
-                               d_in + 3 * un, d_in + 6 * un, d_out);
-        h.resize(un * 12);
-        if (!hip_ok(ctx, hipGetLastError(), "k_bsdf_query") || !hip_ok(ctx, hipStreamSynchronize(ctx->stream), "k_bsdf_query") ||
-            !hip_ok(ctx, hipMemcpy(h.data(), d_out, un * 12 * sizeof(float), hipMemcpyDeviceToHost), "D2H"))
-            rc = PBRT_HIP_ERR_DEVICE;
-    }
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    if (rc != PBRT_HIP_OK) return rc;
-    for (size_t i = 0; i < un; ++i) {
-        const float* o = &h[12 * i];
-        for (int k = 0; k < 3; ++k) {
-            if (f) f[3 * i + k] = o[k];
-            if (wi_s) wi_s[3 * i + k] = o[4 + k];
-            if (f_s) f_s[3 * i + k] = o[7 + k];
-        }
-        if (pdf) pdf[i] = o[3];
-        if (pdf_s) pdf_s[i] = o[10];
-        if (sampled_flags) std::memcpy(&sampled_flags[i], &o[11], 4);
-    }
-    return PBRT_HIP_OK;
+    return bsdf_query(
+        s, "pbrt_hip_bsdf_query", false, material, n, {{wo, 3}, {wi, 3}, {u, 2}}, "null wo / wi / u", "k_bsdf_query",
+        [&](const float* d_in, float* d_out) {
+            const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+            hipStream_t st = s->ctx->stream;
+            if (s->h_materials[material].type == kMatLobes)
+                hipLaunchKernelGGL(k_bsdf_query_lobes, grid, block, 0, st, s->d.lobe_rows + material, n, d_in, d_in + 3 * un, d_in + 6 * un, d_out);
+            else if (s->h_materials[material].type == kMatDisney)
+                hipLaunchKernelGGL(k_bsdf_query_disney, grid, block, 0, st, s->d.disney + material, n, d_in, d_in + 3 * un, d_in + 6 * un, d_out);
+            else
+                hipLaunchKernelGGL(k_bsdf_query, grid, block, 0, st, s->d.materials, material, n, d_in, d_in + 3 * un, d_in + 6 * un, d_out);
+        },
+        BsdfQueryOut{f, pdf, wi_s, f_s, pdf_s, sampled_flags});
 }
 PB_ABI_CATCH
 
@@ -481,31 +385,20 @@ extern "C" int pbrt_hip_light_sample_li(PbrtHipScene* s, int32_t light, int64_t 
     if (!u && !s->h_lights[light].delta) return invalid("null u for a light that is not a delta light");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const size_t un = (size_t)n;
-    float *d_in = nullptr, *d_out = nullptr;
-    int rc = PBRT_HIP_OK;
-    if (!hip_ok(ctx, hipMalloc((void**)&d_in, un * 5 * sizeof(float)), "hipMalloc") ||
-        !hip_ok(ctx, hipMalloc((void**)&d_out, un * 7 * sizeof(float)), "hipMalloc"))
-        rc = PBRT_HIP_ERR_OOM;
-    if (rc == PBRT_HIP_OK && (!hip_ok(ctx, hipMemcpy(d_in, p, un * 3 * sizeof(float), hipMemcpyHostToDevice), "H2D") ||
-                              (u && !hip_ok(ctx, hipMemcpy(d_in + 3 * un, u, un * 2 * sizeof(float), hipMemcpyHostToDevice), "H2D"))))
-        rc = PBRT_HIP_ERR_DEVICE;
     std::vector<float> h;
-    if (rc == PBRT_HIP_OK) {
-        ShadeConsts sc;
-        scene_shade_consts(s, &sc);
-        const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-        const float* d_u = u ? d_in + 3 * un : nullptr;
-        if (s->d.bvh.has_spheres == 2)
-            hipLaunchKernelGGL(k_light_query<true>, grid, block, 0, ctx->stream, sc, light, n, d_in, d_u, d_out);
-        else
-            hipLaunchKernelGGL(k_light_query<false>, grid, block, 0, ctx->stream, sc, light, n, d_in, d_u, d_out);
-        h.resize(un * 7);
-        if (!hip_ok(ctx, hipGetLastError(), "k_light_query") || !hip_ok(ctx, hipStreamSynchronize(ctx->stream), "k_light_query") ||
-            !hip_ok(ctx, hipMemcpy(h.data(), d_out, un * 7 * sizeof(float), hipMemcpyDeviceToHost), "D2H"))
-            rc = PBRT_HIP_ERR_DEVICE;
-    }
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
+    const int rc = run_point_query(
+        ctx, n, {{p, 3}, {u, 2}}, 7, "k_light_query",
+        [&](const float* d_in, float* d_out) {
+            ShadeConsts sc;
+            scene_shade_consts(s, &sc);
+            const dim3 grid((unsigned)((n + 255) / 256)), block(256);
+            const float* d_u = u ? d_in + 3 * un : nullptr;
+            if (s->d.bvh.has_spheres == 2)
+                hipLaunchKernelGGL(k_light_query<true>, grid, block, 0, ctx->stream, sc, light, n, d_in, d_u, d_out);
+            else
+                hipLaunchKernelGGL(k_light_query<false>, grid, block, 0, ctx->stream, sc, light, n, d_in, d_u, d_out);
+        },
+        &h);
     if (rc != PBRT_HIP_OK) return rc;
     for (size_t i = 0; i < un; ++i) {
         const float* o = &h[7 * i];
@@ -518,32 +411,6 @@ extern "C" int pbrt_hip_light_sample_li(PbrtHipScene* s, int32_t light, int64_t 
     return PBRT_HIP_OK;
 }
 PB_ABI_CATCH
-
-static int round_up_pow2(int v) {  // pbrt.rs:174-182
-    v -= 1;
-    v |= v >> 1;
-    v |= v >> 2;
-    v |= v >> 4;
-    v |= v >> 8;
-    v |= v >> 16;
-    return v + 1;
-}
-
-// The samples per pixel the sampler takes (stratified.rs:30-33: nx * ny; zerotwosequence.rs:20: the next power of two), for
-// wavefront_render and for pbrt_hip_camera_rays, whose outputs are sized by THAT count and not by the caller's spp. Returns the
-// refusal, or null.
-static const char* sampler_spp(const PbrtRenderParams& rp, int32_t* spp) {
-    *spp = rp.spp;
-    if (rp.sampler == PBRT_SAMPLER_STRATIFIED) {
-        if (rp.sampler_x < 1 || rp.sampler_y < 1 || (int64_t)rp.sampler_x * rp.sampler_y > 65536)
-            return "stratified sampler: sampler_x * sampler_y must be in [1, 65536]";
-        *spp = rp.sampler_x * rp.sampler_y;
-    } else if (rp.sampler == PBRT_SAMPLER_ZEROTWO) {
-        if (rp.spp > 65536) return "(0,2)-sequence sampler: spp too large";
-        *spp = round_up_pow2(rp.spp);
-    }
-    return nullptr;
-}
 
 extern "C" int pbrt_hip_camera_rays(PbrtHipScene* s, const PbrtCamera* camera, const PbrtRenderParams* params, int64_t capacity,
                                     PbrtRay* rays, uint64_t* stream_keys, float* p_film, int32_t* pixel_sample, int64_t* n_out) try {
@@ -562,44 +429,30 @@ extern "C" int pbrt_hip_camera_rays_moving_camera(PbrtHipScene* s, const PbrtCam
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (params->width <= 0 || params->height <= 0 || params->spp <= 0 || params->x0 > params->x1 || params->y0 > params->y1)
         return PBRT_HIP_ERR_INVALID;
-    int32_t n_tiles = 0;
-    const int world = params->tile_world <= 0 ? 1 : params->tile_world;
-    if (pbrt_hip_tile_partition_order(params->x0, params->y0, params->x1, params->y1, params->tile_rank, world, params->tile_order, nullptr, 0,
-                                      &n_tiles) != PBRT_HIP_OK) {
-        ctx->last_error = "camera rays: bad tile_rank / tile_world / tile_order";
-        return PBRT_HIP_ERR_INVALID;
-    }
-    int32_t spp = 0;  // as wavefront_render will fix them
-    if (const char* why = sampler_spp(*params, &spp)) {
+    int64_t n = 0;  // as wavefront_render will fix it
+    if (const char* why = export_ray_count(*params, &n)) {
         ctx->last_error = why;
         return PBRT_HIP_ERR_INVALID;
     }
-    const int64_t n = (int64_t)n_tiles * kTile * kTile * spp;  // whole tiles: pixels outside the bounds carry pixel = (-1, -1)
     *n_out = n;
     if (n == 0) return PBRT_HIP_OK;
     if (capacity < n || !rays || !stream_keys || !p_film || !pixel_sample) {
         ctx->last_error = "camera rays: output capacity too small (n_out holds the need)";
         return PBRT_HIP_ERR_INVALID;
     }
+    Staging dev(ctx);
     LiBatch b;
-    int rc = PBRT_HIP_OK;
-    if (!hip_ok(ctx, hipMalloc((void**)&b.out_rays, (size_t)n * sizeof(PbrtRay)), "hipMalloc") ||
-        !hip_ok(ctx, hipMalloc((void**)&b.out_keys, (size_t)n * sizeof(uint64_t)), "hipMalloc") ||
-        !hip_ok(ctx, hipMalloc((void**)&b.out_pfilm, (size_t)n * 2 * sizeof(float)), "hipMalloc") ||
-        !hip_ok(ctx, hipMalloc((void**)&b.out_pixel_sample, (size_t)n * 3 * sizeof(int32_t)), "hipMalloc"))
-        rc = PBRT_HIP_ERR_OOM;
-    if (rc == PBRT_HIP_OK) rc = wavefront_render(s, *camera, *params, nullptr, nullptr, &b, row);
-    if (rc == PBRT_HIP_OK && (!hip_ok(ctx, hipMemcpy(rays, b.out_rays, (size_t)n * sizeof(PbrtRay), hipMemcpyDeviceToHost), "D2H") ||
-                              !hip_ok(ctx, hipMemcpy(stream_keys, b.out_keys, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost), "D2H") ||
-                              !hip_ok(ctx, hipMemcpy(p_film, b.out_pfilm, (size_t)n * 2 * sizeof(float), hipMemcpyDeviceToHost), "D2H") ||
-                              !hip_ok(ctx, hipMemcpy(pixel_sample, b.out_pixel_sample, (size_t)n * 3 * sizeof(int32_t), hipMemcpyDeviceToHost), "D2H")))
+    b.out_rays = dev.alloc<PbrtRay>((size_t)n);
+    b.out_keys = dev.alloc<uint64_t>((size_t)n);
+    b.out_pfilm = dev.alloc<float>((size_t)n * 2);
+    b.out_pixel_sample = dev.alloc<int32_t>((size_t)n * 3);
+    if (dev.failed) return PBRT_HIP_ERR_OOM;
+    int rc = wavefront_render(s, *camera, *params, nullptr, nullptr, &b, row);
+    if (rc == PBRT_HIP_OK && (!dev.download(rays, b.out_rays, (size_t)n * sizeof(PbrtRay)) ||
+                              !dev.download(stream_keys, b.out_keys, (size_t)n * sizeof(uint64_t)) ||
+                              !dev.download(p_film, b.out_pfilm, (size_t)n * 2 * sizeof(float)) ||
+                              !dev.download(pixel_sample, b.out_pixel_sample, (size_t)n * 3 * sizeof(int32_t))))
         rc = PBRT_HIP_ERR_DEVICE;
-    if (!ctx->lost) {
-        (void)hipFree(b.out_rays);
-        (void)hipFree(b.out_keys);
-        (void)hipFree(b.out_pfilm);
-        (void)hipFree(b.out_pixel_sample);
-    }
     return rc;
 }
 PB_ABI_CATCH
@@ -771,74 +624,6 @@ int sort_pairs_u32(hipStream_t st, void* temp, size_t* temp_bytes, const uint32_
 int exclusive_scan_u64(hipStream_t st, void* temp, size_t* temp_bytes, const unsigned long long* in, unsigned long long* out, size_t n);
 }
 
-// ---- HaltonSampler host side: prime tables and compute_radical_inverse_permutations (lowdiscrepancy.rs:11-170,
-// 333-349: RNG::default + shuffle per prime), HaltonSampler::new constants (halton.rs:40-98) ----
-namespace {
-struct HostPcg {  // rng.rs
-    uint64_t state = 0x853c49e6748fea9bULL, inc = 0xda3e39cb94b95bdbULL;
-    uint32_t u32() {
-        uint64_t old = state;
-        state = old * 0x5851f42d4c957f2dULL + inc;
-        uint32_t xs = (uint32_t)(((old >> 18) ^ old) >> 27), rot = (uint32_t)(old >> 59);
-        return (xs >> rot) | (xs << ((~rot + 1u) & 31u));
-    }
-    uint32_t bounded(uint32_t b) {
-        uint32_t threshold = (~b + 1u) % b;
-        for (;;) {
-            uint32_t r = u32();
-            if (r >= threshold) return r % b;
-        }
-    }
-};
-void halton_host_tables(std::vector<uint32_t>* primes_and_sums, std::vector<uint16_t>* perms) {
-    std::vector<uint32_t> primes;
-    for (uint32_t v = 2; primes.size() < 1000; ++v) {
-        bool is_prime = true;
-        for (uint32_t q : primes) {
-            if (q * q > v) break;
-            if (v % q == 0) {
-                is_prime = false;
-                break;
-            }
-        }
-        if (is_prime) primes.push_back(v);
-    }
-    primes_and_sums->assign(2000, 0);
-    uint32_t acc = 0;
-    for (int i = 0; i < 1000; ++i) {
-        (*primes_and_sums)[i] = primes[i];
-        (*primes_and_sums)[1000 + i] = acc;
-        acc += primes[i];
-    }
-    perms->resize(acc);
-    HostPcg rng;
-    uint16_t* p = perms->data();
-    for (int i = 0; i < 1000; ++i) {
-        int count = (int)primes[i];
-        for (int j = 0; j < count; ++j) p[j] = (uint16_t)j;
-        for (int j = 0; j < count; ++j) std::swap(p[j], p[j + (int)rng.bounded((uint32_t)(count - j))]);  // sampling.rs:280-287
-        p += count;
-    }
-}
-void extended_gcd(uint64_t a, uint64_t b, int64_t* x, int64_t* y) {  // halton.rs:51-61
-    if (b == 0) {
-        *x = 1;
-        *y = 0;
-        return;
-    }
-    int64_t d = (int64_t)(a / b), xp = 0, yp = 0;
-    extended_gcd(b, a % b, &xp, &yp);
-    *x = yp;
-    *y = xp - d * yp;
-}
-uint64_t multiplicative_inverse(int64_t a, int64_t n) {  // halton.rs:40-49
-    int64_t x = 0, y = 0;
-    extended_gcd((uint64_t)a, (uint64_t)n, &x, &y);
-    int64_t r = x - (x / n) * n;
-    return (uint64_t)(r < 0 ? r + n : r);
-}
-}  // namespace
-
 // ---- wavefront_render in stages: one plain struct holds the render, its member functions are the stages in order ----
 namespace {
 // the four events of a render; they go with this object on every way out
@@ -874,39 +659,26 @@ struct ExpandBufs {
 constexpr int kSortFrom = PB_SORT_FROM;  // first sorted wavefront: the first bounce still follows the pixel order of its camera rays
 static_assert(kSortFrom >= 1, "wavefront 0 is the identity queue k_generate leaves: it has no sort entries");
 
-// One render: what it holds between its stages, and the stages in the order run() goes through them. The device blocks belong to
-// the DevBuf of run()'s own frame.
-struct RenderJob {
+static_assert(kPlanTile == kTile && kPlanPathRecBits == kPathRecBits, "host_render.h plans the tiles and the sort entries of these kernels");
+
+// One render: the plan (host_render.h: everything decided about the call, on the host), what the device half holds between its
+// stages, and the stages in the order run() goes through them. The device blocks belong to the DevBuf of run()'s own frame.
+struct RenderJob : RenderPlan {
     PbrtHipScene* s;
     PbrtHipContext* ctx;
     hipStream_t st;
     const LiBatch* li;
     float* d_film;
     const DevMotion* camera_motion;  // the animated camera's row, or null (kernel_select.h: generate_key)
-    // stage 1, the caller's parameters checked and normalised
-    PbrtRenderParams rp;  // li substitution, the sampler's samples per pixel, AO's round_count, an export's single pass
-    bool li_mode, export_mode;
-    bool tabulated;  // not the RandomSampler
-    bool direct;     // DirectLighting, Whitted and AO share the per-vertex stage machine of k_shade_direct
-    bool box;        // the 0.5 box filter: exact in-order accumulation (k_film_accumulate)
-    float frx, fry;
-    int32_t sb[4];  // pbrt_hip_sample_bounds of the film under the filter
-    int world, rank;
-    // stages 2 - 6
-    int n_pix = 0, spp_pass = 0;
-    int64_t valid_pixels = 0;
-    size_t N = 0;  // concurrent paths of a pass
+    TraceChoice trace;               // kernel_select.h
+    hipError_t mem_query;            // what hipMemGetInfo answered where the plan needed the free bytes
     PathState ps;
     Queues q[2];
-    bool sort_rays = false, sort_shade = false, bin_shade = false;
     SortBufs ray_sort;    // Morton order of the bounce rays: one (cell, packed rays) pair per path
     ExpandBufs ray_expand;
     SortBufs shade_sort;  // shade_order 2: keys, the sorted queue positions (vals)
     uint32_t* shade_positions = nullptr;
-    TraceChoice trace;                 // kernel_select.h
     uint32_t* special_list = nullptr;  // rays the wide kernel leaves to the binary one (wide_bvh.h)
-    std::vector<int> prefix;           // light-sample prefix sums
-    SamplerParams smp{};
     DirectState ds{};
     float* d_filter = nullptr;
     float4* accum = nullptr;
@@ -921,10 +693,8 @@ struct RenderJob {
         ctx->last_error = m;
         return PBRT_HIP_ERR_INVALID;
     }
-    int round_count(int n) const { return rp.sampler == PBRT_SAMPLER_ZEROTWO ? round_up_pow2(n) : n; }  // Sampler::round_count
-    const char* normalise_params(const PbrtRenderParams& rp_in);
-    int size_pass();
-    int alloc_path_buffers(DevBuf& buf, bool* ok);
+    int query_sort_sizes(RenderStep upto);
+    void alloc_path_buffers(DevBuf& buf, bool* ok);
     int setup_sampler(DevBuf& buf, bool* ok);
     int setup_light_distribution(const SceneNeeds& needs);
     PassParams pass_params(int s0) const;
@@ -936,91 +706,24 @@ struct RenderJob {
     int run(const PbrtCamera& camera, PbrtRenderStats* stats);
 };
 
-// stage 1: returns the first refusal, or null
-const char* RenderJob::normalise_params(const PbrtRenderParams& rp_in) {
-    rp = rp_in;
-    li_mode = li && li->d_rays;
-    export_mode = li && li->out_rays;
-    if (li_mode) {  // the batch stands in for a 1-spp "frame" of n pixels in a row; nothing of the film plumbing is used
-        if (li->n <= 0 || li->n > (1ll << 28)) return "li: batch size must be in [1, 2^28]";
-        rp.width = (int32_t)li->n;
-        rp.height = 1;
-        rp.spp = 1;
-        rp.x0 = rp.y0 = 0;
-        rp.x1 = rp.width;
-        rp.y1 = 1;
-        rp.tile_rank = 0;
-        rp.tile_world = 1;
-        rp.spp_per_pass = 1;
-        rp.sampler = PBRT_SAMPLER_RANDOM;  // the caller's Sampler is a RandomSampler stream per ray (sampler.rs:452, random.rs)
-        rp.filter_table = nullptr;
+// The rocPRIM scratch sizes of the sorts the plan switched on. They are asked where they always were among the plan's refusals:
+// the ray sort's behind ray_order, the shade sort's behind shade_order.
+int RenderJob::query_sort_sizes(RenderStep upto) {
+    if (upto == RenderStep::RayOrder && sort_rays) {
+        if (pb::sort_pairs_u32(st, nullptr, &ray_sort.tmp_bytes, nullptr, nullptr, nullptr, nullptr, N, kSortKeyBits) != 0)
+            return invalid("rocPRIM radix sort: size query failed");
+        const size_t n_scan = (size_t)pb::ray_expand_blocks((uint32_t)N) + 1;  // the last element: the sections' totals
+        if (pb::exclusive_scan_u64(st, nullptr, &ray_expand.tmp_bytes, nullptr, nullptr, n_scan) != 0)
+            return invalid("rocPRIM scan: size query failed");
     }
-    if (rp.width <= 0 || rp.height <= 0 || rp.spp <= 0) return "width, height and spp must be positive";
-    // ---- sampler: samples per pixel and Sampler::round_count (stratified.rs:30-33, zerotwosequence.rs:20, 62-64) ----
-    if (rp.sampler < PBRT_SAMPLER_RANDOM || rp.sampler > PBRT_SAMPLER_HALTON) return "unknown sampler";
-    tabulated = rp.sampler != PBRT_SAMPLER_RANDOM;
-    if (tabulated && (rp.sampler_dims < 0 || rp.sampler_dims > 63)) return "sampler_dims must be in [0, 63]";
-    if (const char* why = sampler_spp(rp, &rp.spp)) return why;
-    if (rp.integrator == PBRT_INTEGRATOR_AO && rp.ao_samples >= 1 && rp.ao_samples <= 65535 && tabulated)
-        rp.ao_samples = round_count(rp.ao_samples);  // ao.rs:36
-    frx = rp.filter_radius[0] > 0.0f ? rp.filter_radius[0] : 0.5f;
-    fry = rp.filter_radius[1] > 0.0f ? rp.filter_radius[1] : 0.5f;
-    box = true;
-    if (rp.filter_table) {
-        if (frx != 0.5f || fry != 0.5f) box = false;
-        for (int i = 0; i < 256; ++i)
-            if (rp.filter_table[i] != 1.0f) box = false;
-    } else {
-        frx = fry = 0.5f;
-    }
-    if (frx > 64.0f || fry > 64.0f) return "filter radius too large";
-    pbrt_hip_sample_bounds(rp.width, rp.height, frx, fry, sb);
-    if (rp.x0 < sb[0] || rp.y0 < sb[1] || rp.x1 > sb[2] || rp.y1 > sb[3] || rp.x0 > rp.x1 || rp.y0 > rp.y1)
-        return "pixel bounds outside the film's sample bounds";
-    if (rp.integrator < PBRT_INTEGRATOR_PATH || rp.integrator > PBRT_INTEGRATOR_AO) return "integrator must be a PbrtIntegratorKind";
-    direct = rp.integrator != PBRT_INTEGRATOR_PATH;
-    if (direct && rp.max_depth > 64) return "direct lighting / Whitted: max_depth > 64 (frame stack)";
-    if (rp.integrator == PBRT_INTEGRATOR_AO && (rp.ao_samples < 1 || rp.ao_samples > 65535))
-        return "ambient occlusion: ao_samples must be in [1, 65535]";
-    if (rp.max_depth < 0 || rp.max_depth > 1 << 20) return "bad max_depth";
-    world = rp.tile_world <= 0 ? 1 : rp.tile_world;
-    rank = rp.tile_rank;
-    if (rank < 0 || rank >= world) return "tile_rank outside [0, tile_world)";
-    if (rp.tile_order != PBRT_TILE_ORDER_MORTON && rp.tile_order != PBRT_TILE_ORDER_ROW_MAJOR) return "tile_order must be a PbrtTileOrder";
-    if (rp.samples_per_wave < 0 || rp.samples_per_wave > 64 || (rp.samples_per_wave & (rp.samples_per_wave - 1)) != 0)
-        return "samples_per_wave must be 0 (library default) or a power of two up to 64";
-    if (export_mode) rp.spp_per_pass = rp.spp;  // one pass: the export is indexed by the paths of that pass
-    return nullptr;
-}
-
-// stage 2: the samples of a pixel one pass holds
-int RenderJob::size_pass() {
-    spp_pass = rp.spp_per_pass > 0 ? rp.spp_per_pass : 0;
-    if (spp_pass == 0) {
-        // As many samples of a pixel in flight as two thirds of the free HBM hold (the other integrators: half of it, as
-        // ever). The path integrator takes 500 B per path:
-        // 192 B rays (two generations) + 96 B hits + 104 B pending estimates (two generations) + 52 B persistent state +
-        // 32 B queues + 12 B sort pairs (one per path: keys in / out, sorted values) + 12 B special-list slots; 526 leaves
-        // room for the sampler tables. The others keep one
-        // generation and add their stage machine's frame stack. A whole 64-spp 1080p frame is 133 M paths = 67 GB of the
-        // 288 GB and runs 6 large wavefronts instead of 48 small ones (+10 % on config 3: fewer launches and host round
-        // trips, shorter tails). The share was one half while a path took 376 B; at 500 B a half of 280 GB free would just
-        // admit the 265 M paths (133 GB) of a 32-spp pass of a 4K frame, two thirds (355 M paths) do with room to spare.
-        size_t free_b = 0, total_b = 0;
-        HIP_TRY(ctx, hipMemGetInfo(&free_b, &total_b));
-        for (const auto& b : ctx->block_cache)
-            if (!b.in_use) free_b += b.bytes;  // blocks kept from the previous render are available to this one
-        const int64_t per_path = rp.integrator == PBRT_INTEGRATOR_PATH ? 526 : 400 + 24 + 48ll * std::max(1, rp.max_depth);
-        const size_t share = rp.integrator == PBRT_INTEGRATOR_PATH ? free_b / 3 * 2 : free_b / 2;
-        const int64_t target_paths = std::max<int64_t>(1ll << 20, std::min<int64_t>(1ll << 28, (int64_t)share / per_path));
-        spp_pass = (int)std::max<int64_t>(1, std::min<int64_t>(rp.spp, target_paths / n_pix));
-    }
-    spp_pass = std::min(spp_pass, rp.spp);
+    if (upto == RenderStep::ShadeOrder && sort_shade &&
+        pb::sort_pairs_u32(st, nullptr, &shade_sort.tmp_bytes, nullptr, nullptr, nullptr, nullptr, N, 3) != 0)
+        return invalid("rocPRIM radix sort: size query failed");
     return PBRT_HIP_OK;
 }
 
-// stage 3: path state, queues, sort buffers (allocation failures land in *ok; a refusal is returned)
-int RenderJob::alloc_path_buffers(DevBuf& buf, bool* ok) {
+// stage 3: path state, queues, sort buffers in the sizes the plan states (allocation failures land in *ok)
+void RenderJob::alloc_path_buffers(DevBuf& buf, bool* ok) {
     ps.n_paths = N;
     ps.two_level = s->d.bvh.instanced ? 1 : 0;
     ps.ray = buf.alloc<float4>(N * 6, ok);
@@ -1051,65 +754,35 @@ int RenderJob::alloc_path_buffers(DevBuf& buf, bool* ok) {
             qk.key_inv[a] = hi > lo ? 1.0f / (hi - lo) : 0.0f;
         }
     }
-    // ray-queue sort (spatial order for the bounce rays): keys in / out, sorted entries, rocPRIM scratch
-    // only the path integrator's later bounces are incoherent; the stage machine of the other integrators keeps
-    // shooting from the camera rays' hit points, which are already in pixel order (AO: -6 % with the sort).
-    // PbrtRenderParams.ray_order = 1 leaves the queues as the shading kernel filled them (results do not depend on it).
-    if (rp.ray_order < 0 || rp.ray_order > 1) return invalid("ray_order must be 0 (Morton order from the second bounce on) or 1 (queue order)");
-    // What is sorted is one pair per path (wf_ray_expand.h), whose value packs the record index into kPathRecBits bits: the
-    // passes size_pass makes stay within that; a caller's own spp_per_pass beyond it is traced in queue order.
-    sort_rays = rp.ray_order == 0 && rp.integrator == PBRT_INTEGRATOR_PATH && N <= ((size_t)1 << kPathRecBits);
-    if (sort_rays) {
+    if (sort_rays) {  // ray-queue sort: keys in / out, sorted entries, rocPRIM scratch; the expansion's counts and offsets
         SortBufs& rs = ray_sort;
         rs.keys[0] = buf.alloc<uint32_t>(N, ok);
         rs.keys[1] = buf.alloc<uint32_t>(N, ok);
         rs.vals = buf.alloc<uint32_t>(N, ok);
-        if (pb::sort_pairs_u32(st, nullptr, &rs.tmp_bytes, rs.keys[0], rs.keys[1], rs.vals, rs.vals, N, kSortKeyBits) != 0)
-            return invalid("rocPRIM radix sort: size query failed");
         rs.tmp = buf.alloc<char>(rs.tmp_bytes, ok);
         ExpandBufs& ex = ray_expand;
-        const size_t n_scan = (size_t)pb::ray_expand_blocks((uint32_t)N) + 1;  // the last element: the sections' totals
+        const size_t n_scan = (size_t)pb::ray_expand_blocks((uint32_t)N) + 1;
         ex.counts = buf.alloc<unsigned long long>(n_scan, ok);
         ex.offsets = buf.alloc<unsigned long long>(n_scan, ok);
-        if (pb::exclusive_scan_u64(st, nullptr, &ex.tmp_bytes, ex.counts, ex.offsets, n_scan) != 0)
-            return invalid("rocPRIM scan: size query failed");
         ex.tmp = buf.alloc<char>(ex.tmp_bytes, ok);
     }
-    trace = choose_trace(s);
-    if (!trace.ok) return PBRT_HIP_ERR_INVALID;
     // rays the wide kernel leaves to the binary one (wide_bvh.h): room for every entry of a trace queue
     special_list = trace.kind == TraceKind::Wide ? buf.alloc<uint32_t>(N * 3, ok) : nullptr;
-    // sort-by-material shading (wf_path.h): PbrtRenderParams.shade_order; 2 = the whole shade queue in material order
-    if (rp.shade_order < 0 || rp.shade_order > 2) return invalid("shade_order must be 0 (queue order), 1 (by material inside blocks) or 2 (sorted queue)");
-    sort_shade = rp.shade_order == 2 && rp.integrator == PBRT_INTEGRATOR_PATH;
-    bin_shade = rp.shade_order == 1 && rp.integrator == PBRT_INTEGRATOR_PATH;
     if (sort_shade) {
         SortBufs& ss = shade_sort;
         ss.keys[0] = buf.alloc<uint32_t>(N, ok);
         ss.keys[1] = buf.alloc<uint32_t>(N, ok);
         shade_positions = buf.alloc<uint32_t>(N, ok);
         ss.vals = buf.alloc<uint32_t>(N, ok);
-        if (pb::sort_pairs_u32(st, nullptr, &ss.tmp_bytes, ss.keys[0], ss.keys[1], shade_positions, ss.vals, N, 3) != 0)
-            return invalid("rocPRIM radix sort: size query failed");
         ss.tmp = buf.alloc<char>(ss.tmp_bytes, ok);
     }
-    return PBRT_HIP_OK;
 }
 
-// stage 4: SamplerParams of the render: the Halton tables and constants, the requested 2D arrays, the table sizes
+// stage 4: the device side of the plan's SamplerParams: the per-path counters, the Halton tables (uploaded on first use), the
+// PixelSampler tables and the list of requested arrays
 int RenderJob::setup_sampler(DevBuf& buf, bool* ok) {
-    prefix.assign(s->d.n_lights + 1, 0);
-    for (int i = 0; i < s->d.n_lights; ++i)  // directlighting.rs:58-62: round_count with a tabulating sampler
-        prefix[i + 1] = prefix[i] + (tabulated ? round_count(s->light_samples[i]) : s->light_samples[i]);
-    // ---- PixelSampler tables: n_dims 1D + n_dims 2D dimensions and the requested 2D arrays, per pixel ----
-    smp.kind = rp.sampler;
-    smp.n_dims = rp.sampler_dims;
-    smp.nx = rp.sampler_x;
-    smp.ny = rp.sampler_y;
-    smp.jitter = rp.sampler_jitter;
     ps.samp = buf.alloc<int>(N, ok);
     if (rp.sampler == PBRT_SAMPLER_HALTON) {
-        smp.n_dims = 0;  // nothing is tabulated per pixel: every value is a function of (sample index, dimension)
         if (!ctx->d_halton_primes) {
             std::vector<uint32_t> primes;
             std::vector<uint16_t> perms;
@@ -1121,56 +794,14 @@ int RenderJob::setup_sampler(DevBuf& buf, bool* ok) {
         }
         smp.primes = ctx->d_halton_primes;
         smp.perms = ctx->d_halton_perms;
-        // HaltonSampler::new(spp, film.get_sample_bounds(), false) (halton.rs:63-98)
-        const int res[2] = {sb[2] - sb[0], sb[3] - sb[1]};
-        for (int i = 0; i < 2; ++i) {
-            int base = i == 0 ? 2 : 3, scale = 1, exp = 0;
-            while (scale < std::min(128, res[i])) {
-                scale *= base;
-                ++exp;
-            }
-            smp.h_scale[i] = scale;
-            smp.h_exp[i] = exp;
-        }
-        smp.h_stride = smp.h_scale[0] * smp.h_scale[1];
-        smp.h_minv[0] = (unsigned int)multiplicative_inverse(smp.h_scale[1], smp.h_scale[0]);
-        smp.h_minv[1] = (unsigned int)multiplicative_inverse(smp.h_scale[0], smp.h_scale[1]);
     }
     if (tabulated) {
-        std::vector<int2> arrays;
-        int64_t elems = (int64_t)smp.n_dims * rp.spp * 3;
-        smp.off2 = smp.n_dims * rp.spp;
-        auto request_2d_array = [&](int n) {  // sampler.rs:41-46
-            arrays.push_back(make_int2(n, (int)elems));
-            elems += (int64_t)n * rp.spp * 2;
-        };
-        if (rp.integrator == PBRT_INTEGRATOR_DIRECT && rp.light_strategy == 0) {
-            for (int i = 0; i < rp.max_depth; ++i)  // directlighting.rs:64-75
-                for (int k = 0; k < s->d.n_lights; ++k) {
-                    request_2d_array(prefix[k + 1] - prefix[k]);
-                    request_2d_array(prefix[k + 1] - prefix[k]);
-                }
-        } else if (rp.integrator == PBRT_INTEGRATOR_AO) {
-            request_2d_array(rp.ao_samples);  // ao.rs:37
-        }
-        if (arrays.size() > 0x7fff) return invalid("too many sample arrays (max_depth x lights)");
-        if (elems * n_pix * 4 > (64ll << 30) || elems >= (1ll << 31))
-            return invalid("sampler tables exceed 64 GB: lower spp, sampler_dims or the light sample counts");
-        smp.n_arrays = (int)arrays.size();
-        smp.array_end_dim = 5 + 2 * smp.n_arrays;  // sampler.rs:344-345
-        if (rp.sampler == PBRT_SAMPLER_HALTON) {
-            // start_pixel fills the arrays' dimensions 5..array_end_dim (sampler.rs:355-368); the first one past the
-            // prime table indexes PRIME_SUMS out of range (halton.rs:100-108) and the reference panics there
-            if (smp.array_end_dim > 1000) return invalid("Halton sampler: too many sample arrays for 1000 dimensions");
-            elems = 0;
-        }
-        smp.n_elems = (int)elems;
-        smp.tables = buf.alloc<float>((size_t)elems * n_pix, ok);
+        smp.tables = buf.alloc<float>((size_t)smp.n_elems * n_pix, ok);
         int2* d_arrays = buf.alloc<int2>(arrays.size(), ok);
         smp.arrays = d_arrays;
         if (*ok && !arrays.empty())
             HIP_TRY(ctx, hipMemcpyAsync(d_arrays, arrays.data(), arrays.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-        if (*ok) HIP_TRY(ctx, hipStreamSynchronize(st));  // `arrays` leaves scope
+        if (*ok) HIP_TRY(ctx, hipStreamSynchronize(st));  // as ever: the list is up before anything else of the render is queued
     }
     return PBRT_HIP_OK;
 }
@@ -1180,18 +811,11 @@ int RenderJob::setup_sampler(DevBuf& buf, bool* ok) {
 int RenderJob::setup_light_distribution(const SceneNeeds& needs) {
     // "uniform", or one light -> uniform
     sc.distrib = (rp.light_strategy == 0 || s->d.n_lights == 1) ? s->d.light_distrib_uniform : s->d.light_distrib_power;
-    if (rp.integrator == PBRT_INTEGRATOR_PATH && (rp.light_strategy < 0 || rp.light_strategy > 2))
-        return invalid("path: light_strategy must be 0 (uniform), 1 (power) or 2 (spatial)");
-    if (rp.integrator == PBRT_INTEGRATOR_PATH && rp.light_strategy == 2 && s->d.n_lights > 1) {
-        // create_light_sample_distribution("spatial") -> SpatialLightDistribution::new(scene, 64) (lightdistrib.rs:85-107, 228)
+    if (spatial) {
         if (!s->d_spatial) {
-            const float *mn = s->d.bvh.root_min, *mx = s->d.bvh.root_max;
-            float diag[3] = {mx[0] - mn[0], mx[1] - mn[1], mx[2] - mn[2]};
-            int ext = (diag[0] > diag[1] && diag[0] > diag[2]) ? 0 : (diag[1] > diag[2] ? 1 : 2);
-            for (int i = 0; i < 3; ++i) s->spatial_voxels[i] = std::max(1, (int)std::round(diag[i] / diag[ext] * 64.0f));
+            for (int i = 0; i < 3; ++i) s->spatial_voxels[i] = spatial_voxels[i];
             size_t n_voxels = (size_t)s->spatial_voxels[0] * s->spatial_voxels[1] * s->spatial_voxels[2];
             size_t floats = n_voxels * (size_t)(2 * s->d.n_lights + 2);
-            if (floats > (1ull << 30)) return invalid("spatial light distribution: voxels x lights exceed 4 GB; use \"power\"");
             void* p = nullptr;
             HIP_TRY(ctx, hipMalloc(&p, floats * sizeof(float)));
             s->allocs.push_back(p);
@@ -1207,42 +831,13 @@ int RenderJob::setup_light_distribution(const SceneNeeds& needs) {
     return PBRT_HIP_OK;
 }
 
-// stage 6: the PassParams of the pass that starts at sample s0
+// stage 6: the plan's PassParams of the pass that starts at sample s0, with this call's device pointers
 PassParams RenderJob::pass_params(int s0) const {
-    PassParams pp;
-    pp.smp = smp;
-    pp.n_pix = n_pix;
-    pp.n_samples = std::min(spp_pass, rp.spp - s0);
-    // PbrtRenderParams.samples_per_wave: the largest power of two <= the request that divides the pass's samples per pixel
-    // default: a wave = the samples of ONE pixel (as many as the pass has, up to 64). The tabulating samplers keep the
-    // old layout: their tables are [element][pixel], read coalesced when a wave's lanes are 64 pixels of one sample
-    const int want = rp.samples_per_wave > 0 ? rp.samples_per_wave : ((tabulated && rp.sampler != PBRT_SAMPLER_HALTON) ? 1 : 64);
-    pp.group_shift = 0;
-    while ((2 << pp.group_shift) <= want && pp.group_shift < 6 && pp.n_samples % (2 << pp.group_shift) == 0) ++pp.group_shift;
-    if (li_mode || export_mode) pp.group_shift = 0;  // batches of rays / the exported camera rays keep the caller's order
-    pp.sample0 = s0;
-    pp.spp = rp.spp;
-    pp.width = rp.width;
-    pp.height = rp.height;
-    pp.x0 = rp.x0;
-    pp.y0 = rp.y0;
-    pp.x1 = rp.x1;
-    pp.y1 = rp.y1;
-    pp.sb_x0 = sb[0];
-    pp.sb_y0 = sb[1];
-    pp.sb_w = sb[2] - sb[0];
-    pp.seed = rp.seed;
-    pp.max_depth = rp.max_depth;
-    pp.rr_threshold = rp.rr_threshold;
-    pp.light_strategy = rp.light_strategy;
-    pp.filter_rx = frx;
-    pp.filter_ry = fry;
+    PassParams pp = RenderPlan::pass_params(s0);
     pp.filter_table = d_filter;
-    pp.max_sample_luminance = rp.max_sample_luminance > 0.0f ? rp.max_sample_luminance : INFINITY;
     pp.stream_keys = li_mode ? li->d_keys : nullptr;
     return pp;
 }
-
 #define RENDER_TRY(call) \
     if (rc == PBRT_HIP_OK && !hip_ok(ctx, (call), #call)) rc = PBRT_HIP_ERR_DEVICE;
 
@@ -1438,50 +1033,39 @@ void RenderJob::film_stage(const PassParams& pp, uint32_t n_paths, bool last_pas
     }
 }
 
-// stage 8, the driver: tiles, the stages above, then per pass the camera rays, the wavefront loop and the film
+// stage 8, the driver: the plan's refusals, the stages above, then per pass the camera rays, the wavefront loop and the film
 int RenderJob::run(const PbrtCamera& camera, PbrtRenderStats* stats) {
+    // A refusal surfaces where it always has among the calls that can fail on the device: `upto` names the last step before the next such call
+    auto refused = [&](RenderStep upto) { return refusal && refused_at <= upto; };
+    if (refused(RenderStep::Params)) return invalid(refusal);
     if (d_film) HIP_TRY(ctx, hipMemsetAsync(d_film, 0, (size_t)rp.width * rp.height * 4 * sizeof(float), st));
-
-    // tiles of the sample bounds (integrator.rs:402-409), dealt round-robin in rp.tile_order to the GPUs
-    std::vector<int2> origins;
-    if (li_mode) {
-        origins.assign((size_t)((li->n + kTile * kTile - 1) / (kTile * kTile)), make_int2(0, 0));  // 256 rays per "tile"
-    } else {
-        int32_t n_mine = 0;
-        if (pbrt_hip_tile_partition_order(rp.x0, rp.y0, rp.x1, rp.y1, rank, world, rp.tile_order, nullptr, 0, &n_mine) != PBRT_HIP_OK)
-            return invalid("tile partition: too many tiles");
-        origins.resize(n_mine);
-        pbrt_hip_tile_partition_order(rp.x0, rp.y0, rp.x1, rp.y1, rank, world, rp.tile_order, (int32_t*)origins.data(), n_mine, &n_mine);
-    }
+    if (refused(RenderStep::Tiles)) return invalid(refusal);
     if (origins.empty()) {
         HIP_TRY(ctx, hipStreamSynchronize(st));
         if (stats) *stats = local;
         return PBRT_HIP_OK;
     }
-    n_pix = (int)origins.size() * kTile * kTile;
-    for (const int2& o : origins)
-        valid_pixels += (int64_t)(std::min(o.x + kTile, rp.x1) - o.x) * (std::min(o.y + kTile, rp.y1) - o.y);
-    if (li_mode) valid_pixels = li->n;
-    if (int rc = size_pass()) return rc;
-    if (export_mode && spp_pass != rp.spp) return invalid("camera rays: too many samples for one pass");
-    N = (size_t)n_pix * spp_pass;
-    if (N * 4 >= (1ull << 32)) return invalid("too many concurrent paths for 32-bit queue entries; lower spp_per_pass");
+    if (!hip_ok(ctx, mem_query, "hipMemGetInfo(&free_b, &total_b)")) return PBRT_HIP_ERR_DEVICE;
+    if (refused(RenderStep::RayOrder)) return invalid(refusal);
+    if (int rc = query_sort_sizes(RenderStep::RayOrder)) return rc;
+    if (refused(RenderStep::ShadeOrder)) return invalid(refusal);
+    if (int rc = query_sort_sizes(RenderStep::ShadeOrder)) return rc;
+    if (refusal) return invalid(refusal);
 
     // the device blocks of the call: released (or, on a lost context, kept for good) when this frame ends, after the drain below
     DevBuf buf(ctx);
     bool ok = true;
-    if (int rc = alloc_path_buffers(buf, &ok)) return rc;
+    alloc_path_buffers(buf, &ok);
     if (int rc = setup_sampler(buf, &ok)) return rc;
     int* d_prefix = buf.alloc<int>(prefix.size(), &ok);
     if (direct) {
         ds.stage = buf.alloc<int>(N, &ok);
         ds.ld_acc = buf.alloc<float4>(N, &ok);
         ds.frames = buf.alloc<float4>(N * (size_t)std::max(1, rp.max_depth) * 3, &ok);
-        ds.light_strategy = rp.light_strategy;
-        ds.mode = rp.integrator;
-        ds.ao_samples = rp.ao_samples;
-        ds.ao_cos_sample = rp.light_strategy != 0;
-        if (prefix.back() >= 0xfff0) return invalid("too many light samples per vertex");
+        ds.light_strategy = ds_light_strategy;
+        ds.mode = ds_mode;
+        ds.ao_samples = ds_ao_samples;
+        ds.ao_cos_sample = ds_ao_cos_sample;
     }
     if (!box) {
         d_filter = buf.alloc<float>(256, &ok);
@@ -1502,7 +1086,6 @@ int RenderJob::run(const PbrtCamera& camera, PbrtRenderStats* stats) {
     cam.shutter_open = camera.shutter_open;
     cam.shutter_close = camera.shutter_close;
     cam.kind = camera.kind;
-    if (camera.kind < PBRT_CAMERA_PERSPECTIVE || camera.kind > PBRT_CAMERA_ENVIRONMENT) return invalid("unknown camera kind");
 
     // the scene's tables and, from them, this render's shading kernels (kernel_select.h)
     const SceneNeeds needs = scene_needs(s);
@@ -1571,8 +1154,33 @@ int RenderJob::run(const PbrtCamera& camera, PbrtRenderStats* stats) {
 
 int wavefront_render(PbrtHipScene* s, const PbrtCamera& camera, const PbrtRenderParams& rp_in, float* d_film,
                      PbrtRenderStats* stats, const LiBatch* li, const DevMotion* camera_motion) {
-    RenderJob job{s, s->ctx, s->ctx->stream, li, d_film, camera_motion};
-    if (const char* why = job.normalise_params(rp_in)) return job.invalid(why);
+    PbrtHipContext* ctx = s->ctx;
+    const RenderCall call = li && li->d_rays ? RenderCall::Li : li && li->out_rays ? RenderCall::Export : RenderCall::Frame;
+    RenderSceneFacts facts;
+    std::memcpy(facts.root_min, s->d.bvh.root_min, sizeof(facts.root_min));
+    std::memcpy(facts.root_max, s->d.bvh.root_max, sizeof(facts.root_max));
+    facts.n_lights = s->d.n_lights;
+    facts.light_samples = s->light_samples.data();
+    // The plan is one function, so what it reads of the device is fetched here, ahead of every refusal; what stays at its old
+    // place among the refusals is where a FAILURE of these calls is reported (RenderJob::run). choose_trace writes a refusal
+    // straight into last_error: it is moved aside into trace_refusal (last_error keeps what it held) and comes back through the
+    // plan only when its turn among the refusals is reached. A render refused for its parameters, or one without tiles, now pays
+    // a hipMemGetInfo it did not pay before.
+    std::string trace_refusal = ctx->last_error;
+    const TraceChoice trace = choose_trace(s);
+    if (!trace.ok) {
+        std::swap(trace_refusal, ctx->last_error);
+        facts.trace_refusal = trace_refusal.c_str();
+    }
+    // the free device bytes, where the caller leaves the pass size to the library (li and export fix it themselves)
+    size_t free_b = 0, total_b = 0;
+    hipError_t mem_query = hipSuccess;
+    if (call == RenderCall::Frame && rp_in.spp_per_pass <= 0) {
+        mem_query = hipMemGetInfo(&free_b, &total_b);
+        for (const auto& b : ctx->block_cache)
+            if (!b.in_use) free_b += b.bytes;  // blocks kept from the previous render are available to this one
+    }
+    RenderJob job{plan_render(rp_in, call, li ? li->n : 0, camera.kind, facts, free_b), s, ctx, ctx->stream, li, d_film, camera_motion, trace, mem_query};
     return job.run(camera, stats);
 }
 #undef RENDER_TRY
